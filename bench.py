@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: depth maps / second at 480x640, bf16, HIP kernels only.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--dump-outputs DIR] [--detail FILE]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,7 +12,10 @@ synthetic 480x640 images + 8x8 ToF zones that is already resident in HBM (BASELI
 configs[1]).  Inference does not shard: with N > 1 every rank runs an independent replica on its
 own batch (no data-path collective) and `value` is the sum over ranks = N*batch*K / max-rank-time.
 
-The JSON line also carries
+The run ends with ONE short JSON line (strict JSON, < 4 KB: `ms_per_step` = milliseconds of one of the `--steps` timed steps) that
+carries a summary of each of the objects below; `--detail FILE` writes them whole.  `--dump-outputs DIR` saves what the timed path
+returned in its last timed step (bin edges, pred, a fixed sample of prob) as .npy files, so that two builds can be compared on
+identical inputs.  The objects:
   roofline      the dominant kernel family by GPU time (timed with HIP events around every launch
                 of an instrumented pass on the same stream), algorithmic FLOPs / bytes vs peak
   dw3x3         the encoder's depthwise 3x3 kernels against the HBM roofline (north_star target)
@@ -71,6 +74,11 @@ def parse():
                     help="process-group backend of --train (nccl = RCCL over xGMI; gloo stages the gradient buckets through host memory: "
                          "several ranks can then share one GPU, and with --force-dist a single rank exercises the whole DDP path)")
     ap.add_argument("--force-dist", action="store_true", help="create the process group even for one rank (measures allreduce_ms / overlap_frac at N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step to DIR/<name>.npy (float32, float64 scalars as float64; rank 0; "
+                         "<= 48 MB: prob and --train's parameters as fixed seeded samples)")
+    ap.add_argument("--detail", metavar="FILE", default=None,
+                    help="write the whole result object (per-tile / per-shape / per-family tables, protocols) to FILE; stdout gets the short line")
     return ap.parse_args()
 
 
@@ -649,7 +657,8 @@ def allreduce_plan(tr, inp, target, measure_window: bool):
     return out
 
 
-def training_step_rate(batch: int, dev, steps: int = 6, dist=None, world: int = 1, warmup: int = 2, fidelity: bool = False, dtype=None):
+def training_step_rate(batch: int, dev, steps: int = 6, dist=None, world: int = 1, warmup: int = 2, fidelity: bool = False, dtype=None,
+                       dump_dir=None):
     """BASELINE.json configs[2..3] shape: 416x544 crops, 6x6 zones of 64 px, `batch` samples per GPU, 16-bit activations with
     float32 master parameters; one step = training forward + SILog + backward (+ gradient all-reduce) + AdamW/OneCycle, replayed as
     HIP graphs.  Headline storage type: fp16 (IEEE half, overflow-guarded optimizer) -- its gradient is the float32 one to a cosine
@@ -676,12 +685,16 @@ def training_step_rate(batch: int, dev, steps: int = 6, dist=None, world: int = 
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        loss, _, _ = tr.step(inp, target)
+        loss, lr, beta1 = tr.step(inp, target)
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
     dt = max_over_ranks(time.perf_counter() - t0, dist, dev) / steps
+    if dump_dir is not None:
+        # what the step returns, and the master parameters it updated (a sample: 21.6 M float32)
+        dump_outputs(dump_dir, {"loss": loss.reshape(1), "lr": torch.tensor([float(lr)], dtype=torch.float64),
+                                "beta1": torch.tensor([float(beta1)], dtype=torch.float64), "params": tr.flat.param})
     extra = {}
     if dist is not None:
         # what the gradient averaging costs and how much of it the split step hides: the same steps with the buckets reduced after
@@ -753,8 +766,126 @@ def training_step_rate(batch: int, dev, steps: int = 6, dist=None, world: int = 
             "loss_first_step": l0, "loss_after_%d_steps" % (steps + 2): loss_last}
 
 
+def _pick(d, keys):
+    return {k: d[k] for k in keys if k in d} if isinstance(d, dict) else None
+
+
+def _finite(o, bad=None, path=""):
+    """Strict JSON: NaN / inf become null, and the dotted path of each one is appended to `bad` so that the line can say which
+    figures were not finite (a diverged loss must stay visible)."""
+    if isinstance(o, float):
+        if o == o and abs(o) != float("inf"):
+            return o
+        if bad is not None:
+            bad.append(path)
+        return None
+    if isinstance(o, dict):
+        return {k: _finite(v, bad, f"{path}.{k}" if path else str(k)) for k, v in o.items()}
+    if isinstance(o, (list, tuple)):
+        return [_finite(v, bad, f"{path}[{i}]") for i, v in enumerate(o)]
+    return o
+
+
+RESULT_LINE_MAX = 4096      # the result line is read from the tail of the output: it must stay short
+
+
+def result_line(line: dict) -> str:
+    """The ONE stdout line of a run: the headline figures and a one-level summary of every appendix, strict JSON, < 4 KB.  The
+    whole object (per-tile, per-shape and per-family tables, protocols, all-reduce plan) goes to `--detail FILE`.  A figure that
+    is NaN or infinite is written as null and named in `non_finite`."""
+    keep = ("metric", "value", "unit", "per_gpu", "n_gpus", "ranks_seen", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+            "vs_baseline", "dtype", "data", "rel_l1", "abs_rel", "rel_l1_worst_image", "gate", "gate_met", "kernel_ms_total", "cpu_baseline",
+            "loss_first_step", "allreduce_ms", "overlap_frac", "ms_per_step_sequential_allreduce", "ms_per_step_no_allreduce")
+    out = _pick(line, keep)
+    if "ms_per_step_repeats" in line:
+        out["ms_per_step_repeats"] = _pick(line["ms_per_step_repeats"], ("min", "median", "max"))
+    if "config" in line:
+        cfg = line["config"]
+        out["config"] = _pick(cfg, ("workload", "layers", "launch", "parallelism", "n_gpus", "global_batch"))
+        if "parity" in cfg:
+            out["config"]["parity"] = _pick(cfg["parity"], ("rel_l1", "gate_met"))
+        if "compliant_default" in cfg:
+            out["config"]["compliant_default"] = _pick(cfg["compliant_default"], ("dtype", "value", "ms_per_step", "rel_l1", "gate_met_on_every_family"))
+    if "roofline" in line:
+        out["roofline"] = _pick(line["roofline"], ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic", "traffic_source",
+                                                   "algorithmic_bytes_per_launch", "launches_per_step", "avg_launch_us"))
+    if "dw3x3" in line:
+        out["dw3x3"] = {line.get("dtype"): {"frac_of_measured_copy": line["dw3x3"].get("frac_of_measured_copy_in_graph"),
+                                            "met": line["dw3x3"].get("target", {}).get("met")}}
+    for key in ("f16", "f32", "f32x3"):
+        if key in line:
+            out[key] = _pick(line[key], ("value", "ms_per_step", "rel_l1", "gate_met", "gate_met_on_every_family"))
+    x3 = line.get("f32x3", {})
+    if "roofline" in x3:
+        out["f32x3"]["roofline"] = _pick(x3["roofline"], ("kernel", "bound", "achieved", "unit", "frac"))
+    if "dw3x3" in x3:
+        out.setdefault("dw3x3", {})["f32x3"] = {"frac_of_measured_copy": x3["dw3x3"].get("frac_of_measured_copy_in_graph"),
+                                                "met": x3["dw3x3"].get("target", {}).get("met")}
+    if "latency" in line:
+        lat = line["latency"]
+        out["latency"] = {m: {k: v["ms"] for k, v in src.items() if k.startswith("latency_b")}
+                          for m, src in ((line.get("dtype"), lat), ("f32x3", lat.get("f32x3", {}))) if src}
+    if "training" in line:
+        t = line["training"]
+        out["training"] = _pick(t, ("value", "unit", "ms_per_step", "per_gpu", "dtype", "allreduce_ms", "overlap_frac", "loss_first_step"))
+        if "config" in t:
+            out["training"]["config"] = _pick(t["config"], ("n_gpus", "global_batch"))
+        if "fidelity_vs_f32_same_batch" in t:
+            out["training"]["gradient_cosine_vs_f32"] = {k: v["gradient_cosine"] for k, v in t["fidelity_vs_f32_same_batch"].items()}
+        if "roofline" in t:
+            out["training"]["roofline"] = _pick(t["roofline"], ("kernel", "bound", "achieved", "unit", "frac", "launches_per_step"))
+        if "bf16" in t:
+            out["training"]["bf16"] = _pick(t["bf16"], ("value", "ms_per_step"))
+    bad = []
+    out = _finite(out, bad)
+    if bad:
+        out["non_finite"] = bad
+    s = json.dumps(out, separators=(",", ":"), allow_nan=False)
+    for k in ("latency", "f32", "dw3x3", "training"):      # never expected; the least needed summaries go first (`non_finite` stays)
+        if len(s) < RESULT_LINE_MAX:
+            break
+        out.pop(k, None)
+        s = json.dumps(out, separators=(",", ":"), allow_nan=False)
+    return s
+
+
+DUMP_MAX_VALUES = 12_000_000         # 48 MB of float32 over all the files --dump-outputs writes (limit: 64 MB)
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """What the timed path handed its caller in the last timed step, as DIR/<name>.npy (float32; float64 stays float64).  When the
+    whole set exceeds DUMP_MAX_VALUES, each tensor above a quarter of the budget (the [B,256,H/2,W/2] prob, the flat parameters) is
+    written as a fixed sample, `<name>_sample.npy`, and the smaller ones are written whole.  The sample positions are drawn with
+    replacement (a position may repeat: harmless for a comparison) from a generator with a fixed seed and sorted, so they are
+    the same on every run and two builds can be compared element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: t.detach() for k, t in arrays.items() if t is not None}
+    big = DUMP_MAX_VALUES // 4 if sum(t.numel() for t in arrays.values()) > DUMP_MAX_VALUES else DUMP_MAX_VALUES
+    left = DUMP_MAX_VALUES - sum(t.numel() for t in arrays.values() if t.numel() <= big)     # what the sampled tensors share
+    n_big = sum(1 for t in arrays.values() if t.numel() > big)
+    for name, t in arrays.items():
+        if t.numel() <= big:
+            np.save(os.path.join(out_dir, name + ".npy"), (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy())
+            continue
+        g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+        idx = torch.randint(0, t.numel(), (left // n_big,), generator=g).sort().values
+        np.save(os.path.join(out_dir, name + "_sample.npy"), t.reshape(-1)[idx.to(t.device)].float().cpu().numpy())
+
+
 def main():
     a = parse()
+
+    def emit(line):
+        if a.detail:
+            bad = []
+            full = _finite(line, bad)
+            with open(a.detail, "w") as f:
+                json.dump({**full, "non_finite": bad} if bad else full, f, indent=1, allow_nan=False)
+        print(result_line(line), flush=True)
+
+    torch.manual_seed(0)        # torch's global generator, which Trainer.draw_pos_offsets draws the training step's positional windows from: same draws every run
     rank, world, local, dist = init_dist(a.backend, force=a.force_dist)
     ndev = max(1, torch.cuda.device_count())       # (counting devices does not initialise the GPU)
     local_dev = local % ndev                        # more ranks than GPUs (the 2-ranks-on-one-GPU gloo test of the driver command): they share a device
@@ -764,14 +895,15 @@ def main():
                   "devices_visible": ndev, "ranks_per_device": (world + ndev - 1) // ndev}
 
     if a.train:
-        r = training_step_rate(a.train_batch, dev, steps=a.steps, dist=dist, world=world, warmup=a.warmup)
+        r = training_step_rate(a.train_batch, dev, steps=a.steps, dist=dist, world=world, warmup=a.warmup,
+                               dump_dir=a.dump_outputs if rank == 0 else None)
         if rank == 0:
-            print(json.dumps({"metric": "training samples/sec @ 416x544, 16-bit activations (whole job: forward + SILog + backward + gradient all-reduce + AdamW)",
-                              "value": r["value"], "unit": "samples/s", "per_gpu": r["value"] / world, "n_gpus": world, "steps": a.steps,
-                              "warmup": a.warmup, "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "weak",
-                              "vs_baseline": None, "dtype": r["dtype"], "data": "synthetic", "config": r["config"],
-                              "loss_first_step": r["loss_first_step"],
-                              **{k: r[k] for k in ("allreduce_ms", "overlap_frac", "ms_per_step_sequential_allreduce", "ms_per_step_no_allreduce", "allreduce", "allreduce_plan") if k in r}}))
+            emit({"metric": "training samples/sec @ 416x544, 16-bit activations (whole job: forward + SILog + backward + gradient all-reduce + AdamW)",
+                  "value": r["value"], "unit": "samples/s", "per_gpu": r["value"] / world, "n_gpus": world, "steps": a.steps,
+                  "warmup": a.warmup, "ms_per_step": r["ms_per_step"], "higher_is_better": True, "scaling": "weak",
+                  "vs_baseline": None, "dtype": r["dtype"], "data": "synthetic", "config": r["config"],
+                  "loss_first_step": r["loss_first_step"],
+                  **{k: r[k] for k in ("allreduce_ms", "overlap_frac", "ms_per_step_sequential_allreduce", "ms_per_step_no_allreduce", "allreduce", "allreduce_plan") if k in r}})
         if dist:
             dist.barrier()
             dist.destroy_process_group()
@@ -819,14 +951,19 @@ def main():
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
+    last = None
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = max_over_ranks(time.perf_counter() - t0, dist, dev)
+    if a.dump_outputs and rank == 0 and last is not None:
+        # the results of the last timed step, read before anything else replays (an in-flight slot's outputs live until its next turn)
+        edges, pred, prob = last[0] if a.inflight > 1 and not a.eager else last
+        dump_outputs(a.dump_outputs, {"bin_edges": edges, "pred": pred, "prob": prob})
     # the line's own noise estimate: the same K-step region five more times (each synchronised), per-step time of each
     repeats = []
     for _ in range(5):
@@ -1116,7 +1253,7 @@ def main():
         if x3 is not None and "f32x3" not in line:      # --config5: the default mode timed under the same protocol (parity: tests/test_forward_gpu.py's config5 case)
             line["f32x3"] = {"value": a.batch * a.steps / x3[1], "unit": "maps/s", "ms_per_step": x3[1] / a.steps * 1e3, "dtype": "f32x3",
                              "launch": "same as the headline line", "note": "the drop-in boundary's default numerics (float32 storage, f16x3 matrix math, float32 prob)"}
-        print(json.dumps(line))
+        emit(line)
     if dist:
         dist.barrier()
         dist.destroy_process_group()

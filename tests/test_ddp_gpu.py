@@ -244,7 +244,7 @@ def test_the_driver_command_for_two_ranks_runs_end_to_end(tmp_path):
     two ranks on this box's one GPU over gloo (RCCL cannot put two ranks on one device), started as a FRESH child process before
     anything in it touches the GPU: inference replicas with in-flight slots, teardown, then the data-parallel training leg with its
     gradient all-reduce -- the whole sequence, parsed from the one JSON line rank 0 prints."""
-    import json, os, socket, subprocess, sys
+    import json, math, os, socket, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -261,4 +261,5 @@ def test_the_driver_command_for_two_ranks_runs_end_to_end(tmp_path):
     t = d["training"]
     assert t["config"]["n_gpus"] == 2 and t["config"]["global_batch"] == 8
     assert "allreduce_ms" in t and "overlap_frac" in t and t["ms_per_step"] > 0
-    assert t["loss_first_step"] == t["loss_first_step"]          # finite, not NaN
+    assert isinstance(t["loss_first_step"], float) and math.isfinite(t["loss_first_step"]), t["loss_first_step"]    # finite, not NaN / null
+    assert "non_finite" not in d, d["non_finite"]                # no figure of the line was NaN or infinite
