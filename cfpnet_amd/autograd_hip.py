@@ -35,7 +35,7 @@ class V:
 class P(V):
     """A parameter: `t` in the layout the kernels want, `g` accumulated in float32 in the same layout;
     `to_torch(g)` converts a gradient back to the reference's state_dict layout."""
-    __slots__ = ("name", "to_torch", "gview", "wt", "geom")
+    __slots__ = ("name", "to_torch", "gview", "wt", "geom", "pk", "pkt", "fgeom")
 
     def __init__(self, name: str, t: torch.Tensor, to_torch: Callable[[torch.Tensor], torch.Tensor], gview: Optional[torch.Tensor] = None):
         super().__init__(t, True)
@@ -43,6 +43,10 @@ class P(V):
         self.gview = gview          # preallocated (zeroed) float32 gradient in the kernel layout: kernels write into it directly
         self.wt = None              # conv weights: the flipped copy for the data gradient, when the trainer refreshes all of them in one launch
         self.geom = None            # conv weights whose data gradient is needed: (Cout, KH, KW, Cin), recorded by Tape.conv
+        # f16x3 numerics: the pre-split operands (ops.pack_w_x3 layout) of the forward (`pk`) and of the data gradient (`pkt`: the flipped
+        # weights; for a patch conv, k == stride, the transposed ones = the flip of a 1x1 conv over k*k*Cin channels) when the trainer packs
+        # them all in one launch per step, and the forward geometry (Cout, KH, KW, Cin) that packing needs
+        self.pk, self.pkt, self.fgeom = None, None, None
 
 
 def _act(t: torch.Tensor) -> ops.Act:
@@ -53,11 +57,17 @@ def _act(t: torch.Tensor) -> ops.Act:
 
 
 class Tape:
-    def __init__(self, device, dtype=torch.float32, side: Optional[torch.cuda.Stream] = None):
-        """`side`: a second stream for the parameter-gradient kernels (weight / bias gradients): nothing later in the backward
+    def __init__(self, device, dtype=torch.float32, side: Optional[torch.cuda.Stream] = None, x3: bool = False):
+        """`x3`: the f16x3 training numerics (float32 storage, so `dtype` is float32): the dense conv / Linear GEMMs of the forward, the
+        data gradient and the weight gradient run in split precision (hi / lo IEEE halves, three f16 MFMAs per block, float32 accumulate);
+        their dY operand carries a power-of-two scale from max|dY| (train_ops.grad_absmax) so that the small activation gradients keep
+        their bits in the halves.  Every other op is the float32 tape's.
+        `side`: a second stream for the parameter-gradient kernels (weight / bias gradients): nothing later in the backward
         reads them, so they leave the critical path dY -> dX -> ... and run beside it (forked and joined inside a captured step
         as graph edges).  Every tensor they read stays referenced by the tape until `backward()` has joined the streams."""
         self.dev, self.dtype = torch.device(device), dtype
+        self.x3 = bool(x3)
+        assert not self.x3 or dtype == torch.float32, "the f16x3 numerics keep float32 storage"
         self.bw: List[Callable[[], None]] = []
         self._const: Dict[Tuple[str, int], torch.Tensor] = {}
         self.side, self._forked = side, False
@@ -174,6 +184,8 @@ class Tape:
         leaves the per-row-tile channel moments of its output beside it (V.mom) and bn_act merges them instead of reading the tensor."""
         Cout = w.t.shape[0]
         y = V(self.new(B * Ho * Wo, Cout, x.t.dtype))
+        if self.x3:
+            return self._conv_x3(x, w, bias, y, B, H, W, k, stride, pt, pl, Ho, Wo)
         # split-K slabs (few rows, long K: the sr convs) in the 16-bit modes; float32 parity mode keeps its single summation chain
         nws = ops.conv2d_ws_bytes(B * Ho * Wo, Cout, w.t.shape[1], ops.DT[x.t.dtype]) if x.t.dtype != torch.float32 else 0
         ws = torch.empty(nws // 4, dtype=torch.float32, device=self.dev) if nws else None
@@ -225,6 +237,53 @@ class Tape:
                     x.g, x.g_owned = dx, True
                 else:
                     self.acc(x, train_ops.conv2d_dgrad(g, wt, B, H, W, x.C, k, k, stride, pt, pl, Ho, Wo))
+        self.bw.append(bw)
+        return y
+
+    def _conv_x3(self, x: V, w: P, bias: Optional[P], y: V, B, H, W, k, stride, pt, pl, Ho, Wo) -> V:
+        """Tape.conv in the f16x3 numerics: the same forward / backward structure with the split-precision kernels."""
+        Cout, Cin = w.t.shape[0], x.C
+        w.fgeom = (Cout, k, k, Cin)
+        pk = w.pk if w.pk is not None else ops.pack_w_x3(w.t)
+        M, K = B * Ho * Wo, k * k * Cin
+        nws = ops.conv2d_ws_bytes(M, Cout, K, hip.F32X3)
+        ws = torch.empty(nws // 4, dtype=torch.float32, device=self.dev) if nws else None
+        ops.conv2d(_act(x.t), pk, None, bias.t if bias is not None else None, _act(y.t), B, H, W, k, k, stride, pt, pl, Ho, Wo, ws=ws)
+        patch = k == stride and k > 1 and pt == 0 and pl == 0
+        if x.needs_grad:
+            w.geom = (Cout, 1, 1, K) if patch else (Cout, k, k, Cin)
+
+        def bw():
+            g = y.g
+            if g is None:
+                return
+            sc = train_ops.grad_absmax(g)             # device int32: the dY scale both GEMMs of this layer read
+
+            def param_grads():
+                if bias is not None:
+                    self.pgrad(bias, lambda out, beta: train_ops.colsum(g, out=out, beta=beta))
+                self.pgrad(w, lambda out, beta: train_ops.conv2d_wgrad(x.t, g, B, H, W, k, k, stride, pt, pl, Ho, Wo, dw=out, beta=beta,
+                                                                       queue=self._queue(out, beta), x3=True, dy_scale=sc))
+            self.off_path(param_grads)
+            if not x.needs_grad:
+                return
+            if patch:
+                # non-overlapping patches: dX = dY [M, Cout] x W [Cout, k*k*Cin] + depth-to-space (see Tape.conv), the GEMM as the data
+                # gradient of a 1x1 conv over k*k*Cin channels
+                pkt = w.pkt if w.pkt is not None else ops.pack_w_x3(w.t.t().contiguous())
+                tmp = train_ops.conv2d_dgrad(g, pkt, 1, M, 1, K, 1, 1, 1, 0, 0, M, 1, x3=True, dy_scale=sc)
+                self.acc(x, train_ops.index_rows(tmp.view(M * k * k, Cin), self._patch_map(B, H, W, k, Ho, Wo)))
+                return
+            pkt = w.pkt if w.pkt is not None else ops.pack_w_x3(train_ops.conv2d_weight_flip(w.t, Cout, k, k, Cin))
+            if x.g is not None and x.g_owned:
+                train_ops.conv2d_dgrad(g, pkt, B, H, W, Cin, k, k, stride, pt, pl, Ho, Wo, dx=x.g, accumulate=True, x3=True, dy_scale=sc)
+            elif x.g is not None:
+                # shared (not ours to overwrite): read it as the residual of the data-gradient conv, write a fresh tensor
+                dx = self.new(B * H * W, Cin)
+                train_ops.conv2d_dgrad(g, pkt, B, H, W, Cin, k, k, stride, pt, pl, Ho, Wo, dx=dx, res=x.g, x3=True, dy_scale=sc)
+                x.g, x.g_owned = dx, True
+            else:
+                self.acc(x, train_ops.conv2d_dgrad(g, pkt, B, H, W, Cin, k, k, stride, pt, pl, Ho, Wo, x3=True, dy_scale=sc))
         self.bw.append(bw)
         return y
 

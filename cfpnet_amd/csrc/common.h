@@ -115,6 +115,19 @@ __device__ __forceinline__ void split8(const f32x4& x0, const f32x4& x1, f16x8& 
   }
 }
 
+// ---- power-of-two scale of an activation GRADIENT before its f16x3 split (training, conv_bwd.hip) ----
+// `maxbits` holds the float32 bits of max|dY| (cfp_grad_absmax).  The scale 2^e puts that maximum into [2^14, 2^15): the hi halves stay
+// normal down to 2^-38 of the maximum and far from the half range's top.  Multiplying by 2^e and by 2^-e afterwards is exact (no float32
+// result here is subnormal), so a gradient scaled by any power of two gives the same result scaled by it, bit for bit.  No word: e = 0.
+__device__ __forceinline__ int grad_exp2(const int* maxbits) {
+  if (!maxbits) return 0;
+  const unsigned m = (unsigned)*maxbits;
+  if (m == 0u) return 0;
+  const int e = 14 - ((int)((m >> 23) & 255u) - 127);
+  return e < -126 ? -126 : (e > 126 ? 126 : e);
+}
+__device__ __forceinline__ float exp2i(int e) { return __int_as_float((127 + e) << 23); }      // 2^e, -126 <= e <= 127
+
 // Two f32 -> one packed dword of H (low half = first element).
 template <typename H> __device__ __forceinline__ uint32_t pack2(float a, float b);
 template <> __device__ __forceinline__ uint32_t pack2<bf16_t>(float a, float b) {

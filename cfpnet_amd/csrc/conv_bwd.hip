@@ -332,6 +332,200 @@ __global__ __launch_bounds__(256) void conv_wgrad16_kernel(WgP p) {
       }
 }
 
+// Float32 inputs on the 16-bit matrix cores in split precision (dtype CFP_F32X3, the f16x3 training numerics): the loader splits every
+// staged float32 value of X and of dY * 2^e (split8: x = hi + lo, hi truncated to half, lo = half(x - hi)) into a hi and a lo LDS plane,
+// and every 16 x 16 x 32 block is  dY_lo X_hi + dY_hi X_lo + dY_hi X_hi  -- three v_mfma_f32_16x16x32_f16 into one float32 accumulator.
+// Operand reads are the 16-bit kernel's transpose reads on each plane.  dY carries the power-of-two scale of `dy_exp` (grad_exp2):
+// multiplied in before the split, divided out of the accumulator on the way to the slab (both exact), so the reduction of the slabs is
+// the float32 kernel's.  One tile shape (64 x 64, 64 pixel rows per barrier pair); X is never scaled (the forward's split).
+template <bool PW>
+__global__ __launch_bounds__(256) void conv_wgrad_x3_kernel(WgP p, const int* __restrict__ dy_exp) {
+  constexpr int MS = 64, T = WB, PT = T + 8;
+  __shared__ __attribute__((aligned(16))) unsigned short sDh[MS * PT];
+  __shared__ __attribute__((aligned(16))) unsigned short sDl[MS * PT];
+  __shared__ __attribute__((aligned(16))) unsigned short sXh[MS * PT];
+  __shared__ __attribute__((aligned(16))) unsigned short sXl[MS * PT];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tiles_k = (p.K + T - 1) / T;
+  int tile, split;
+  if (p.xcd_order) {
+    const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
+    tile = slot % p.ntiles; split = (slot / p.ntiles) * 8 + xcd;
+  } else {
+    tile = blockIdx.x % p.ntiles; split = blockIdx.x / p.ntiles;
+  }
+  if (split >= p.nsplit) return;
+  const int tile_co = tile / tiles_k, tile_k = tile - tile_co * tiles_k;
+  const int co0 = tile_co * T, k0 = tile_k * T;
+  const int m_begin = split * p.rows_per_split;
+  const int m_end = min(p.M, m_begin + p.rows_per_split);
+  const float* __restrict__ X = reinterpret_cast<const float*>(p.x);
+  const float* __restrict__ DY = reinterpret_cast<const float*>(p.dy);
+  const int e = grad_exp2(dy_exp);
+  const float up = exp2i(e), down = exp2i(-e);
+  constexpr int NV = MS * (T / 4) / 256;             // 16-byte float32 vectors per thread, step and operand (4)
+  int v_row[NV], v_col[NV], x_kh[NV], x_kw[NV], x_ci[NV];
+  bool k_ok[NV], co_ok[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int q = tid + i * 256;
+    v_row[i] = q / (T / 4);
+    v_col[i] = (q - v_row[i] * (T / 4)) * 4;
+    const int kk = k0 + v_col[i];
+    k_ok[i] = kk < p.K;
+    const int tap = kk / p.Cin;                      // Cin % 4 == 0 keeps a vector inside one tap
+    x_ci[i] = kk - tap * p.Cin;
+    x_kh[i] = tap / p.KW;
+    x_kw[i] = tap - x_kh[i] * p.KW;
+    co_ok[i] = co0 + v_col[i] < p.Cout;
+  }
+  const int HoWo = p.Ho * p.Wo;
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 rD[NV], rX[NV];
+  auto fetch = [&](int m0) {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int m = m0 + v_row[i];
+      const bool m_ok = m < m_end;
+      const int mm = m_ok ? m : m_begin;
+      bool in_ok;
+      long long xrow;
+      if (PW) {
+        in_ok = m_ok && k_ok[i];
+        xrow = mm;
+      } else {
+        const int b = fastdiv(mm, p.mg_hw, p.sh_hw), r = mm - b * HoWo;
+        const int ho = fastdiv(r, p.mg_w, p.sh_w), wo = r - ho * p.Wo;
+        const int hi = ho * p.stride - p.pad_t + x_kh[i], wi = wo * p.stride - p.pad_l + x_kw[i];
+        in_ok = m_ok && k_ok[i] && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
+        const int hic = min(max(hi, 0), p.H - 1), wic = min(max(wi, 0), p.W - 1);
+        xrow = (long long)(b * p.H + hic) * p.W + wic;
+      }
+      const f32x4 vx = *reinterpret_cast<const f32x4*>(X + xrow * p.x_ld + (k_ok[i] ? x_ci[i] : 0));
+      rX[i] = in_ok ? vx : zero4;
+      const f32x4 vd = *reinterpret_cast<const f32x4*>(DY + (long long)mm * p.dy_ld + (co_ok[i] ? co0 + v_col[i] : 0));
+      rD[i] = (m_ok && co_ok[i]) ? vd * up : zero4;
+    }
+  };
+  typedef _Float16 h4_t __attribute__((ext_vector_type(4)));
+  auto put = [&](unsigned short* ph, unsigned short* pl, int at, const f32x4& v) {
+    f16x8 h, l;
+    split8(v, zero4, h, l);
+    *reinterpret_cast<h4_t*>(ph + at) = h4_t{h[0], h[1], h[2], h[3]};
+    *reinterpret_cast<h4_t*>(pl + at) = h4_t{l[0], l[1], l[2], l[3]};
+  };
+  auto stash = [&]() {
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      put(sXh, sXl, v_row[i] * PT + v_col[i], rX[i]);
+      put(sDh, sDl, v_row[i] * PT + v_col[i], rD[i]);
+    }
+  };
+  constexpr int TI = T / 32, TJ = T / 32;
+  const int qa = (wave >> 1) * (T / 2), qb = (wave & 1) * (T / 2);
+  const int g = lane >> 4, idx = lane & 15, tq = idx >> 2, tp = idx & 3;
+  const int blk = (8 * g + tq) * PT + 4 * tp;
+  auto tr = [&](const unsigned short* base) -> s16x8 {
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(base + 4 * PT));
+    return s16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+  };
+  f32x4 acc[TI][TJ];
+#pragma unroll
+  for (int i = 0; i < TI; ++i)
+#pragma unroll
+    for (int j = 0; j < TJ; ++j) acc[i][j] = zero4;
+  if (m_begin < m_end) fetch(m_begin);
+  for (int m0 = m_begin; m0 < m_end; m0 += MS) {
+    __syncthreads();
+    stash();
+    __syncthreads();
+    if (m0 + MS < m_end) fetch(m0 + MS);
+#pragma unroll
+    for (int ks = 0; ks < MS / 32; ++ks) {
+      s16x8 ah[TI], al[TI], bh[TJ], bl[TJ];
+#pragma unroll
+      for (int i = 0; i < TI; ++i) {
+        const int o = ks * 32 * PT + blk + qa + i * 16;
+        ah[i] = tr(sDh + o); al[i] = tr(sDl + o);
+      }
+#pragma unroll
+      for (int j = 0; j < TJ; ++j) {
+        const int o = ks * 32 * PT + blk + qb + j * 16;
+        bh[j] = tr(sXh + o); bl[j] = tr(sXl + o);
+      }
+#pragma unroll
+      for (int i = 0; i < TI; ++i)
+#pragma unroll
+        for (int j = 0; j < TJ; ++j) {
+          acc[i][j] = mfma16<f16_t>(al[i], bh[j], acc[i][j]);      // the small terms first
+          acc[i][j] = mfma16<f16_t>(ah[i], bl[j], acc[i][j]);
+          acc[i][j] = mfma16<f16_t>(ah[i], bh[j], acc[i][j]);
+        }
+    }
+  }
+  const int fr = lane & 15, fk = lane >> 4;
+  float* __restrict__ slab = p.slabs + (long long)split * p.Cout * p.K;
+#pragma unroll
+  for (int i = 0; i < TI; ++i)
+#pragma unroll
+    for (int j = 0; j < TJ; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int co = co0 + qa + i * 16 + fk * 4 + r, kk = k0 + qb + j * 16 + fr;
+        if (co < p.Cout && kk < p.K) slab[(long long)co * p.K + kk] = acc[i][j][r] * down;
+      }
+}
+
+__global__ void grad_word_zero_kernel(int* __restrict__ word) {
+  if (threadIdx.x == 0) *word = 0;
+}
+
+// max |x| over a float32 [rows][C] tensor as float32 bits in *word (zeroed by grad_word_zero_kernel just before): a workgroup maximum, then
+// one integer atomic per workgroup (non-negative floats order as their bit patterns; the maximum does not depend on the order, so the
+// result is deterministic).  One atomic per WAVE over ~1000 workgroups serialised on the one address: 45 us per call, 11 ms per step.
+__global__ __launch_bounds__(256) void grad_absmax_kernel(const float* __restrict__ x, int ld, FastDiv cv, unsigned total, int* __restrict__ word) {
+  __shared__ unsigned wmax[4];
+  unsigned m = 0u;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+    unsigned r, c;
+    fd_rowcol(i, cv, r, c);
+    const f32x4 v = *reinterpret_cast<const f32x4*>(x + (long long)r * ld + c * 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) m = max(m, __float_as_uint(v[e]) & 0x7fffffffu);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, off));
+  if ((threadIdx.x & 63) == 0) wmax[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    m = max(max(wmax[0], wmax[1]), max(wmax[2], wmax[3]));
+    if (m) atomicMax(reinterpret_cast<unsigned*>(word), m);
+  }
+}
+
+// out [B][Hd][Wd][C] (Hd = (Ho-1) dil + 1, ...) = dY * 2^e with dil - 1 zero pixels between dY's pixels (dil = 1: a scaled copy), and
+// inv[0 .. n_inv) = 2^-e: the per-channel epilogue scale of the convolution that reads `out`
+__global__ __launch_bounds__(256) void grad_scale_kernel(const float* __restrict__ dy, int ld, int Ho, int Wo, int dil, FastDiv cv,
+                                                         FastDiv wd, FastDiv hd, unsigned total, const int* __restrict__ word,
+                                                         float* __restrict__ out, float* __restrict__ inv, int n_inv) {
+  const int e = grad_exp2(word);
+  const float up = exp2i(e);
+  if (blockIdx.x == 0)
+    for (int t = threadIdx.x; t < n_inv; t += 256) inv[t] = exp2i(-e);
+  const int C = (int)cv.d * 4;
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
+    unsigned pix, c, t, x, y, b;
+    fd_rowcol(i, cv, pix, c);
+    fd_rowcol(pix, wd, t, x);
+    fd_rowcol(t, hd, b, y);
+    f32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (y % dil == 0 && x % dil == 0)
+      v = *reinterpret_cast<const f32x4*>(dy + ((long long)(b * Ho + y / dil) * Wo + x / dil) * ld + c * 4) * up;
+    *reinterpret_cast<f32x4*>(out + (long long)pix * C + c * 4) = v;
+  }
+}
+
 // dw = beta * dw + sum over the splits, in a fixed order.  EW consecutive elements per workgroup, 256 / EW lanes over the splits:
 // a small weight tensor split 768 ways (32x32 Linear over 2*10^5 rows) is a long dependent chain per element, so the splits are
 // walked by up to 8 lanes with 4 loads in flight each, and the lanes meet in LDS in lane order.
@@ -545,10 +739,13 @@ extern "C" int cfp_conv2d_wgrad(const void* x, int x_ld, const void* dy, int dy_
 
 static int wgrad_impl(const void* x, int x_ld, const void* dy, int dy_ld, float* dw, float* db, int B, int H, int W, int Cin,
                       int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, float beta, float beta_b,
-                      int dtype, void* ws, size_t ws_bytes, cfp_wgrad_job* job, cfp_stream_t stream) {
+                      int dtype, void* ws, size_t ws_bytes, cfp_wgrad_job* job, cfp_stream_t stream, const int* dy_exp = nullptr) {
   CFP_REQUIRE(x && dy && dw && ws, CFP_EINVAL, "cfp_conv2d_wgrad: null pointer");
-  CFP_REQUIRE(!db || is16(dtype), CFP_EINVAL, "cfp_conv2d_wgrad_bias: the fused bias gradient is a 16-bit path (float32: cfp_colsum)");
+  CFP_REQUIRE(!db || is16(dtype), CFP_EINVAL, "cfp_conv2d_wgrad_bias: the fused bias gradient is a 16-bit path (float32 / f16x3: cfp_colsum)");
+  const bool x3 = dtype == CFP_F32X3;                         // float32 tensors, split-precision matrix math
+  if (x3) dtype = CFP_F32;
   CFP_REQUIRE(dtype_ok(dtype), CFP_EINVAL, "cfp_conv2d_wgrad: bad dtype");
+  CFP_REQUIRE(!dy_exp || (x3 && (reinterpret_cast<uintptr_t>(dy_exp) & 3) == 0), CFP_EINVAL, "cfp_conv2d_wgrad: a gradient scale is an f16x3 input");
   const int ve = vec_elems(dtype);
   CFP_REQUIRE(B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && Ho > 0 && Wo > 0, CFP_ESHAPE,
               "cfp_conv2d_wgrad: non-positive dimension");
@@ -565,7 +762,7 @@ static int wgrad_impl(const void* x, int x_ld, const void* dy, int dy_ld, float*
   p.Ho = Ho; p.Wo = Wo; p.M = (int)M; p.K = (int)K;
   fastdiv_make((unsigned)(Ho * Wo), &p.mg_hw, &p.sh_hw);
   fastdiv_make((unsigned)Wo, &p.mg_w, &p.sh_w);
-  const WgPlan pl = is16(dtype) ? wgrad_plan16(Cout, (int)K, (int)M) : WgPlan{WB, WB, WM, wgrad_nsplit(Cout, (int)K, (int)M)};
+  const WgPlan pl = is16(dtype) ? wgrad_plan16(Cout, (int)K, (int)M) : WgPlan{WB, WB, x3 ? 64 : WM, wgrad_nsplit(Cout, (int)K, (int)M)};
   p.nsplit = pl.nsplit;
   const int mstep = pl.mstep;
   p.rows_per_split = cdiv(cdiv(M, p.nsplit), mstep) * mstep;
@@ -581,7 +778,9 @@ static int wgrad_impl(const void* x, int x_ld, const void* dy, int dy_ld, float*
 #define WG16(H, PWV, A, Bk) hipLaunchKernelGGL((conv_wgrad16_kernel<H, PWV, A, Bk>), grid16, dim3(256), 0, s, p)
 #define WG16_T(H, PWV) do { if (pl.tco == 128 && pl.tk == 128) WG16(H, PWV, 128, 128); else if (pl.tco == 128) WG16(H, PWV, 128, 64); \
                             else if (pl.tk == 128) WG16(H, PWV, 64, 128); else WG16(H, PWV, 64, 64); } while (0)
-  if (dtype == CFP_BF16 && pw) WG16_T(bf16_t, true);
+  if (x3 && pw) hipLaunchKernelGGL(conv_wgrad_x3_kernel<true>, grid16, dim3(256), 0, s, p, dy_exp);
+  else if (x3) hipLaunchKernelGGL(conv_wgrad_x3_kernel<false>, grid16, dim3(256), 0, s, p, dy_exp);
+  else if (dtype == CFP_BF16 && pw) WG16_T(bf16_t, true);
   else if (dtype == CFP_BF16) WG16_T(bf16_t, false);
   else if (dtype == CFP_F16 && pw) WG16_T(f16_t, true);
   else if (dtype == CFP_F16) WG16_T(f16_t, false);
@@ -617,6 +816,37 @@ extern "C" int cfp_conv2d_wgrad_deferred(const void* x, int x_ld, const void* dy
   CFP_REQUIRE(job, CFP_EINVAL, "cfp_conv2d_wgrad_deferred: null job");
   return wgrad_impl(x, x_ld, dy, dy_ld, dw, db, B, H, W, Cin, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo, beta, beta_b, dtype, ws, ws_bytes,
                     job, stream);
+}
+
+extern "C" int cfp_conv2d_wgrad_x3(const float* x, int x_ld, const float* dy, int dy_ld, float* dw, int B, int H, int W, int Cin, int Cout,
+                                   int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, float beta, const int* dy_scale, void* ws,
+                                   size_t ws_bytes, cfp_wgrad_job* job, cfp_stream_t stream) {
+  return wgrad_impl(x, x_ld, dy, dy_ld, dw, nullptr, B, H, W, Cin, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo, beta, 0.f, CFP_F32X3, ws,
+                    ws_bytes, job, stream, dy_scale);
+}
+
+extern "C" int cfp_grad_absmax(const float* x, int ld, long long rows, int C, int* word, cfp_stream_t stream) {
+  CFP_REQUIRE(x && word && aligned16(x) && (reinterpret_cast<uintptr_t>(word) & 3) == 0, CFP_EINVAL, "cfp_grad_absmax: bad pointer");
+  CFP_REQUIRE(rows > 0 && C > 0 && C % 4 == 0 && ld % 4 == 0 && ld >= C && rows * (C / 4) < (1ll << 31), CFP_ESHAPE, "cfp_grad_absmax: bad shape");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const unsigned total = (unsigned)(rows * (C / 4));
+  const int blocks = (int)std::min<long long>(256, (total + 255) / 256);
+  hipLaunchKernelGGL(grad_word_zero_kernel, dim3(1), dim3(64), 0, s, word);      // a kernel, not a memset: the same node type in a captured step
+  hipLaunchKernelGGL(grad_absmax_kernel, dim3(blocks), dim3(256), 0, s, x, ld, make_fastdiv((unsigned)(C / 4)), total, word);
+  return cfp_check_launch("cfp_grad_absmax");
+}
+
+extern "C" int cfp_grad_scale(const float* dy, int ld, int B, int Ho, int Wo, int C, int dil, const int* dy_scale, float* out, float* inv,
+                              int n_inv, cfp_stream_t stream) {
+  CFP_REQUIRE(dy && out && aligned16(dy) && aligned16(out) && (n_inv == 0 || inv) && dy != out, CFP_EINVAL, "cfp_grad_scale: bad pointer");
+  const long long Hd = (long long)(Ho - 1) * dil + 1, Wd = (long long)(Wo - 1) * dil + 1;
+  CFP_REQUIRE(B > 0 && Ho > 0 && Wo > 0 && dil > 0 && C > 0 && C % 4 == 0 && ld % 4 == 0 && ld >= C && n_inv >= 0 &&
+                  (long long)B * Hd * Wd * (C / 4) < (1ll << 31), CFP_ESHAPE, "cfp_grad_scale: bad shape");
+  const unsigned total = (unsigned)((long long)B * Hd * Wd * (C / 4));
+  const int blocks = (int)std::min<long long>(2048, (total + 255) / 256);
+  hipLaunchKernelGGL(grad_scale_kernel, dim3(blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dy, ld, Ho, Wo, dil,
+                     make_fastdiv((unsigned)(C / 4)), make_fastdiv((unsigned)Wd), make_fastdiv((unsigned)Hd), total, dy_scale, out, inv, n_inv);
+  return cfp_check_launch("cfp_grad_scale");
 }
 
 extern "C" int cfp_wgrad_reduce_jobs(const cfp_wgrad_job* jobs, int njobs, cfp_stream_t stream) {

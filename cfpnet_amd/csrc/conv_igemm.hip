@@ -916,12 +916,53 @@ extern "C" int cfp_upsample_cat_conv3x3(const void* low, int low_ld, int Hs, int
 // Data gradient of a convolution: dX [B,H,W,Cin] from dY [B,Ho,Wo,Cout] and the flipped weights of cfp_conv2d_weight_flip
 // ([Cin][KH][KW][Cout]).  dX = conv_stride1(zero-stuff(dY, stride), Wt) with padding K-1-pad, accumulate into dX when
 // `accumulate` (the skip connections' gradient) by passing dX as the residual.
+static int dgrad_x3(const float* dy, int dy_ld, const void* wt, const float* res, int res_ld, float* dx, int dx_ld, int B, int H, int W, int Cin,
+                    int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, const int* dy_scale, void* ws, size_t ws_bytes,
+                    cfp_stream_t stream);
+
 extern "C" int cfp_conv2d_dgrad(const void* dy, int dy_ld, const void* wt, void* dx, int dx_ld, int B, int H, int W, int Cin, int Cout,
                                 int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, int accumulate, int dtype, void* ws,
                                 size_t ws_bytes, cfp_stream_t stream) {
   CFP_REQUIRE(pad_t >= 0 && pad_l >= 0 && pad_t < KH && pad_l < KW, CFP_ESHAPE, "cfp_conv2d_dgrad: padding must be smaller than the kernel");
+  if (dtype == CFP_F32X3)
+    return dgrad_x3((const float*)dy, dy_ld, wt, accumulate ? (const float*)dx : nullptr, dx_ld, (float*)dx, dx_ld, B, H, W, Cin, Cout, KH, KW,
+                    stride, pad_t, pad_l, Ho, Wo, nullptr, ws, ws_bytes, stream);
   return conv2d_impl(dy, dy_ld, wt, nullptr, nullptr, accumulate ? dx : nullptr, dx_ld, dx, dx_ld, B, Ho, Wo, Cout, Cin, KH, KW, 1,
                      KH - 1 - pad_t, KW - 1 - pad_l, H, W, CFP_ACT_NONE, dtype, nullptr, nullptr, 0.f, 0, ws, ws_bytes, stream, stride);
+}
+
+// f16x3 data gradient (float32 dY / dX, `wt` = the pre-split operand of the flipped weights, cfp_pack_w_x3_batch mode 1).  dY goes to the
+// split-precision kernels of the forward either as it is (stride 1, no scale) or through cfp_grad_scale into `ws`: multiplied by the power of
+// two of `dy_scale` and, for stride > 1, zero-stuffed (the x3 loaders take no input dilation: those few layers read a stuffed copy).  The
+// convolution's per-channel epilogue scale is then 2^-e (exact), so dX comes out unscaled.
+extern "C" size_t cfp_conv2d_dgrad_x3_ws_bytes(int B, int Ho, int Wo, int Cout, int Cin, int stride) {
+  if (B <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0 || Cin <= 0 || stride <= 0) return 0;
+  const long long Hd = (long long)(Ho - 1) * stride + 1, Wd = (long long)(Wo - 1) * stride + 1;
+  return ((size_t)cdiv(Cin, 64) * 64 + (size_t)B * Hd * Wd * Cout) * sizeof(float);
+}
+
+static int dgrad_x3(const float* dy, int dy_ld, const void* wt, const float* res, int res_ld, float* dx, int dx_ld, int B, int H, int W, int Cin,
+                    int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, const int* dy_scale, void* ws, size_t ws_bytes,
+                    cfp_stream_t stream) {
+  CFP_REQUIRE(pad_t >= 0 && pad_l >= 0 && pad_t < KH && pad_l < KW, CFP_ESHAPE, "cfp_conv2d_dgrad: padding must be smaller than the kernel");
+  if (!dy_scale && stride == 1)
+    return conv2d_impl(dy, dy_ld, wt, nullptr, nullptr, res, res_ld, dx, dx_ld, B, Ho, Wo, Cout, Cin, KH, KW, 1, KH - 1 - pad_t, KW - 1 - pad_l,
+                       H, W, CFP_ACT_NONE, CFP_F32, nullptr, nullptr, 0.f, CFP_CONV_X3, nullptr, 0, stream, 1);
+  CFP_REQUIRE(ws && aligned16(ws) && ws_bytes >= cfp_conv2d_dgrad_x3_ws_bytes(B, Ho, Wo, Cout, Cin, stride), CFP_EINVAL,
+              "cfp_conv2d_dgrad (f16x3): workspace missing or too small (cfp_conv2d_dgrad_x3_ws_bytes)");
+  float* inv = reinterpret_cast<float*>(ws);
+  float* dys = inv + (size_t)cdiv(Cin, 64) * 64;
+  int e = cfp_grad_scale(dy, dy_ld, B, Ho, Wo, Cout, stride, dy_scale, dys, inv, Cin, stream);
+  if (e != CFP_OK) return e;
+  const int Hd = (Ho - 1) * stride + 1, Wd = (Wo - 1) * stride + 1;
+  return conv2d_impl(dys, Cout, wt, inv, nullptr, res, res_ld, dx, dx_ld, B, Hd, Wd, Cout, Cin, KH, KW, 1, KH - 1 - pad_t, KW - 1 - pad_l, H, W,
+                     CFP_ACT_NONE, CFP_F32, nullptr, nullptr, 0.f, CFP_CONV_X3, nullptr, 0, stream, 1);
+}
+
+extern "C" int cfp_conv2d_dgrad_x3(const float* dy, int dy_ld, const void* wt, const float* res, int res_ld, float* dx, int dx_ld, int B, int H, int W,
+                                   int Cin, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, const int* dy_scale,
+                                   void* ws, size_t ws_bytes, cfp_stream_t stream) {
+  return dgrad_x3(dy, dy_ld, wt, res, res_ld, dx, dx_ld, B, H, W, Cin, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo, dy_scale, ws, ws_bytes, stream);
 }
 
 extern "C" int cfp_conv2d_nhwc(const void* in, int in_ld, const void* w, const float* scale, const float* shift,

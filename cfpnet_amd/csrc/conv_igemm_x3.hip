@@ -837,7 +837,64 @@ __global__ __launch_bounds__(256) void pack_w_x3_kernel(const float* __restrict_
   }
 }
 
+// Every training convolution's pre-split operands in one launch (cfp_pack_w_x3_batch): desc[t] = {source offset (floats), destination
+// offset (halves), Cout, KH, KW, Cin, first workgroup, mode}; mode 0 packs w [Cout][KH*KW*Cin] as it is (the forward operand), mode 1 packs
+// its flipped copy [Cin][KH][KW][Cout] (both kernel axes reversed: the data gradient's operand) without writing that copy.  Same values,
+// same split as weight_flip_kernel + pack_w_x3_kernel.
+constexpr int PACK_PER_BLOCK = 2048;
+__global__ __launch_bounds__(256) void pack_w_x3_batch_kernel(const float* __restrict__ src, f16_t* __restrict__ dst, const long long* __restrict__ desc,
+                                                              int n) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (desc[mid * 8 + 6] <= (long long)blockIdx.x) lo = mid; else hi = mid - 1;
+  }
+  const long long* d = desc + lo * 8;
+  const float* __restrict__ w = src + d[0];
+  f16_t* __restrict__ out = dst + d[1];
+  const int Cout = (int)d[2], KH = (int)d[3], KW = (int)d[4], Cin = (int)d[5];
+  const bool flip = d[7] != 0;
+  const long long rows = flip ? Cin : Cout;
+  const int K = KH * KW * (flip ? Cout : Cin), nk = (K + 31) / 32;
+  const long long total = rows * nk * 32;
+  const long long i0 = ((long long)blockIdx.x - d[6]) * PACK_PER_BLOCK;
+  for (long long i = i0 + threadIdx.x; i < min(total, i0 + PACK_PER_BLOCK); i += 256) {
+    const int r = (int)(i & 31);
+    const long long t = i >> 5;
+    const int ks = (int)(t % nk);
+    const long long row = t / nk;
+    const int k = ks * 32 + r;
+    float x = 0.f;
+    if (k < K) {
+      if (!flip) {
+        x = w[row * K + k];
+      } else {                                   // row = ci, k = (kh', kw', co) of the flipped tensor
+        const int co = k % Cout, tt = k / Cout, kw2 = tt % KW, kh2 = tt / KW;
+        x = w[(((long long)co * KH + (KH - 1 - kh2)) * KW + (KW - 1 - kw2)) * Cin + row];
+      }
+    }
+    const f16_t h = f2h(x);
+    const f16_t l = (f16_t)(x - (float)h);
+    const int pos = ((r & 15) >> 2) * 8 + (r & 3) + ((r >> 4) << 2);
+    f16_t* o = out + (row * nk + ks) * 64;
+    o[pos] = h;
+    o[32 + pos] = l;
+  }
+}
+
 }  // namespace
+
+extern "C" int cfp_pack_w_x3_blocks(long long rows, int K) {
+  return rows > 0 && K > 0 ? (int)((rows * ((K + 31) / 32) * 32 + PACK_PER_BLOCK - 1) / PACK_PER_BLOCK) : 0;
+}
+
+extern "C" int cfp_pack_w_x3_batch(const float* src_base, void* dst_base, const long long* desc, int n, int total_blocks, cfp_stream_t stream) {
+  CFP_REQUIRE(src_base && dst_base && desc, CFP_EINVAL, "cfp_pack_w_x3_batch: null pointer");
+  CFP_REQUIRE(n > 0 && total_blocks > 0, CFP_ESHAPE, "cfp_pack_w_x3_batch: empty batch");
+  hipLaunchKernelGGL(pack_w_x3_batch_kernel, dim3(total_blocks), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src_base,
+                     reinterpret_cast<f16_t*>(dst_base), desc, n);
+  return cfp_check_launch("cfp_pack_w_x3_batch");
+}
 
 int igemm_x3_num_variants() { return kNumCfg; }
 void igemm_x3_variant_shape(int v, int* bm, int* bn, int* stages) { *bm = kCfg[v].bm; *bn = kCfg[v].bn; *stages = kCfg[v].stages; }

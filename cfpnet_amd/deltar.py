@@ -54,7 +54,7 @@ class _Store(nn.Module):
 class Deltar(_Store):
     def __init__(self, n_bins: int = 100, min_val: float = 0.1, max_val: float = 10, norm: str = "linear", *,
                  args=None, dtype="f32x3", stem_act: bool = False, init: str = "deterministic",
-                 base_resolution=spec.BASE_RESOLUTION, prob_dtype=torch.float32):
+                 base_resolution=spec.BASE_RESOLUTION, prob_dtype=torch.float32, train_dtype=None):
         """`dtype` (not in the reference) picks the numerics of the HIP path:
           "f32x3" (DEFAULT)  float32 storage, split-precision (f16 x 3) matrix math: the mode whose depth maps stay within the reference
                              tolerance (1e-3 relative L1 against the reference's float32 forward, deltar.py:34-67) on every weight family
@@ -66,7 +66,11 @@ class Deltar(_Store):
                              (one host sync per forward); dtype=torch.float32 is the mode without the limit.
           torch.float32      float32 storage and float32 matrix cores: the bit-level parity mode (1/16 of the 16-bit matrix rate)
           torch.float16 / torch.bfloat16   16-bit storage, opt-in SPEED modes: 2.4 x the default's throughput, but outside the tolerance
-                             on ill-conditioned (confident-head) networks -- fp16 0.8e-3 ... 1.2e-2, bf16 ~6e-3."""
+                             on ill-conditioned (confident-head) networks -- fp16 0.8e-3 ... 1.2e-2, bf16 ~6e-3.
+        `train_dtype` (not in the reference): the numerics of `model.train()` forwards and their backward.  None (default): the storage
+        type above (the float32 tape for "f32x3").  "f32x3": float32 storage with every dense conv / Linear GEMM of the forward, the data
+        gradient and the weight gradient in split precision (f16 x 3, power-of-two scaled activation gradients) -- the float32 tape's
+        gradients at the 16-bit matrix rate; the attribute `model.train_dtype` may be changed later."""
         super().__init__()
         a = args if args is not None else _global_args
         self.num_classes = n_bins
@@ -85,6 +89,9 @@ class Deltar(_Store):
         if isinstance(dtype, str):
             dtype = {"f32x3": torch.float32, "x3": torch.float32, "f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}[dtype.lower()]
         self.compute_dtype = dtype
+        if isinstance(train_dtype, str) and train_dtype.lower() != "f32x3":
+            raise ValueError(f"train_dtype {train_dtype!r}: None or 'f32x3'")
+        self.train_dtype = train_dtype
         # the reference returns `prob` in float32 (deltar.py:51,64-67); the engine writes it in its storage type (2 bytes per element at
         # batch 8 = 315 MB instead of 630 MB).  At THIS boundary the reference's type is the default (one cast); prob_dtype=None hands
         # out the engine's tensor as it is
@@ -282,7 +289,7 @@ class _CapturedTrainStep:
         offs_dev = {n: self.offs[i] for i, n in enumerate(_OFFSET_NAMES)}
         sd = {k: v.detach() for k, v in model.state_dict(keep_vars=True).items()}
         self.net = TrainNet(sd, model.layer_names, dev, n_bins=model.num_classes, min_val=model.min_val, max_val=model.max_val,
-                            stem_act=model.stem_act, change_embedding=model.change_embedding, share_buffers=True, dtype=model.compute_dtype,
+                            stem_act=model.stem_act, change_embedding=model.change_embedding, share_buffers=True, dtype=_train_numerics(model),
                             no_skip_inside=model.no_skip_inside, norm=model.norm, base_resolution=model.base_resolution)
         self.names = list(names)
         # one real execution before the capture (sets kernel attributes, builds the index maps); its update of the running
@@ -291,7 +298,7 @@ class _CapturedTrainStep:
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
-            t = Tape(dev, model.compute_dtype)
+            t = self.net.new_tape()
             pred, _, (B, h, w) = self.net.forward(t, self.inp, offs_dev)
             pred.g = torch.zeros(B * h * w, 1, dtype=torch.float32, device=dev)
             t.backward()
@@ -302,7 +309,7 @@ class _CapturedTrainStep:
             self.net.buf[k].copy_(v)
         self.gf, self.gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.gf):
-            self.tape = Tape(dev, model.compute_dtype)
+            self.tape = self.net.new_tape()
             self.pred, self.edges, (B, h, w) = self.net.forward(self.tape, self.inp, offs_dev)
         self.shape = (B, 1, h, w)
         self.gpred = torch.zeros(B * h * w, 1, dtype=torch.float32, device=dev)
@@ -345,7 +352,7 @@ class _TrainStep(torch.autograd.Function):
         ctx.names = names
         if model.train_graphs:
             add = input_data["additional"]
-            key = (tuple(input_data["rgb"].shape), tuple(add["hist_data"].shape), _patch_signature(add["patch_info"]), model.compute_dtype)
+            key = (tuple(input_data["rgb"].shape), tuple(add["hist_data"].shape), _patch_signature(add["patch_info"]), _train_numerics(model))
             cap = model._train_captures.get(key)
             if cap is None or cap.ptrs != tuple(p.data_ptr() for p in params):
                 model._train_captures.clear()                     # one geometry at a time: a capture pins ~25 GB of activations
@@ -358,9 +365,9 @@ class _TrainStep(torch.autograd.Function):
         ctx.cap = None
         sd = {k: v.detach() for k, v in model.state_dict(keep_vars=True).items()}
         net = TrainNet(sd, model.layer_names, dev, n_bins=model.num_classes, min_val=model.min_val, max_val=model.max_val,
-                       stem_act=model.stem_act, change_embedding=model.change_embedding, share_buffers=True, dtype=model.compute_dtype,
+                       stem_act=model.stem_act, change_embedding=model.change_embedding, share_buffers=True, dtype=_train_numerics(model),
                        no_skip_inside=model.no_skip_inside, norm=model.norm, base_resolution=model.base_resolution)
-        tape = Tape(dev, model.compute_dtype)
+        tape = net.new_tape()
         pred, edges, (B, h, w) = net.forward(tape, input_data, pos_offsets)
         ctx.net, ctx.tape, ctx.pred = net, tape, pred
         ctx.mark_non_differentiable(edges)
@@ -377,6 +384,12 @@ class _TrainStep(torch.autograd.Function):
         ctx.tape.backward()
         grads = ctx.net.grads()
         return (None, None, None, None) + tuple(grads.get(n) for n in ctx.names)
+
+
+def _train_numerics(model):
+    """What TrainNet gets as its dtype: the storage type, or "f32x3" for the split-precision training numerics (Deltar.train_dtype)."""
+    td = getattr(model, "train_dtype", None)
+    return "f32x3" if isinstance(td, str) and td.lower() == "f32x3" else model.compute_dtype
 
 
 def _forward_train(self, input_data: Dict, pos_offsets=None):

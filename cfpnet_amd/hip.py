@@ -77,6 +77,13 @@ SIGNATURES = {
     "cfp_eval_metrics_ws_bytes": (_sz, [_i]),
     "cfp_eval_metrics": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _i, _f, _f, _p, _sz, _p, _p]),
     "cfp_conv2d_wgrad_ws_bytes": (_sz, [_i, _i, _i]),
+    "cfp_grad_absmax": (_i, [_p, _i, _ll, _i, _p, _p]),
+    "cfp_grad_scale": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p]),
+    "cfp_conv2d_wgrad_x3": (_i, [_p, _i, _p, _i, _p] + [_i] * 12 + [_f, _p, _p, _sz, _p, _p]),
+    "cfp_conv2d_dgrad_x3_ws_bytes": (_sz, [_i] * 6),
+    "cfp_conv2d_dgrad_x3": (_i, [_p, _i, _p, _p, _i, _p, _i] + [_i] * 12 + [_p, _p, _sz, _p]),
+    "cfp_pack_w_x3_blocks": (_i, [_ll, _i]),
+    "cfp_pack_w_x3_batch": (_i, [_p, _p, _p, _i, _i, _p]),
     "cfp_conv2d_wgrad": (_i, [_p, _i, _p, _i, _p] + [_i] * 12 + [_f, _i, _p, _sz, _p]),
     "cfp_conv2d_wgrad_bias": (_i, [_p, _i, _p, _i, _p, _p] + [_i] * 12 + [_f, _f, _i, _p, _sz, _p]),
     "cfp_conv2d_wgrad_deferred": (_i, [_p, _i, _p, _i, _p, _p] + [_i] * 12 + [_f, _f, _i, _p, _sz, _p, _p]),

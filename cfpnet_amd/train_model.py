@@ -49,8 +49,13 @@ class TrainNet:
                  no_skip_inside: bool = False, norm: str = "linear", base_resolution=spec.BASE_RESOLUTION):
         """`dtype`: storage of activations and of the matrix-core weight operands (float32 = parity mode; bfloat16 /
         float16 = mixed precision: float32 master parameters, float32 gradients of the parameters, 16-bit activations
-        and activation gradients, float32 accumulation everywhere)."""
+        and activation gradients, float32 accumulation everywhere; "f32x3" = float32 storage with the dense conv / Linear GEMMs of the
+        forward and of both gradients in split precision, autograd_hip.Tape(x3=True))."""
         self.dev = torch.device(device)
+        self.x3 = isinstance(dtype, str)
+        if self.x3 and dtype.lower() != "f32x3":
+            raise ValueError(f"training numerics {dtype!r}: torch.float32 / bfloat16 / float16 or 'f32x3'")
+        dtype = torch.float32 if self.x3 else dtype
         self.dtype = dtype
         self.base_resolution = tuple(base_resolution)
         self.fusion = spec.fusion_table(self.base_resolution)
@@ -73,6 +78,8 @@ class TrainNet:
         self.side_stream: Optional[torch.cuda.Stream] = None      # set by the trainer: parameter gradients beside the dY -> dX chain
         self._open_tape = None
         self.flipped: Dict[str, torch.Tensor] = {}        # bound mode: name -> flipped conv weight, refreshed by the trainer every step
+        self.packed: Dict[str, torch.Tensor] = {}         # bound f16x3 mode: name -> pre-split forward operand, refreshed every step
+        self.packed_t: Dict[str, torch.Tensor] = {}       # ... and the pre-split operand of the data gradient (flipped / transposed weights)
         self._bound = None                                # (FlatParams in kernel layouts, 16-bit shadow) once `bind` was called
         self.discovered: Optional[Dict[str, tuple]] = None    # set to {} to collect name -> (float32 kernel layout, to_torch, is16)
         self.record: Optional[Dict[str, V]] = None       # debugging: name -> tape value (tools/train_grad_check.py compares their .g)
@@ -90,6 +97,7 @@ class TrainNet:
                 src = shadow if (is16 and shadow is not None) else flat.param
                 p = P(name, src[s.start:s.start + s.numel].view(s.shape), to_torch, gview=flat.view(name, "grad"))
                 p.wt = self.flipped.get(name)
+                p.pk, p.pkt = self.packed.get(name), self.packed_t.get(name)
             else:
                 t32 = make32().contiguous().to(self.dev)
                 if self.discovered is not None:
@@ -455,7 +463,7 @@ class TrainNet:
         `stop`: any tape mark (BACKWARD_MARKS) instead of "encoder"; `finish_backward(stop=...)` continues to the next one.
         `defer_param_grads`: weight / bias gradient kernels are queued on the tape; `run_deferred_param_grads()` issues them."""
         dev = self.dev
-        t = Tape(dev, self.dtype, side=self.side_stream)
+        t = self.new_tape(side=self.side_stream)
         t.defer = defer_param_grads
         pred, edges, (B, h0, w0) = self.forward(t, input_data, pos_offsets)
         # SILog (loss.py:9-19) on the half-resolution prediction against the full-resolution target
@@ -471,6 +479,10 @@ class TrainNet:
         t.backward(stop=stop)
         self._open_tape = t if (stop is not None or defer_param_grads) else None
         return loss, pred4, edges
+
+    def new_tape(self, side: Optional[torch.cuda.Stream] = None) -> Tape:
+        """A tape in this network's numerics (storage dtype, f16x3 GEMMs or not)."""
+        return Tape(self.dev, self.dtype, side=side, x3=self.x3)
 
     def finish_backward(self, stop: Optional[str] = None) -> None:
         """The next part of a backward that `forward_backward(stop=...)` left open: down to mark `stop`, or to the end."""

@@ -303,11 +303,23 @@ class WgradQueue:
         self.jobs, self.keep = [], []
 
 
+def grad_absmax(g2d: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """-> int32[1] on the device: the float32 bits of max|g| (cfp_grad_absmax), the power-of-two scale of an f16x3 backward GEMM's dY."""
+    from . import hip
+    assert g2d.dtype == torch.float32 and g2d.dim() == 2 and g2d.stride(1) == 1
+    if out is None:
+        out = torch.empty(1, dtype=torch.int32, device=g2d.device)
+    hip.call("cfp_grad_absmax", g2d.data_ptr(), g2d.stride(0), g2d.shape[0], g2d.shape[1], out.data_ptr(), hip.current_stream())
+    return out
+
+
 def conv2d_wgrad(x2d: torch.Tensor, dy2d: torch.Tensor, B, H, W, KH, KW, stride, pad_t, pad_l, Ho, Wo, dw: Optional[torch.Tensor] = None,
-                 beta: float = 0.0, db: Optional[torch.Tensor] = None, beta_b: float = 0.0, queue: Optional[WgradQueue] = None) -> torch.Tensor:
+                 beta: float = 0.0, db: Optional[torch.Tensor] = None, beta_b: float = 0.0, queue: Optional[WgradQueue] = None,
+                 x3: bool = False, dy_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x2d [B*H*W, Cin], dy2d [B*Ho*Wo, Cout] (same dtype: f32 / bf16 / f16) -> dw [Cout, KH*KW*Cin] f32 (= beta*dw + grad).
     `db` (16-bit dtypes): float32 [>= Cout], receives beta_b*db + the bias gradient (column sums of dy) from the same launch.
-    `queue`: leave the reduction of the split slabs to `queue.flush()` (dw / db hold the result only after it)."""
+    `queue`: leave the reduction of the split slabs to `queue.flush()` (dw / db hold the result only after it).
+    `x3` (float32 tensors): the f16x3 kernel (cfp_conv2d_wgrad_x3); `dy_scale`: grad_absmax(dy2d), the power-of-two scale of dY."""
     from . import hip, ops
     Cin, Cout = x2d.shape[1], dy2d.shape[1]
     K, M = KH * KW * Cin, B * Ho * Wo
@@ -316,6 +328,17 @@ def conv2d_wgrad(x2d: torch.Tensor, dy2d: torch.Tensor, B, H, W, KH, KW, stride,
         beta = 0.0
     nbytes = hip.load().cfp_conv2d_wgrad_ws_bytes(Cout, K, M)
     ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=x2d.device)
+    if x3:
+        assert x2d.dtype == torch.float32 and dy2d.dtype == torch.float32 and db is None
+        job = hip.WgradJob() if queue is not None else None
+        hip.call("cfp_conv2d_wgrad_x3", x2d.data_ptr(), x2d.stride(0), dy2d.data_ptr(), dy2d.stride(0), dw.data_ptr(), B, H, W, Cin, Cout, KH, KW,
+                 stride, pad_t, pad_l, Ho, Wo, beta, hip.ptr(dy_scale), ws.data_ptr(), nbytes, ctypes.addressof(job) if job is not None else None,
+                 hip.current_stream())
+        if job is not None and job.nsplit > 0:
+            queue.jobs.append(job)
+            queue.keep.append((ws, dw, dy_scale))
+        return dw
+    assert dy_scale is None
     if db is not None:
         assert x2d.dtype != torch.float32 and db.dtype == torch.float32 and db.numel() >= Cout
     if queue is not None:
@@ -345,12 +368,24 @@ def conv2d_weight_flip(w2d: torch.Tensor, Cout, KH, KW, Cin) -> torch.Tensor:
 
 
 def conv2d_dgrad(dy2d: torch.Tensor, wt: torch.Tensor, B, H, W, Cin, KH, KW, stride, pad_t, pad_l, Ho, Wo, dx: Optional[torch.Tensor] = None,
-                 accumulate: bool = False) -> torch.Tensor:
+                 accumulate: bool = False, x3: bool = False, dy_scale: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`x3` (float32 tensors): `wt` is the pre-split operand of the flipped weights (ops.pack_w_x3 of conv2d_weight_flip) and the f16x3
+    kernels run (cfp_conv2d_dgrad_x3); `dy_scale`: grad_absmax(dy2d); `res`: dx = conv + res (a tensor other than dx)."""
     from . import hip, ops
     Cout = dy2d.shape[1]
     if dx is None:
         dx = torch.empty(B * H * W, Cin, dtype=dy2d.dtype, device=dy2d.device)
         accumulate = False
+    if x3:
+        assert dy2d.dtype == torch.float32 and wt.dtype == torch.float16 and dy2d.stride(1) == 1
+        r = dx if accumulate else res
+        nbytes = hip.load().cfp_conv2d_dgrad_x3_ws_bytes(B, Ho, Wo, Cout, Cin, stride) if (dy_scale is not None or stride > 1) else 0
+        ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dy2d.device) if nbytes else None
+        hip.call("cfp_conv2d_dgrad_x3", dy2d.data_ptr(), dy2d.stride(0), wt.data_ptr(), hip.ptr(r), r.stride(0) if r is not None else 0,
+                 dx.data_ptr(), dx.stride(0), B, H, W, Cin, Cout, KH, KW, stride, pad_t, pad_l, Ho, Wo, hip.ptr(dy_scale), hip.ptr(ws), nbytes,
+                 hip.current_stream())
+        return dx
+    assert dy_scale is None and res is None
     hip.call("cfp_conv2d_dgrad", dy2d.data_ptr(), dy2d.stride(0), wt.data_ptr(), dx.data_ptr(), dx.stride(0), B, H, W, Cin, Cout, KH, KW,
              stride, pad_t, pad_l, Ho, Wo, int(accumulate), ops.DT[dy2d.dtype], None, 0, hip.current_stream())
     return dx

@@ -28,8 +28,13 @@ class Trainer:
                  change_embedding: bool = True, dtype=torch.float32, no_skip_inside: bool = False, norm: str = "linear", kernel_layout: bool = True,
                  base_resolution=spec.BASE_RESOLUTION, overlap_param_grads: bool = False, comm: str = "overlap", sync_loss: bool = False):
         self.dev = torch.device(device)
-        self.dtype, self.kernel_layout, self._hist10 = dtype, kernel_layout, hist_encoder_10x
-        self._net_kw = dict(n_bins=n_bins, min_val=min_val, max_val=max_val, change_embedding=change_embedding, dtype=dtype,
+        # dtype "f32x3": float32 storage (as torch.float32) with the dense conv / Linear GEMMs of the step in split precision (TrainNet)
+        self.x3 = isinstance(dtype, str) and dtype.lower() == "f32x3"
+        if isinstance(dtype, str) and not self.x3:
+            raise ValueError(f"training numerics {dtype!r}: torch.float32 / bfloat16 / float16 or 'f32x3'")
+        self.dtype = torch.float32 if self.x3 else dtype
+        self.kernel_layout, self._hist10 = kernel_layout, hist_encoder_10x
+        self._net_kw = dict(n_bins=n_bins, min_val=min_val, max_val=max_val, change_embedding=change_embedding, dtype="f32x3" if self.x3 else dtype,
                             no_skip_inside=no_skip_inside, norm=norm, base_resolution=base_resolution)
         self._layers = list(layer_names)
         self._opt_kw = dict(lr=lr, total_steps=total_steps, div_factor=div_factor, final_div_factor=final_div_factor, weight_decay=weight_decay,
@@ -60,7 +65,7 @@ class Trainer:
         for name, _ in names:                                     # TrainNet.__init__ keeps device tensors as they are: still views
             assert self.net.sd[name].data_ptr() == self.flat.view(name).data_ptr()
         self.opt = train_ops.FlatAdamW(self.flat, train_ops.OneCycle(lr, total_steps, div_factor, final_div_factor), weight_decay=weight_decay,
-                                       clip_grad_norm=clip_grad_norm, overflow_guard=dtype == torch.float16)
+                                       clip_grad_norm=clip_grad_norm, overflow_guard=self.dtype == torch.float16)
         self.min_val = min_val
         self._graph = None
         if overlap_param_grads:        # measured SLOWER inside a captured step (48.8 vs 45.2 ms): off by default, see DESIGN 4.0
@@ -72,7 +77,7 @@ class Trainer:
         from .autograd_hip import Tape
         scratch = TrainNet(self.net.sd, self._layers, self.dev, **self._net_kw)              # own copy of the running statistics
         scratch.discovered = {}
-        scratch.forward(Tape(self.dev, self.dtype), input_data, offs)
+        scratch.forward(scratch.new_tape(), input_data, offs)
         found = scratch.discovered
         kflat = train_ops.FlatParams([(n, tuple(t32.shape)) for n, (t32, _, _) in found.items()], train_ops.lr_group_of(self._hist10),
                                      device=self.dev, align=128)                                # 128 elements: every tensor starts on a 256-byte line in the 16-bit shadow too
@@ -102,6 +107,10 @@ class Trainer:
         from . import hip, ops
         lib = hip.load()
         jobs = []
+        if self.x3:
+            self._plan_packs()
+            self._flip_jobs = jobs
+            return
         sources = ([self._shadow] if self._shadow is not None else []) + [self.flat.param]      # 16-bit operands / float32 ones
         for src in sources:
             rows, off, blocks = [], 0, 0
@@ -124,8 +133,41 @@ class Trainer:
             jobs.append((src, dst, desc, len(rows), blocks, ops.DT[src.dtype]))
         self._flip_jobs = jobs
 
+    def _plan_packs(self) -> None:
+        """f16x3 numerics: instead of flipped float32 copies, every dense conv / Linear weight gets its pre-split forward operand and
+        (where the data gradient is needed) the pre-split operand of its flipped weights, all written by ONE launch at the start of
+        each step (cfp_pack_w_x3_batch; the weights change every step)."""
+        from . import hip
+        lib = hip.load()
+        rows, off, blocks = [], 0, 0
+        for name, p in self.net.P.items():
+            for mode, geom in ((0, p.fgeom), (1, p.geom)):
+                if geom is None:
+                    continue
+                co, kh, kw, ci = geom
+                assert co * kh * kw * ci == p.t.numel(), name
+                r, k = (co, kh * kw * ci) if mode == 0 else (ci, kh * kw * co)
+                cols = (k + 31) // 32 * 64
+                nb = int(lib.cfp_pack_w_x3_blocks(r, k))
+                rows.append((name, mode, [self.flat._by_name[name].start, off, co, kh, kw, ci, blocks, mode], (r, cols)))
+                off += (r * cols + 127) // 128 * 128                      # every operand starts on a 256-byte line
+                blocks += nb
+        self._pack_job = None
+        if not rows:
+            return
+        dst = torch.zeros(off, dtype=torch.float16, device=self.dev)
+        desc = torch.tensor([r[2] for r in rows], dtype=torch.int64).to(self.dev)
+        for name, mode, d, shape in rows:
+            (self.net.packed if mode == 0 else self.net.packed_t)[name] = dst[d[1]:d[1] + shape[0] * shape[1]].view(shape)
+        self._pack_job = (dst, desc, len(rows), blocks)
+
     def _refresh_weight_flips(self) -> None:
         from . import hip
+        if self.x3:
+            if self._pack_job is not None:
+                dst, desc, n, blocks = self._pack_job
+                hip.call("cfp_pack_w_x3_batch", self.flat.param.data_ptr(), dst.data_ptr(), desc.data_ptr(), n, blocks, hip.current_stream())
+            return
         for src, dst, desc, n, blocks, dt in self._flip_jobs:
             hip.call("cfp_conv2d_weight_flip_batch", src.data_ptr(), dst.data_ptr(), desc.data_ptr(), n, blocks, dt, hip.current_stream())
 

@@ -479,6 +479,7 @@ int cfp_eval_metrics(const float* pred, int Hp, int Wp, const float* gt, int H, 
 /* Weight gradient of nn.Conv2d / nn.Linear (autograd of the layers cfp_conv2d_nhwc replaces; train.py:125):
  * dw[Cout][KH*KW*Cin] (f32) = beta * dw + sum over output pixels of dy[m][co] * x[window(m)][ci].  x [B,H,W,Cin] and
  * dy [B,Ho,Wo,Cout] in `dtype` (16-bit inputs are widened to f32 on the way to the matrix cores; accumulation f32).
+ * dtype CFP_F32X3 (also for _bias without db, and _deferred): float32 x / dy in split precision, see cfp_conv2d_wgrad_x3.
  * Split over pixel chunks into f32 slabs (ws) that a second kernel adds in a fixed order: bit-reproducible. */
 size_t cfp_conv2d_wgrad_ws_bytes(int Cout, int K, int M);
 int cfp_conv2d_wgrad(const void* x, int x_ld, const void* dy, int dy_ld, float* dw, int B, int H, int W, int Cin, int Cout,
@@ -524,10 +525,43 @@ int cfp_weight_flip_blocks(long long elems);
 int cfp_conv2d_weight_flip_batch(const void* src_base, void* dst_base, const long long* desc, int n, int total_blocks, int dtype,
                                  cfp_stream_t stream);
 /* Data gradient: dx [B,H,W,Cin] (+= when accumulate) from dy [B,Ho,Wo,Cout] and the flipped weights, for the forward
- * geometry (KH,KW,stride,pad_t,pad_l): a stride-1 convolution over dy with `stride - 1` zeros stuffed between its pixels. */
+ * geometry (KH,KW,stride,pad_t,pad_l): a stride-1 convolution over dy with `stride - 1` zeros stuffed between its pixels.
+ * dtype CFP_F32X3: float32 dy / dx, f16x3 matrix math; `wt` is then the PRE-SPLIT operand of the flipped weights
+ * (cfp_pack_w_x3_batch mode 1, = cfp_pack_w_x3 of cfp_conv2d_weight_flip's output) and stride > 1 needs `ws` of
+ * cfp_conv2d_dgrad_x3_ws_bytes (a zero-stuffed copy of dy). */
 int cfp_conv2d_dgrad(const void* dy, int dy_ld, const void* wt, void* dx, int dx_ld, int B, int H, int W, int Cin, int Cout,
                      int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, int accumulate, int dtype, void* ws,
                      size_t ws_bytes, cfp_stream_t stream);
+
+/* ---- f16x3 training numerics (float32 tensors, split-precision matrix math in the dense-convolution backward) ----------------
+ * Activation gradients are far below the range of IEEE half (SILog spreads ~10 / pixels over the image), so the dY operand of both
+ * backward GEMMs carries a power-of-two scale: cfp_grad_absmax leaves the float32 bits of max|dY| in one device int32 (`dy_scale`);
+ * the GEMMs multiply dY by 2^e before the split (e = 14 - exponent of the maximum: max * 2^e in [2^14, 2^15)) and multiply their
+ * float32 results by 2^-e.  Both multiplications are exact, so dY * 2^k gives results * 2^k bit for bit.  dy_scale NULL: e = 0. */
+int cfp_grad_absmax(const float* x, int ld, long long rows, int C, int* dy_scale, cfp_stream_t stream);
+/* out [B][(Ho-1)*dil+1][(Wo-1)*dil+1][C] (contiguous) = dy * 2^e with dil - 1 zero pixels between dy's pixels (dil = 1: a scaled copy),
+ * inv[0 .. n_inv) = 2^-e (the epilogue scale of the convolution that reads `out`). */
+int cfp_grad_scale(const float* dy, int ld, int B, int Ho, int Wo, int C, int dil, const int* dy_scale, float* out, float* inv, int n_inv,
+                   cfp_stream_t stream);
+/* Weight gradient in f16x3 (the call cfp_conv2d_wgrad / _deferred make for dtype CFP_F32X3, plus the dY scale): float32 x and dy,
+ * both split into hi / lo halves in the loader, three v_mfma_f32_16x16x32_f16 per block, float32 slabs reduced as for float32
+ * (job != NULL: deferred as cfp_conv2d_wgrad_deferred; ws of cfp_conv2d_wgrad_ws_bytes).  The bias gradient stays cfp_colsum. */
+int cfp_conv2d_wgrad_x3(const float* x, int x_ld, const float* dy, int dy_ld, float* dw, int B, int H, int W, int Cin, int Cout,
+                        int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, float beta, const int* dy_scale, void* ws,
+                        size_t ws_bytes, cfp_wgrad_job* job, cfp_stream_t stream);
+/* Data gradient in f16x3 with the dY scale: dx = conv(dy) + res (res may be NULL or equal dx: accumulation); geometry and `wt` as
+ * cfp_conv2d_dgrad with CFP_F32X3.  With a scale or stride > 1, `ws` of cfp_conv2d_dgrad_x3_ws_bytes holds the scaled (stuffed) dy. */
+size_t cfp_conv2d_dgrad_x3_ws_bytes(int B, int Ho, int Wo, int Cout, int Cin, int stride);
+int cfp_conv2d_dgrad_x3(const float* dy, int dy_ld, const void* wt, const float* res, int res_ld, float* dx, int dx_ld, int B, int H, int W,
+                        int Cin, int Cout, int KH, int KW, int stride, int pad_t, int pad_l, int Ho, int Wo, const int* dy_scale,
+                        void* ws, size_t ws_bytes, cfp_stream_t stream);
+/* Every convolution's pre-split operands of a training step in one launch.  `desc` is a DEVICE array of n rows of 8 int64:
+ * {source offset (floats from src_base), destination offset (halves from dst_base), Cout, KH, KW, Cin, first workgroup, mode};
+ * mode 0 writes cfp_pack_w_x3 of w [Cout][KH*KW*Cin], mode 1 cfp_pack_w_x3 of its cfp_conv2d_weight_flip ([Cin][KH*KW*Cout]),
+ * bit for bit.  A tensor takes cfp_pack_w_x3_blocks(rows, K) workgroups (rows / K of the packed matrix), rows sorted by first
+ * workgroup, total_blocks = their sum. */
+int cfp_pack_w_x3_blocks(long long rows, int K);
+int cfp_pack_w_x3_batch(const float* src_base, void* dst_base, const long long* desc, int n, int total_blocks, cfp_stream_t stream);
 
 /* cfp_conv2d_nhwc (no activation / residual) that ALSO emits, per tile of output rows, the channel moments of its stored output for the
  * batch-statistics BatchNorm that follows it in model.train() (timm ConvBnAct / torch `Conv2d -> BatchNorm2d`): mom[tile][0][c] = mean,

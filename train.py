@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Training with the reference's CLI and loop (`/root/reference/train.py:41-209`):
 
-    python train.py @configs/cfpnet_combine1.txt [--synthetic N] [--max_steps K] [--stop_after K] [--seed S] [--save weights/x.pt] [--dtype bf16|f16|f32] [--eager] [--validate N]
+    python train.py @configs/cfpnet_combine1.txt [--synthetic N] [--max_steps K] [--stop_after K] [--seed S] [--save weights/x.pt] [--dtype bf16|f16|f32|f32x3] [--eager] [--validate N]
                     [--resume checkpoints/x.pt] [--weight_path weights/x.pt] [--backend nccl|gloo] [--local_gpu I]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py @configs/cfpnet_combine1.txt --synthetic 4096
 
@@ -149,6 +149,11 @@ def drop_zones(sim, s, drop, rng):
     return mask, sim.sample_points(s["fh"], mask)
 
 
+# --dtype: the training numerics.  f32x3 = float32 storage with the dense conv / Linear GEMMs of the forward and of both gradients in
+# split precision (Trainer(dtype="f32x3"))
+TRAIN_DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "f32x3": "f32x3"}
+
+
 def main(argv=None):
     from cfpnet_amd import config, geometry, spec, weights
     from cfpnet_amd.tof import TofSimulator, zone_layout
@@ -165,7 +170,7 @@ def main(argv=None):
     save_path = _pop(argv, "--save", "", str)
     log_every = _pop(argv, "--log_every", 10, int)
     n_val = _pop(argv, "--validate", 0, int)
-    dtype = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16}[_pop(argv, "--dtype", "bf16")]
+    dtype = TRAIN_DTYPES[_pop(argv, "--dtype", "bf16")]
     backend = _pop(argv, "--backend", "nccl")        # "gloo": ranks may share one GPU (tests), buckets staged through the host
     local_gpu = _pop(argv, "--local_gpu", None, int)
     eager = "--eager" in argv
