@@ -393,10 +393,10 @@ void cfp_dwl_wgrad_debug_set(int value);     // train_misc2.hip: key 23 = 1 keep
 void cfp_wgrad_debug_set(int value);         // conv_bwd.hip: key 22 = workgroups a small weight-gradient launch aims for (sets the slab count)
 void cfp_bn_debug_set(int key, int value);   // bn_train.hip: 20 / 21 = workgroup targets of the column reductions / elementwise sweeps
 void cfp_attn_debug_set(int value);          // attention.hip: key 19 = waves the key / value reduction aims for when it splits a group's keys
-void cfp_dw_debug_set(int key, int value);   // dwconv.hip: key 3 = channel vectors per workgroup, 4 = rows per strip (0 = automatic), 5 = 1 forces the VALU kernel
+int cfp_dw_debug_set(int key, int value);    // dwconv.hip: depthwise 3x3 keys 3-6 and 9-11 (CFP_EINVAL for a value it does not take)
 extern "C" int cfp_debug_set(int key, int value) {
   switch (key) {
-    case 3: case 4: case 5: case 6: case 7: case 8: case 9: case 10: case 11: cfp_dw_debug_set(key, value); return CFP_OK;
+    case 3: case 4: case 5: case 6: case 9: case 10: case 11: return cfp_dw_debug_set(key, value);
     case 30: cfp_dwl3_debug_set(value); return CFP_OK;
     case 32: g_x3_occ = value; return CFP_OK;
     case 33: g_x3_small_m = value; return CFP_OK;

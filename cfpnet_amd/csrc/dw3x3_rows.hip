@@ -24,7 +24,7 @@
 // the activation -- the stored tensor is bit-identical to the old kernel's (tests/test_ops_gpu.py::test_dw3x3_rows_*).
 #include <algorithm>
 
-#include "common.h"
+#include "dw3x3.h"
 
 namespace {
 
@@ -165,19 +165,15 @@ __global__ __launch_bounds__(256) void dw3x3_rows_kernel(DwrP p) {
 }  // namespace
 
 // Work decomposition: runs of R output rows.  Short runs re-read halo rows, long runs leave the chip short of waves; ragged pixel-slot groups
-// and channel blocks idle lanes.
-struct DwrPlan { int R, nruns, npx, nps, ncb; };
-int g_dwr_mode = 1;           // cfp_debug_set key 10: 0 = the round-1 LDS-strip kernel
-int g_dwr_force_R = 0;        // cfp_debug_set key 11 (tools/dw_bench.py --sweep-r)
-
-static bool dwr_plan(int B, int H, int W, int Ho, int Wo, int C, int stride, int in_ld, int out_ld, DwrPlan& d) {
+// and channel blocks idle lanes.  The input extent enters only the feasibility test (< 2^30 bytes per image).
+bool dwr_plan(int B, int H, int W, int Ho, int Wo, int C, int stride, int in_ld, int out_ld, int force_R, DwrPlan& d) {
   if (C % 4 != 0 || (long long)H * W * in_ld * 4 >= (1ll << 30) || (long long)Ho * Wo * out_ld * 4 >= (1ll << 30)) return false;
   const int CV = C / 4, ncb = cdiv(CV, 8);
   int best = 0; double bc = 1e30;
   for (int R = 1; R <= Ho; ++R) {
-    if (g_dwr_force_R && R != std::min(g_dwr_force_R, Ho)) continue;
+    if (force_R && R != std::min(force_R, Ho)) continue;
     const int nruns = cdiv(Ho, R);
-    if (!g_dwr_force_R && cdiv(Ho, nruns) != R) continue;                // the shortest run length for this run count
+    if (!force_R && cdiv(Ho, nruns) != R) continue;                      // the shortest run length for this run count
     const long long npx = (long long)Wo * nruns, nps = (npx + 7) / 8;      // pixel-slot groups = live waves per image and channel block
     const long long waves = (long long)B * ncb * nps;
     // A time model in microseconds, fitted on tools/dw_bench_f32.py --sweep-r at batch 1 / 8 / 128 (profiles/r5a_dw_f32_sweep.txt):
@@ -188,8 +184,8 @@ static bool dwr_plan(int B, int H, int W, int Ho, int Wo, int C, int stride, int
     const double lanes = (double)(((nps + 3) / 4) * 32) / npx;         // idle lanes AND idle waves of the four-wave workgroups: they hold registers
                                                                          // (122 VGPRs: 16 waves per CU) that would otherwise keep loads in flight
     const double rows = (double)(nruns * R) / Ho;                       // ragged last run (its lanes idle through the tail rows)
-    const double in_b = 4.0 * B * (Ho * stride) * (Wo * stride) * C, out_b = 4.0 * B * Ho * Wo * C;      // from the OUTPUT extent only: cfp_dwr_slots (asked before
-                                                                                                         // the launch, without H / W) must see the same plan
+    const double in_b = 4.0 * B * (Ho * stride) * (Wo * stride) * C, out_b = 4.0 * B * Ho * Wo * C;      // from the OUTPUT extent only: the slot queries (asked
+                                                                                                         // without H / W) must see the same plan
     const double t_mem = (in_b * halo + out_b) * lanes * rows / 5.5e6;
     const double t_chain = std::max(1.0, (double)waves / 4096.0) * R * 0.25;
     const double t_tail = 0.01 * (double)((nps + 3) / 4) * ncb;
@@ -201,32 +197,9 @@ static bool dwr_plan(int B, int H, int W, int Ho, int Wo, int C, int stride, int
   return (long long)B * ncb * d.nps < (1ll << 31);
 }
 
-int cfp_dwr_launch_slots(int B, int H, int W, int Ho, int Wo, int C, int stride, int in_ld, int out_ld) {
-  DwrPlan d;
-  if (!g_dwr_mode || !dwr_plan(B, H, W, Ho, Wo, C, stride, in_ld, out_ld, d)) return 0;
-  return d.nps;
-}
-
-void cfp_dwr_debug_set(int key, int value) { if (key == 10) g_dwr_mode = value; else if (key == 11) g_dwr_force_R = value; }
-
-int cfp_dwr_slots(int B, int H, int W, int Ho, int Wo, int C, int stride, int* ncb) {
-  DwrPlan d;
-  if (!g_dwr_mode) return 0;
-  if (!dwr_plan(B, H, W, Ho, Wo, C, stride, C, C, d)) return 0;
-  if (ncb) *ncb = d.ncb;
-  return d.nps;
-}
-
-// -> CFP_OK, an error code, or 1 when the shape is not taken (the caller falls back to dw3x3_kernel<float>)
-int cfp_dwr_launch(const void* in, int in_ld, const void* w, const float* scale, const float* shift, void* out, int out_ld, float* partial,
-                   const float* w_red, int RD, float* hpart, int B, int H, int W, int C, int stride, int pad_t, int pad_l, int Ho, int Wo, int act, cfp_stream_t stream, const char* who) {
-  DwrPlan d, d0;
-  if (!g_dwr_mode || (act != CFP_ACT_SILU && act != CFP_ACT_RELU && act != CFP_ACT_NONE)) return 1;
-  const bool dense_ok = dwr_plan(B, H, W, Ho, Wo, C, stride, C, C, d0);          // what cfp_dwr_slots told the caller (it sized `partial` by it)
-  if (!dwr_plan(B, H, W, Ho, Wo, C, stride, in_ld, out_ld, d) || !dense_ok || d0.nps != d.nps) {
-    if ((partial || hpart) && dense_ok) { cfp_set_error(std::string(who) + ": row pitch too large for the float32 depthwise kernel"); return CFP_ESHAPE; }
-    return 1;
-  }
+int dwr_launch(const DwrPlan& d, const void* in, int in_ld, const void* w, const float* scale, const float* shift, void* out, int out_ld,
+               float* partial, const float* w_red, int RD, float* hpart, int B, int H, int W, int C, int stride, int pad_t, int pad_l,
+               int Ho, int Wo, int act, cfp_stream_t stream, const char* who) {
   DwrP p;
   p.in = (const float*)in; p.w = (const float*)w; p.scale = scale; p.shift = shift; p.out = (float*)out; p.partial = partial;
   p.w_red = w_red; p.hpart = hpart; p.RD = RD;
@@ -238,10 +211,19 @@ int cfp_dwr_launch(const void* in, int in_ld, const void* w, const float* scale,
   const long long wgs = (long long)B * d.ncb * d.nps;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // the activation is a template argument (one register budget per variant: erff's temporaries would set it for all of them otherwise)
-#define DWR(ST, AC) hipLaunchKernelGGL((dw3x3_rows_kernel<ST, AC>), dim3((unsigned)wgs), dim3(256), 0, s, p)
-  if (act == CFP_ACT_SILU) { if (stride == 1) DWR(1, CFP_ACT_SILU); else DWR(2, CFP_ACT_SILU); }
-  else if (act == CFP_ACT_RELU) { if (stride == 1) DWR(1, CFP_ACT_RELU); else DWR(2, CFP_ACT_RELU); }
-  else { if (stride == 1) DWR(1, CFP_ACT_NONE); else DWR(2, CFP_ACT_NONE); }
+#define DWR(AC)                                                                                           \
+  do {                                                                                                    \
+    if (stride == 1) hipLaunchKernelGGL((dw3x3_rows_kernel<1, AC>), dim3((unsigned)wgs), dim3(256), 0, s, p); \
+    else hipLaunchKernelGGL((dw3x3_rows_kernel<2, AC>), dim3((unsigned)wgs), dim3(256), 0, s, p);           \
+  } while (0)
+  switch (act) {
+    case CFP_ACT_SILU: DWR(CFP_ACT_SILU); break;
+    case CFP_ACT_RELU: DWR(CFP_ACT_RELU); break;
+    case CFP_ACT_LRELU: DWR(CFP_ACT_LRELU); break;
+    case CFP_ACT_GELU: DWR(CFP_ACT_GELU); break;
+    case CFP_ACT_SIGMOID: DWR(CFP_ACT_SIGMOID); break;
+    default: DWR(CFP_ACT_NONE); break;
+  }
 #undef DWR
   return cfp_check_launch(who);
 }

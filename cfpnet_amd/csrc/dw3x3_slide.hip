@@ -21,7 +21,7 @@
 // 16 bits (tests: <= 1 ulp of the storage type, and bit-exact on small integers).
 #include <algorithm>
 
-#include "common.h"
+#include "dw3x3.h"
 
 namespace {
 
@@ -36,7 +36,6 @@ struct DwlP {
   int colsA;                 // allocated input columns per LDS row = (XS - 1) * stride + 3
   int rowpitch;              // LDS bytes per input row: colsA * 144 rounded up to 16 x odd (16 consecutive rows hit 16 different bank groups)
   FastDiv dcols;             // item -> (row, column) of the patch
-  float* dbg;                // diagnostic stamps [workgroup][8] (tools/dw_bench.py --stamps), or null; they feed no output value
 };
 
 constexpr int DWL_PP = 144;  // pixel pitch: 8 chunks of 16 bytes + 16 bytes of padding
@@ -61,8 +60,6 @@ __global__ __launch_bounds__(256, 4) void dw3x3_slide_kernel(DwlP p) {
   const int x0 = xs * p.XS, nx = min(p.XS, p.Wo - x0);
   const int iy0 = y0 * STRIDE - p.pad_t, ix0 = x0 * STRIDE - p.pad_l;
   const int nrows_in = (ny - 1) * STRIDE + 3, ncols_in = (nx - 1) * STRIDE + 3;
-  unsigned long long tk0 = 0, tk1 = 0, tk2 = 0, tr0 = 0;
-  if (p.dbg) { tk0 = __builtin_amdgcn_s_memtime(); tr0 = __builtin_amdgcn_s_memrealtime(); }
 
   // ---- per-lane constants: requested first, their latency hides under the patch loads ------------------------------------------
   const int cbase = (cv0 + 2 * g) * 8;
@@ -120,7 +117,6 @@ __global__ __launch_bounds__(256, 4) void dw3x3_slide_kernel(DwlP p) {
       if (dst[n] >= 0) *reinterpret_cast<u32x4*>(lds + dst[n]) = v[n];
   }
   __syncthreads();
-  if (p.dbg) tk1 = __builtin_amdgcn_s_memtime();
 
   // ---- 2. every wave slides along x on its own ---------------------------------------------------------------------------------------
   float csum[4] = {0.f, 0.f, 0.f, 0.f};
@@ -202,12 +198,6 @@ __global__ __launch_bounds__(256, 4) void dw3x3_slide_kernel(DwlP p) {
     });
   }
 
-  if (p.dbg && tid == 0) {
-    tk2 = __builtin_amdgcn_s_memtime();
-    const unsigned long long tr1 = __builtin_amdgcn_s_memrealtime();
-    float* d = p.dbg + (long long)blockIdx.x * 8;
-    d[0] = (float)(tk1 - tk0); d[1] = (float)(tk2 - tk1); d[2] = 0.f; d[3] = (float)(tr0 & 0xffffff); d[4] = (float)(tr1 & 0xffffff); d[5] = 4.f;
-  }
   // ---- 3. channel sums of the task (rows in the 16-lane butterfly's fixed order) ---------------------------------------------------------
   if (p.partial == nullptr && p.hpart == nullptr) return;
 #pragma unroll
@@ -245,10 +235,7 @@ __global__ __launch_bounds__(256, 4) void dw3x3_slide_kernel(DwlP p) {
 
 // Work decomposition: y-runs of 16 output rows, x-segments of XS columns chosen so that the launch has >= ~3 workgroups per CU with
 // the least halo; the patch must fit the per-thread load count of the kernel.
-struct DwlPlan { int XS, nxs, nyr, colsA, rowpitch; size_t lds; };
-int g_dwl_force_xs = 0;        // cfp_debug_set key 9 (tools/dw_bench.py --sweep-xs)
-
-static bool dwl_plan(int B, int Ho, int Wo, int C, int stride, DwlPlan& d) {
+bool dwl_plan(int B, int Ho, int Wo, int C, int stride, int force_xs, DwlPlan& d) {
   const int ncb = cdiv(C, 64), nyr = cdiv(Ho, 16);
   const int rows = 15 * stride + 3, nld = stride == 1 ? 8 : 10;
   const int xs_max = stride == 1 ? 12 : 4;
@@ -256,7 +243,7 @@ static bool dwl_plan(int B, int Ho, int Wo, int C, int stride, DwlPlan& d) {
   for (int XS = 2; XS <= xs_max && XS <= std::max(Wo, 2); ++XS) {
     const int colsA = (XS - 1) * stride + 3;
     if (rows * colsA * 8 > 256 * nld) continue;
-    if (g_dwl_force_xs && XS != g_dwl_force_xs) continue;
+    if (force_xs && XS != force_xs) continue;
     const int nxs = cdiv(Wo, XS);
     const long long tasks = (long long)B * ncb * nyr * nxs;
     const double halo = (double)((std::min(XS, Wo) - 1) * stride + 3) / (std::min(XS, Wo) * stride);
@@ -275,19 +262,9 @@ static bool dwl_plan(int B, int Ho, int Wo, int C, int stride, DwlPlan& d) {
   return d.lds <= 64 * 1024 && (long long)B * ncb * nyr * d.nxs < (1ll << 31);
 }
 
-void cfp_dwl_debug_set(int value) { g_dwl_force_xs = value; }
-
-int cfp_dwl_slots(int B, int Ho, int Wo, int C, int stride) {
-  DwlPlan d;
-  return dwl_plan(B, Ho, Wo, C, stride, d) ? d.nyr * d.nxs : 0;
-}
-
-// -> CFP_OK, an error code, or 1 when the shape is not taken (the caller falls back to dw3x3_mfma_kernel)
-int cfp_dwl_launch(const void* in, int in_ld, const void* w, const float* scale, const float* shift, void* out, int out_ld, float* partial,
-                   const float* w_red, int RD, float* hpart, int B, int H, int W, int C, int stride, int pad_t, int pad_l, int Ho, int Wo,
-                   int act, int dtype, cfp_stream_t stream, const char* who) {
-  DwlPlan d;
-  if (!dwl_plan(B, Ho, Wo, C, stride, d)) return 1;
+int dwl_launch(const DwlPlan& d, const void* in, int in_ld, const void* w, const float* scale, const float* shift, void* out, int out_ld,
+               float* partial, const float* w_red, int RD, float* hpart, int B, int H, int W, int C, int stride, int pad_t, int pad_l,
+               int Ho, int Wo, int act, int dtype, cfp_stream_t stream, const char* who) {
   DwlP p;
   p.in = (const bf16_t*)in; p.w = (const bf16_t*)w; p.scale = scale; p.shift = shift; p.out = (bf16_t*)out; p.partial = partial;
   p.w_red = w_red; p.hpart = hpart; p.RD = RD;
@@ -295,11 +272,6 @@ int cfp_dwl_launch(const void* in, int in_ld, const void* w, const float* scale,
   p.B = B; p.H = H; p.W = W; p.C = C; p.pad_t = pad_t; p.pad_l = pad_l; p.Ho = Ho; p.Wo = Wo; p.act = act;
   p.XS = d.XS; p.nxs = d.nxs; p.nyr = d.nyr; p.ncb = cdiv(C, 64); p.colsA = d.colsA; p.rowpitch = d.rowpitch;
   p.dcols = make_fastdiv((unsigned)d.colsA);
-  p.dbg = nullptr;
-  if (act >= 100) {             // diagnostic launch: stamps behind the partial-sum area (the caller sized it: tools/dw_bench.py)
-    act -= 100; p.act = act;
-    if (partial) p.dbg = partial + (long long)B * d.nyr * d.nxs * C;
-  }
   const long long tasks = (long long)B * p.ncb * d.nyr * d.nxs;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
 #define DWL_LAUNCH(HH, ST)                                                                                                          \

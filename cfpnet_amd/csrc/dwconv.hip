@@ -7,7 +7,7 @@
 //          served by L2; column re-use by registers.
 // dwlarge: LKPM's 7x7 / 15x15 / 31x31 depthwise convs (C = 128 / 64 / 32).  Up to 480 FLOP/byte
 //          -> vector-FMA bound; design notes at the kernel.
-#include "common.h"
+#include "dw3x3.h"
 
 namespace {
 
@@ -228,12 +228,6 @@ __global__ __launch_bounds__(256) void dw3x3_mfma_kernel(const bf16_t* __restric
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 15, q = lane >> 4;         // B/D column (pixel) and k-chunk / D row block
-  // diagnostic path of the same kernel (tools/dw_bench.py --stamps): act >= 100 writes per-workgroup phase
-  // stamps AFTER the partial-sum area; the stamps feed no output value
-  const bool stamps = act >= 100;
-  if (stamps) act -= 100;
-  unsigned long long tk0 = 0, tk1 = 0, tk2 = 0, tr0 = 0;
-  if (stamps) { tk0 = __builtin_amdgcn_s_memtime(); tr0 = __builtin_amdgcn_s_memrealtime(); }
 
   // per-lane constants are requested BEFORE the tile staging so that their latency hides under it
   short wv5[GPW][5];
@@ -301,7 +295,6 @@ __global__ __launch_bounds__(256) void dw3x3_mfma_kernel(const bf16_t* __restric
     }
   }
   __syncthreads();
-  if (stamps) tk1 = __builtin_amdgcn_s_memtime();
 
   // ---- 2. runs of 16 output pixels on the matrix cores -------------------------------------------------
   // unit list of the strip, in an order that keeps the in-place writes safe: for every block of RB rows,
@@ -321,7 +314,7 @@ __global__ __launch_bounds__(256) void dw3x3_mfma_kernel(const bf16_t* __restric
     const int g = wave + 4 * gi;                   // wave-uniform
     const int cbase = (cv0 + 2 * g) * 8;
     float csum[4] = {0.f, 0.f, 0.f, 0.f};
-    if (g < G && cbase < C && act != 99) {         // act 99: timing experiment (staging + copy-out only)
+    if (g < G && cbase < C) {
       s16x8 afr[5];                                // diagonal weight fragments: lane (row i = j, chunk q) holds A[i][k = 8q..8q+7]
       int toff[5];                                 // byte offset of this lane's tap (pair pr, slot q>>1) + its 16-byte vector
 #pragma unroll
@@ -399,12 +392,7 @@ __global__ __launch_bounds__(256) void dw3x3_mfma_kernel(const bf16_t* __restric
         }
       }
     } else {
-      if (partial != nullptr && g < G && cbase < C && j == 0) {
-        float* dst = partial + ((long long)b * nstrips + strip) * C + cbase + 4 * q;
-#pragma unroll
-        for (int r4 = 0; r4 < 4; ++r4) dst[r4] = 0.f;
-      }
-      if (hpart != nullptr && g < G && j == 0) {
+      if (hpart != nullptr && g < G && j == 0) {     // channels past C: zero sums for the dot products below
         float* cs = reinterpret_cast<float*>(tile + cs_off);
 #pragma unroll
         for (int r4 = 0; r4 < 4; ++r4) cs[16 * g + 4 * q + r4] = 0.f;
@@ -412,7 +400,6 @@ __global__ __launch_bounds__(256) void dw3x3_mfma_kernel(const bf16_t* __restric
     }
   }
   __syncthreads();
-  if (stamps) tk2 = __builtin_amdgcn_s_memtime();
 
   // squeeze-excite (round 3): the reduce FC is linear in the channel sums, so this workgroup adds ITS part of every hidden unit,
   //   hpart[b][strip * blocks + block][r] = sum_{c in block} w_reduce[r][c] * csum[c],
@@ -455,12 +442,6 @@ __global__ __launch_bounds__(256) void dw3x3_mfma_kernel(const bf16_t* __restric
     sdot += __shfl_xor(sdot, 1, 64);
     sdot += __shfl_xor(sdot, 2, 64);
     if (hq == 0 && hr < RD) hpart[(((long long)b * nstrips + strip) * gridDim.x + bx) * RD + hr] = sdot;
-  }
-  if (stamps && partial != nullptr && tid == 0) {
-    const unsigned long long tk3 = __builtin_amdgcn_s_memtime(), tr1 = __builtin_amdgcn_s_memrealtime();
-    float* dbg = partial + (long long)B * nstrips * C + ((long long)blockIdx.y * gridDim.x + blockIdx.x) * 6;
-    dbg[0] = (float)(tk1 - tk0); dbg[1] = (float)(tk2 - tk1); dbg[2] = (float)(tk3 - tk2);
-    dbg[3] = (float)(tr0 & 0xffffff); dbg[4] = (float)(tr1 & 0xffffff); dbg[5] = 1.f;
   }
 }
 
@@ -823,39 +804,20 @@ hipError_t launch_dwlarge_any(const void* in, int in_ld, const float* w, const f
   return hipSuccess;
 }
 
-}  // namespace
+// Tuning knobs (cfp_debug_set), read by dw3x3_choose only:
+int g_dw_force_cvb = 0, g_dw_force_R = 0, g_dw_valu = 0;   // keys 3 / 4 / 5 (tools/dw_bench.py)
+// key 6: 2 = dw3x3_slide_kernel (round 3: register window over input columns, one barrier per workgroup), 1 = dw3x3_mfma_kernel.
+// The sliding-window kernel is the default: 14 vs 19 us at 30x40x816, 8.8 vs 12.6 at 15x20x1392.  (Round 3's software-pipelined
+// dw3x3_stream_kernel was measured slower than the MFMA kernel -- 24 vs 19 us at 30x40x816, profiles/r3_dw3x3_stream.md -- and is removed.)
+int g_dw_kernel16 = 2;
+int g_dwl_force_xs = 0;        // key 9: the sliding-window kernel's output columns per task (tools/dw_bench.py --sweep-xs)
+int g_dwr_mode = 1;            // key 10: 0 = float32 storage through the round-1 LDS-strip kernel instead of dw3x3_rows_kernel
+int g_dwr_force_R = 0;         // key 11: dw3x3_rows_kernel's output rows per run
 
-// dw3x3_stream.hip
-int cfp_dws_launch(const void* in, int in_ld, const void* w, const float* scale, const float* shift, void* out, int out_ld, float* partial,
-                   int B, int H, int W, int C, int stride, int pad_t, int pad_l, int Ho, int Wo, int act, int dtype, cfp_stream_t stream,
-                   const char* who);
-int cfp_dws_strips(int B, int Ho, int Wo, int C, int stride);
-void cfp_dws_debug_set(int key, int value);
-// dw3x3_slide.hip
-int cfp_dwl_launch(const void* in, int in_ld, const void* w, const float* scale, const float* shift, void* out, int out_ld, float* partial,
-                   const float* w_red, int RD, float* hpart, int B, int H, int W, int C, int stride, int pad_t, int pad_l, int Ho, int Wo,
-                   int act, int dtype, cfp_stream_t stream, const char* who);
-int cfp_dwl_slots(int B, int Ho, int Wo, int C, int stride);
-void cfp_dwl_debug_set(int value);
-// dw3x3_rows.hip: float32 storage, register-sliding rows (round 5)
-int cfp_dwr_launch(const void* in, int in_ld, const void* w, const float* scale, const float* shift, void* out, int out_ld, float* partial,
-                   const float* w_red, int RD, float* hpart, int B, int H, int W, int C, int stride, int pad_t, int pad_l, int Ho, int Wo, int act, cfp_stream_t stream, const char* who);
-int cfp_dwr_slots(int B, int H, int W, int Ho, int Wo, int C, int stride, int* ncb);
-void cfp_dwr_debug_set(int key, int value);
-int cfp_dwr_launch_slots(int B, int H, int W, int Ho, int Wo, int C, int stride, int in_ld, int out_ld);
-
-namespace {
 // Work decomposition of the depthwise 3x3 kernel: CVB channel vectors and R output rows per workgroup.
 // Among the configurations whose input strip fits 64 KB of LDS, take the one with the lowest
 // (halo read amplification) x (penalty for leaving CUs idle).
 struct DwPlan { int cvb, R, nstrips; size_t lds; };
-int g_dw_force_cvb = 0, g_dw_force_R = 0, g_dw_valu = 0;   // cfp_debug_set keys 3 / 4 / 5 (tools/dw_bench.py)
-// key 6: 2 = dw3x3_slide_kernel (round 3, second design: register window over input columns, one barrier per workgroup),
-//        0 = dw3x3_stream_kernel (round 3: persistent, LDS-DMA staged, row steps behind counted vmcnt waits; bit-identical outputs), 1 = dw3x3_mfma_kernel.
-// The pipelined kernel is correct and MEASURED SLOWER at batch 8 (24 vs 19 us at 30x40x816, profiles/r3_dw3x3_stream.md): its steps
-// run in lock-step (all 8 waves read LDS, then all run the SiLU), and per-lane LDS-DMA costs ~300 cycles per 1 KB instruction.  The
-// sliding-window kernel built on those findings is the default: 14 vs 19 us at 30x40x816, 8.8 vs 12.6 at 15x20x1392.
-int g_dw_no_stream = 2;
 inline DwPlan dw_plan(int B, int Ho, int Wo, int C, int stride, int ve, bool out_tile = false) {
   DwPlan best{8, 1, Ho, 0};
   double bc = 1e30;
@@ -895,41 +857,65 @@ inline DwPlan dw_plan(int B, int Ho, int Wo, int C, int stride, int ve, bool out
   return best;
 }
 
+// The depthwise 3x3 kernel a launch runs, its plan, and the partial-sum slots it writes per image (each slot: `hblocks` squeeze-excite
+// blocks).  The slot queries ask with the dense extents of the output (dw3x3_dense_choice), a launch with its real arguments.
+enum DwKind { DW_ROWS, DW_SLIDE, DW_MFMA, DW_VALU };
+struct DwChoice { DwKind kind; DwrPlan rows; DwlPlan slide; DwPlan strip; int slots, hblocks; };
+
+DwChoice dw3x3_choose(int B, int H, int W, int Ho, int Wo, int C, int stride, int in_ld, int out_ld, int dtype) {
+  DwChoice c{};
+  if (dtype == CFP_F32 && g_dwr_mode && dwr_plan(B, H, W, Ho, Wo, C, stride, in_ld, out_ld, g_dwr_force_R, c.rows)) {
+    c.kind = DW_ROWS; c.slots = c.rows.nps; c.hblocks = c.rows.ncb;
+    return c;
+  }
+  const bool mfma = is16(dtype) && C % 16 == 0 && !g_dw_valu;
+  if (mfma && g_dw_kernel16 == 2 && dwl_plan(B, Ho, Wo, C, stride, g_dwl_force_xs, c.slide)) {
+    c.kind = DW_SLIDE; c.slots = c.slide.nyr * c.slide.nxs; c.hblocks = cdiv(C, 64);
+    return c;
+  }
+  const int ve = vec_elems(dtype);
+  c.kind = mfma ? DW_MFMA : DW_VALU;
+  c.strip = dw_plan(B, Ho, Wo, C, stride, ve, mfma);
+  c.slots = c.strip.nstrips; c.hblocks = cdiv(C / ve, c.strip.cvb);
+  return c;
+}
+
+DwChoice dw3x3_dense_choice(int B, int Ho, int Wo, int C, int stride, int dtype) {
+  return dw3x3_choose(B, (Ho - 1) * stride + 3, (Wo - 1) * stride + 3, Ho, Wo, C, stride, C, C, dtype);
+}
+
 int dw3x3_launch(const void* in, int in_ld, const void* w, const float* scale, const float* shift, void* out, int out_ld,
                  float* partial, int B, int H, int W, int C, int stride, int pad_t, int pad_l, int Ho, int Wo, int act, int dtype,
                  cfp_stream_t stream, const char* who, const float* w_red = nullptr, int RD = 0, float* hpart = nullptr) {
   CFP_REQUIRE(in && w && out && scale && shift, CFP_EINVAL, std::string(who) + ": null pointer");
   CFP_REQUIRE(dtype_ok(dtype), CFP_EINVAL, std::string(who) + ": bad dtype");
+  CFP_REQUIRE(act >= CFP_ACT_NONE && act <= CFP_ACT_SIGMOID, CFP_EINVAL, std::string(who) + ": bad activation");
   const int ve = vec_elems(dtype);
   CFP_REQUIRE(stride == 1 || stride == 2, CFP_ESHAPE, std::string(who) + ": stride must be 1 or 2");
   CFP_REQUIRE(B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && C > 0 && C % 8 == 0 && in_ld % ve == 0 && out_ld % ve == 0 &&
                   in_ld >= C && out_ld >= C, CFP_ESHAPE, std::string(who) + ": bad shape");
   CFP_REQUIRE(aligned16(in) && aligned16(w) && aligned16(out) && aligned16(scale) && aligned16(shift), CFP_EINVAL,
               std::string(who) + ": pointers must be 16-byte aligned");
-  const bool mfma = is16(dtype) && C % 16 == 0 && !g_dw_valu;
-  CFP_REQUIRE(hpart == nullptr || ((mfma || dtype == CFP_F32) && w_red && RD > 0 && RD <= 64 && aligned16(w_red)), CFP_ESHAPE,
+  const DwChoice d = dw3x3_choose(B, H, W, Ho, Wo, C, stride, in_ld, out_ld, dtype);
+  CFP_REQUIRE(hpart == nullptr || ((d.kind != DW_VALU || dtype == CFP_F32) && w_red && RD > 0 && RD <= 64 && aligned16(w_red)), CFP_ESHAPE,
               std::string(who) + ": the squeeze-excite partials need R <= 64 and, in 16-bit storage, C % 16 == 0");
-  if (dtype == CFP_F32 && act != 99) {
-    // float32 storage (the default f16x3 mode): the register-sliding kernel (dw3x3_rows.hip), no LDS, no barrier
-    const int rc = cfp_dwr_launch(in, in_ld, w, scale, shift, out, out_ld, partial, w_red, RD, hpart, B, H, W, C, stride, pad_t, pad_l, Ho, Wo, act, stream, who);
-    if (rc != 1) return rc;
+  if (partial || hpart) {
+    // the caller sized `partial` / `hpart` by cfp_dwconv3x3_strips / _se_parts, which do not see the input extent or the row pitches
+    const DwChoice q = dw3x3_dense_choice(B, Ho, Wo, C, stride, dtype);
+    CFP_REQUIRE(q.kind == d.kind && q.slots == d.slots, CFP_ESHAPE,
+                std::string(who) + ": the input extent or row pitch changes the kernel plan the partial-sum slot count was queried for");
   }
-  if (mfma && g_dw_no_stream == 2 && act != 99) {
-    // the sliding-window kernel (dw3x3_slide.hip): register window over input columns, one barrier per workgroup
-    const int rc = cfp_dwl_launch(in, in_ld, w, scale, shift, out, out_ld, partial, w_red, RD, hpart, B, H, W, C, stride, pad_t, pad_l, Ho, Wo,
-                                  act, dtype, stream, who);
-    if (rc != 1) return rc;
-  }
-  if (mfma && !g_dw_no_stream && hpart == nullptr) {
-    // the software-pipelined kernel (dw3x3_stream.hip): same arithmetic, load / compute / store overlapped inside a workgroup
-    const int rc = cfp_dws_launch(in, in_ld, w, scale, shift, out, out_ld, partial, B, H, W, C, stride, pad_t, pad_l, Ho, Wo, act, dtype, stream, who);
-    if (rc != 1) return rc;
-  }
-  const DwPlan d = dw_plan(B, Ho, Wo, C, stride, ve, mfma);
-  CFP_REQUIRE((long long)B * d.nstrips <= 65535, CFP_ESHAPE, std::string(who) + ": grid too large");
-  CFP_REQUIRE(d.lds <= 64 * 1024, CFP_ESHAPE, std::string(who) + ": map too wide for the LDS strip");
+  if (d.kind == DW_ROWS)
+    return dwr_launch(d.rows, in, in_ld, w, scale, shift, out, out_ld, partial, w_red, RD, hpart, B, H, W, C, stride, pad_t, pad_l, Ho, Wo, act,
+                      stream, who);
+  if (d.kind == DW_SLIDE)
+    return dwl_launch(d.slide, in, in_ld, w, scale, shift, out, out_ld, partial, w_red, RD, hpart, B, H, W, C, stride, pad_t, pad_l, Ho, Wo,
+                      act, dtype, stream, who);
+  const DwPlan& p = d.strip;
+  CFP_REQUIRE((long long)B * p.nstrips <= 65535, CFP_ESHAPE, std::string(who) + ": grid too large");
+  CFP_REQUIRE(p.lds <= 64 * 1024, CFP_ESHAPE, std::string(who) + ": map too wide for the LDS strip");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  dim3 grid(cdiv(C / ve, d.cvb), B * d.nstrips);
+  dim3 grid(cdiv(C / ve, p.cvb), B * p.nstrips);
 #define DW_LAUNCH(T, S, V)                                                                                                \
   do {                                                                                                                    \
     static bool attr = false;                                                                                             \
@@ -938,10 +924,10 @@ int dw3x3_launch(const void* in, int in_ld, const void* w, const float* scale, c
       if (e != hipSuccess) { cfp_set_error(std::string(who) + ": " + hipGetErrorString(e)); return CFP_EHIP; }            \
       attr = true;                                                                                                        \
     }                                                                                                                     \
-    hipLaunchKernelGGL((dw3x3_kernel<T, S, V>), grid, dim3(256), d.lds, s, (const T*)in, in_ld, (const T*)w, scale, shift,  \
-                       (T*)out, out_ld, partial, B, H, W, C, pad_t, pad_l, Ho, Wo, act, d.R, d.nstrips, w_red, RD, hpart);  \
+    hipLaunchKernelGGL((dw3x3_kernel<T, S, V>), grid, dim3(256), p.lds, s, (const T*)in, in_ld, (const T*)w, scale, shift,  \
+                       (T*)out, out_ld, partial, B, H, W, C, pad_t, pad_l, Ho, Wo, act, p.R, p.nstrips, w_red, RD, hpart);  \
   } while (0)
-#define DW_CVB(T, S) do { if (d.cvb == 16) DW_LAUNCH(T, S, 16); else DW_LAUNCH(T, S, 8); } while (0)
+#define DW_CVB(T, S) do { if (p.cvb == 16) DW_LAUNCH(T, S, 16); else DW_LAUNCH(T, S, 8); } while (0)
 #define DWM_LAUNCH(HH, S, V)                                                                                                  \
   do {                                                                                                                    \
     static bool attr = false;                                                                                             \
@@ -950,11 +936,12 @@ int dw3x3_launch(const void* in, int in_ld, const void* w, const float* scale, c
       if (e != hipSuccess) { cfp_set_error(std::string(who) + ": " + hipGetErrorString(e)); return CFP_EHIP; }            \
       attr = true;                                                                                                        \
     }                                                                                                                     \
-    hipLaunchKernelGGL((dw3x3_mfma_kernel<HH, S, V>), grid, dim3(256), d.lds, s, (const bf16_t*)in, in_ld, (const bf16_t*)w, scale, \
-                       shift, (bf16_t*)out, out_ld, partial, B, H, W, C, pad_t, pad_l, Ho, Wo, act, d.R, d.nstrips, w_red, RD, hpart, \
-                       (int)(d.lds - (size_t)V * 8 * sizeof(float)));                                                       \
+    hipLaunchKernelGGL((dw3x3_mfma_kernel<HH, S, V>), grid, dim3(256), p.lds, s, (const bf16_t*)in, in_ld, (const bf16_t*)w, scale, \
+                       shift, (bf16_t*)out, out_ld, partial, B, H, W, C, pad_t, pad_l, Ho, Wo, act, p.R, p.nstrips, w_red, RD, hpart, \
+                       (int)(p.lds - (size_t)V * 8 * sizeof(float)));                                                       \
   } while (0)
-#define DWM_CVB(HH, S) do { if (d.cvb == 16) DWM_LAUNCH(HH, S, 16); else DWM_LAUNCH(HH, S, 8); } while (0)
+#define DWM_CVB(HH, S) do { if (p.cvb == 16) DWM_LAUNCH(HH, S, 16); else DWM_LAUNCH(HH, S, 8); } while (0)
+  const bool mfma = d.kind == DW_MFMA;
   if (mfma && dtype == CFP_F16) { if (stride == 1) DWM_CVB(f16_t, 1); else DWM_CVB(f16_t, 2); }
   else if (mfma) { if (stride == 1) DWM_CVB(bf16_t, 1); else DWM_CVB(bf16_t, 2); }
   else if (dtype == CFP_BF16) { if (stride == 1) DW_CVB(bf16_t, 1); else DW_CVB(bf16_t, 2); }
@@ -968,10 +955,20 @@ int dw3x3_launch(const void* in, int in_ld, const void* w, const float* scale, c
 }
 }  // namespace
 
-void cfp_dw_debug_set(int key, int value) {
-  if (key == 3) g_dw_force_cvb = value; else if (key == 4) g_dw_force_R = value; else if (key == 5) g_dw_valu = value;
-  else if (key == 6) g_dw_no_stream = value; else if (key == 9) cfp_dwl_debug_set(value); else if (key == 10 || key == 11) cfp_dwr_debug_set(key, value);
-  else cfp_dws_debug_set(key, value);
+int cfp_dw_debug_set(int key, int value) {
+  switch (key) {
+    case 3: g_dw_force_cvb = value; return CFP_OK;
+    case 4: g_dw_force_R = value; return CFP_OK;
+    case 5: g_dw_valu = value; return CFP_OK;
+    case 6:
+      CFP_REQUIRE(value == 1 || value == 2, CFP_EINVAL, "cfp_debug_set: key 6 takes 1 (dw3x3_mfma_kernel) or 2 (dw3x3_slide_kernel)");
+      g_dw_kernel16 = value;
+      return CFP_OK;
+    case 9: g_dwl_force_xs = value; return CFP_OK;
+    case 10: g_dwr_mode = value; return CFP_OK;
+    case 11: g_dwr_force_R = value; return CFP_OK;
+    default: cfp_set_error("cfp_debug_set: unknown key"); return CFP_EINVAL;
+  }
 }
 
 extern "C" int cfp_dwconv3x3_nhwc(const void* in, int in_ld, const void* w, const float* scale, const float* shift,
@@ -983,24 +980,13 @@ extern "C" int cfp_dwconv3x3_nhwc(const void* in, int in_ld, const void* w, cons
 
 extern "C" int cfp_dwconv3x3_strips(int B, int Ho, int Wo, int C, int stride, int dtype) {
   if (B <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || (stride != 1 && stride != 2)) return 0;
-  if (dtype == CFP_F32) {
-    const int n = cfp_dwr_slots(B, (Ho - 1) * stride + 3, (Wo - 1) * stride + 3, Ho, Wo, C, stride, nullptr);
-    if (n > 0) return n;
-  }
-  if (is16(dtype) && C % 16 == 0 && !g_dw_valu && g_dw_no_stream == 2) {
-    const int n = cfp_dwl_slots(B, Ho, Wo, C, stride);
-    if (n > 0) return n;
-  }
-  if (is16(dtype) && C % 16 == 0 && !g_dw_valu && !g_dw_no_stream) {
-    const int n = cfp_dws_strips(B, Ho, Wo, C, stride);
-    if (n > 0) return n;
-  }
-  return dw_plan(B, Ho, Wo, C, stride, vec_elems(dtype), is16(dtype) && C % 16 == 0 && !g_dw_valu).nstrips;
+  return dw3x3_dense_choice(B, Ho, Wo, C, stride, dtype).slots;
 }
 
 extern "C" int cfp_dwconv3x3_launch_slots(int B, int H, int W, int Ho, int Wo, int C, int stride, int in_ld, int out_ld, int dtype) {
-  if (B <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || (stride != 1 && stride != 2) || dtype != CFP_F32) return 0;
-  return cfp_dwr_launch_slots(B, H, W, Ho, Wo, C, stride, in_ld, out_ld);
+  if (B <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || (stride != 1 && stride != 2)) return 0;
+  const DwChoice d = dw3x3_choose(B, H, W, Ho, Wo, C, stride, in_ld, out_ld, dtype), q = dw3x3_dense_choice(B, Ho, Wo, C, stride, dtype);
+  return d.kind == q.kind && d.slots == q.slots ? d.slots : 0;
 }
 
 extern "C" int cfp_dwconv3x3_sum_nhwc(const void* in, int in_ld, const void* w, const float* scale, const float* shift,
@@ -1012,21 +998,9 @@ extern "C" int cfp_dwconv3x3_sum_nhwc(const void* in, int in_ld, const void* w, 
 }
 
 extern "C" int cfp_dwconv3x3_se_parts(int B, int Ho, int Wo, int C, int stride, int dtype) {
-  if (B <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || (stride != 1 && stride != 2)) return 0;
-  if (dtype == CFP_F32 && C % 8 == 0) {     // float32 storage (the default f16x3 mode): the register-sliding kernel, else the LDS-strip one
-    int ncb = 0;
-    const int n = cfp_dwr_slots(B, (Ho - 1) * stride + 3, (Wo - 1) * stride + 3, Ho, Wo, C, stride, &ncb);
-    if (n > 0) return n * ncb;
-    const DwPlan d = dw_plan(B, Ho, Wo, C, stride, 4, false);
-    return d.nstrips * cdiv(C / 4, d.cvb);
-  }
-  if (!is16(dtype) || C % 16 != 0 || g_dw_valu) return 0;
-  if (g_dw_no_stream == 2) {
-    const int n = cfp_dwl_slots(B, Ho, Wo, C, stride);
-    if (n > 0) return n * cdiv(C, 64);
-  }
-  const DwPlan d = dw_plan(B, Ho, Wo, C, stride, 8, true);
-  return d.nstrips * cdiv(C / 8, d.cvb);
+  if (B <= 0 || Ho <= 0 || Wo <= 0 || C <= 0 || C % 8 != 0 || (stride != 1 && stride != 2)) return 0;
+  const DwChoice d = dw3x3_dense_choice(B, Ho, Wo, C, stride, dtype);
+  return d.kind != DW_VALU || dtype == CFP_F32 ? d.slots * d.hblocks : 0;   // 16-bit storage through the VALU kernel: no reduce-FC partials
 }
 
 extern "C" int cfp_dwconv3x3_se_nhwc(const void* in, int in_ld, const void* w, const float* scale, const float* shift, void* out, int out_ld,

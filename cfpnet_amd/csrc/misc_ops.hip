@@ -339,7 +339,7 @@ __global__ __launch_bounds__(1024) void se_gate_fold_kernel(const float* __restr
 }
 
 // se_gate_fold2 (round 3): the squeeze-excite tail when the depthwise kernel has already taken the reduce FC's dot products.
-// The reduce layer is linear in the channel sums, so every workgroup of dw3x3_stream_kernel (image b, 64-channel block, row
+// The reduce layer is linear in the channel sums, so every workgroup of the depthwise 3x3 kernel (image b, channel block, pixel
 // range) contributes  hpart[b][k][r] = sum_{c in block} w_reduce[r][c] * (sum of its output pixels of channel c)  and what is
 // left here is
 //   phase A  hidden[r] = silu(inv_hw * sum_k hpart[b][k][r] + b_reduce[r])        K = blocks x ranges partials, added in k order

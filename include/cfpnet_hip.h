@@ -122,15 +122,17 @@ int cfp_conv2d_variant(int M, int Cout);
 /* Test/benchmark knobs, not for production use (process-global, not thread-safe):
  * key 0 = force second-generation variant v, or 200 + v = direct 3x3 variant v (-1 = automatic), key 1 = force K-splits (-1 = automatic),
  * key 2 = 1 routes bf16 through the first-generation kernel; keys 3 / 4 = depthwise 3x3 channel vectors per
- * workgroup (8 / 16) and output rows per strip (0 = automatic); key 5 = 1 forces the VALU depthwise kernel; keys 6-21 are
- * listed in README.md ("Kernel choices") and at the dispatch in csrc/conv_igemm.hip. */
+ * workgroup (8 / 16) and output rows per strip (0 = automatic); key 5 = 1 forces the VALU depthwise kernel; key 6 = 16-bit depthwise
+ * 3x3 kernel (1 or 2, CFP_EINVAL otherwise); keys 7 and 8 are unused (CFP_EINVAL); keys 9-39 are listed in README.md ("Kernel choices")
+ * and at the dispatch in csrc/conv_igemm.hip.  The depthwise keys change the slot counts of cfp_dwconv3x3_strips / _se_parts too. */
 int cfp_debug_set(int key, int value);
 
 /* Depthwise 3x3 convolution, stride 1/2, explicit (TF-"SAME", possibly asymmetric) padding, fused
  * BatchNorm scale/shift + activation.  w packed [9][C].  HBM-bandwidth-bound.
  * Replaces timm InvertedResidual.conv_dw + bn2 + SiLU (encoder.py:66-69, 24 convs).
- * Kernels: float32 storage -> dw3x3_rows_kernel (round 5: register-sliding rows, no LDS; csrc/dw3x3_rows.hip; SiLU / ReLU / none), 16-bit storage with
- * C % 16 == 0 -> dw3x3_slide_kernel (diagonal-weight MFMA, csrc/dw3x3_slide.hip), otherwise the LDS-strip kernel of csrc/dwconv.hip. */
+ * Kernels: float32 storage -> dw3x3_rows_kernel (round 5: register-sliding rows, no LDS; csrc/dw3x3_rows.hip), 16-bit storage with
+ * C % 16 == 0 -> dw3x3_slide_kernel (diagonal-weight MFMA, csrc/dw3x3_slide.hip), otherwise the LDS-strip kernel of csrc/dwconv.hip.
+ * act is one of CFP_ACT_* (CFP_EINVAL otherwise, on all three depthwise 3x3 entry points); the kernel choice does not depend on it. */
 int cfp_dwconv3x3_nhwc(const void* in, int in_ld, const void* w, const float* scale, const float* shift,
                        void* out, int out_ld, int B, int H, int W, int C, int stride, int pad_t, int pad_l,
                        int Ho, int Wo, int act, int dtype, cfp_stream_t stream);
@@ -141,9 +143,10 @@ int cfp_dwconv3x3_nhwc(const void* in, int in_ld, const void* w, const float* sc
  * pass: cfp_se_hidden(partial, nsplit = strips, ...) consumes it directly.  Strip order and the
  * in-strip reduction order are fixed: the sums are run-to-run deterministic. */
 int cfp_dwconv3x3_strips(int B, int Ho, int Wo, int C, int stride, int dtype);
-/* The number of slots the float32-storage LAUNCH will write for these full arguments (0: it does not take the shape and the older kernel's
- * own count applies).  Host-side only, no GPU work: tests/test_abi.py sweeps shapes and checks that it equals cfp_dwconv3x3_strips, which is
- * asked WITHOUT the input extent -- a mismatch would be an out-of-bounds write into `partial` (found and fixed in round 5). */
+/* The number of partial-sum slots per image a cfp_dwconv3x3_sum_nhwc LAUNCH writes for these full arguments, any dtype; 0 when such a
+ * launch refuses them (CFP_ESHAPE: the input extent or a row pitch gives another kernel or slot count than cfp_dwconv3x3_strips, which is
+ * asked WITHOUT them and sized `partial`).  Host-side only, no GPU work: tests/test_abi.py sweeps shapes and checks that it equals
+ * cfp_dwconv3x3_strips (a mismatch was an out-of-bounds write into `partial`, found and fixed in round 5). */
 int cfp_dwconv3x3_launch_slots(int B, int H, int W, int Ho, int Wo, int C, int stride, int in_ld, int out_ld, int dtype);
 int cfp_dwconv3x3_sum_nhwc(const void* in, int in_ld, const void* w, const float* scale, const float* shift,
                            void* out, int out_ld, float* partial, int B, int H, int W, int C, int stride,

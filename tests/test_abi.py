@@ -100,35 +100,49 @@ def test_deltar_container_on_cpu():
         make_model(args)
 
 
-def test_float32_depthwise_slot_count_is_the_same_with_and_without_the_input_extent():
+def test_depthwise_slot_count_is_the_same_with_and_without_the_input_extent(lib):
     """Round 5 bug: `cfp_dwconv3x3_strips` (asked before the launch, without H / W) and the launch's own plan used slightly different byte
     counts in their time model, chose different run lengths at batch 4 and the kernel wrote more `partial` slots than the caller had
-    allocated (a GPU memory fault in tools/probes/x3_b4_check.py).  The plan now depends on the output extent only; this sweep pins it for
-    every encoder shape x batch 1..32 x both paddings of a SAME-padded input, and for odd sizes."""
+    allocated (a GPU memory fault in tools/probes/x3_b4_check.py).  Both queries and the launch now take the kernel and its plan from one
+    chooser, which a launch with partials also asks with the dense arguments the queries use.  This sweep pins it for every encoder shape
+    x batch 1..32 x both paddings of a SAME-padded input, odd sizes and channel counts that are not a multiple of 16 (the VALU strip
+    kernel in 16-bit storage), in all three storage types; the squeeze-excite query counts whole slots of the same plan."""
     from cfpnet_amd import hip
-    lib = hip.load()
     n = 0
     for (H, W, C, s) in [(60, 80, 224, 2), (30, 40, 448, 1), (30, 40, 672, 1), (30, 40, 816, 1), (30, 40, 816, 2), (15, 20, 1392, 1),
                          (52, 68, 224, 2), (26, 34, 672, 1), (13, 17, 1392, 1), (80, 120, 224, 2), (40, 60, 816, 1), (20, 30, 1392, 1),
-                         (7, 5, 16, 1), (33, 130, 48, 2), (17, 3, 40, 1), (1, 1, 8, 1)]:
+                         (7, 5, 16, 1), (33, 130, 48, 2), (17, 3, 40, 1), (1, 1, 8, 1), (30, 40, 232, 1), (60, 80, 200, 2)]:
         Ho, Wo = -(-H // s), -(-W // s)
-        for B in list(range(1, 33)) + [48, 64, 128, 256]:
-            want = lib.cfp_dwconv3x3_strips(B, Ho, Wo, C, s, hip.F32)
-            for (h, w) in ((H, W), (Ho * s, Wo * s), ((Ho - 1) * s + 1, (Wo - 1) * s + 1)):
-                for ld in (C, C + 12):
-                    got = lib.cfp_dwconv3x3_launch_slots(B, h, w, Ho, Wo, C, s, ld, ld, hip.F32)
-                    assert got == want and got > 0, (B, H, W, C, s, h, w, ld, got, want)
-                    n += 1
-    assert n > 3000
+        for dt in (hip.F32, hip.BF16, hip.F16):
+            ve = 4 if dt == hip.F32 else 8
+            for B in list(range(1, 33)) + [48, 64, 128, 256]:
+                want = lib.cfp_dwconv3x3_strips(B, Ho, Wo, C, s, dt)
+                assert want > 0, (B, H, W, C, s, dt)
+                dense = lib.cfp_dwconv3x3_launch_slots(B, (Ho - 1) * s + 3, (Wo - 1) * s + 3, Ho, Wo, C, s, C, C, dt)
+                assert dense == want, (B, H, W, C, s, dt, dense, want)
+                for (h, w) in ((H, W), (Ho * s, Wo * s), ((Ho - 1) * s + 1, (Wo - 1) * s + 1)):
+                    for ld in (C, C + 3 * ve):
+                        got = lib.cfp_dwconv3x3_launch_slots(B, h, w, Ho, Wo, C, s, ld, ld, dt)
+                        assert got == want, (B, H, W, C, s, dt, h, w, ld, got, want)
+                        n += 1
+                se = lib.cfp_dwconv3x3_se_parts(B, Ho, Wo, C, s, dt)
+                if dt != hip.F32 and C % 16:
+                    assert se == 0, (B, H, W, C, s, dt, se)          # the VALU kernel leaves no reduce-FC partials in 16-bit storage
+                else:
+                    assert se > 0 and se % want == 0, (B, H, W, C, s, dt, se, want)
+    assert n > 3 * 3000
+    # an input of more than 2^30 bytes per image (row pitch 56 000) takes float32 storage off the rows kernel the queries chose: a launch
+    # with partials refuses it (CFP_ESHAPE) and the query says so with 0
+    assert lib.cfp_dwconv3x3_launch_slots(1, 60, 80, 60, 80, 224, 1, 56000, 224, hip.F32) == 0
+    assert lib.cfp_dwconv3x3_launch_slots(1, 60, 80, 60, 80, 224, 1, 56000, 224, hip.BF16) == lib.cfp_dwconv3x3_strips(1, 60, 80, 224, 1, hip.BF16)
 
 
-def test_f16x3_plan_picks_the_occupancy_builds_only_for_in_flight_launches():
+def test_f16x3_plan_picks_the_occupancy_builds_only_for_in_flight_launches(lib):
     """The 64x64 / 128x32 / 64x128 f16x3 tiles exist a second time under a register budget (variant ids 34-36: one more resident workgroup per
     CU; faster with several batches in flight, slower alone).  The plan must hand them out under the in-flight hint only, never for split-K
     or per-image split plans, and every other variant must be unchanged by the hint's occupancy rule (cfp_debug_set key 32 switches it off)."""
     import ctypes
     from cfpnet_amd import hip
-    lib = hip.load()
 
     def plan(M, N, K, rpb=0, B=1):
         v, s = ctypes.c_int(0), ctypes.c_int(0)

@@ -840,14 +840,16 @@ def test_pointwise_conv_per_image_weights(B, HW, Cin, Cout, dtype):
     close(out.torch().float().cpu().reshape(B, HW, Cout), ref, dtype, f"per-image weights {B}x{HW}x{Cin}->{Cout}")
 
 
+ACT_REF = {hip.ACT_NONE: lambda t: t, hip.ACT_RELU: F.relu, hip.ACT_LRELU: lambda t: F.leaky_relu(t, 0.01), hip.ACT_SILU: F.silu,
+           hip.ACT_GELU: F.gelu, hip.ACT_SIGMOID: torch.sigmoid}
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("act", [hip.ACT_NONE, hip.ACT_RELU, hip.ACT_LRELU, hip.ACT_GELU, hip.ACT_SIGMOID])
 def test_conv_activations_no_scale(act, dtype):
     x = q(rnd(1, 64, 6, 10, seed=7), dtype)
     w = q(rnd(96, 64, 1, 1, seed=8, scale=0.2), dtype)
-    ref = F.conv2d(x, w)
-    ref = {hip.ACT_NONE: lambda t: t, hip.ACT_RELU: F.relu, hip.ACT_LRELU: lambda t: F.leaky_relu(t, 0.01),
-           hip.ACT_GELU: F.gelu, hip.ACT_SIGMOID: torch.sigmoid}[act](ref)
+    ref = ACT_REF[act](F.conv2d(x, w))
     out = ops.new_act(60, 96, dtype, DEV)
     ops.conv2d(to_act(nhwc(x), dtype), w.reshape(96, 64).to(dtype).to(DEV), None, None, out, 1, 6, 10, 1, 1, 1, 0, 0, 6, 10, act)
     close(from_nhwc(out.torch(), 1, 6, 10), ref, dtype)
@@ -916,32 +918,79 @@ def test_dwconv_large_x3_toeplitz(case):
             lib.cfp_debug_set(30, int(os.environ.get("CFP_DWL3_DEFAULT", "1")))
 
 
+_FUSED_SUM_CASES = [(2, 30, 40, 224, 2, (0, 0, 1, 1)), (2, 15, 20, 1392, 1, (1, 1, 1, 1)), (3, 30, 40, 816, 1, (1, 1, 1, 1)),
+                    (2, 9, 7, 64, 2, (1, 1, 1, 1)), (1, 5, 3, 8, 1, (1, 1, 1, 1))]
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("case", [(2, 30, 40, 224, 2, (0, 0, 1, 1)), (2, 15, 20, 1392, 1, (1, 1, 1, 1)), (3, 30, 40, 816, 1, (1, 1, 1, 1)),
-                                  (2, 9, 7, 64, 2, (1, 1, 1, 1)), (1, 5, 3, 8, 1, (1, 1, 1, 1))])
+@pytest.mark.parametrize("case", _FUSED_SUM_CASES)
 def test_dwconv3x3_with_fused_channel_sums(case, dtype):
+    _dwconv3x3_with_fused_channel_sums(case, dtype, hip.ACT_SILU)
+
+
+@pytest.mark.parametrize("act", [a for a in sorted(ACT_REF) if a != hip.ACT_SILU])
+@pytest.mark.parametrize("dtype", DTYPES)
+@pytest.mark.parametrize("case", _FUSED_SUM_CASES)
+def test_dwconv3x3_with_fused_channel_sums_every_activation(case, dtype, act):
+    _dwconv3x3_with_fused_channel_sums(case, dtype, act)
+
+
+def _dwconv3x3_with_fused_channel_sums(case, dtype, act):
+    """Every activation writes exactly the partial-sum slots cfp_dwconv3x3_strips reports (a float32 launch with an activation the rows
+    kernel did not take once fell back to a kernel with more slots): the guard of as many slots again behind them stays NaN."""
     B, H, W, Cc, s, (pt, pl, pb, pr) = case
     x = q(rnd(B, Cc, H, W, seed=1), dtype)
     w = q(rnd(Cc, 1, 3, 3, seed=2, scale=0.4), dtype)
     scale, shift = rnd(Cc, seed=3).abs() + 0.5, rnd(Cc, seed=4)
     Ho, Wo = (H + pt + pb - 3) // s + 1, (W + pl + pr - 3) // s + 1
     ref = F.conv2d(F.pad(x, (pl, pr, pt, pb)), w, None, s, 0, 1, Cc)
-    ref = F.silu(ref * scale[None, :, None, None] + shift[None, :, None, None])
+    ref = ACT_REF[act](ref * scale[None, :, None, None] + shift[None, :, None, None])
     wa = w.reshape(Cc, 9).t().contiguous().to(dtype).to(DEV)
     out = ops.new_act(B * Ho * Wo, Cc, dtype, DEV)
     ns = ops.dwconv3x3_strips(B, Ho, Wo, Cc, s, ops.DT[dtype])
-    part = torch.full((B, ns, Cc), float("nan"), device=DEV)
-    ops.dwconv3x3_sum(to_act(nhwc(x), dtype), wa, scale.to(DEV), shift.to(DEV), out, part, B, H, W, s, pt, pl, Ho, Wo, hip.ACT_SILU)
+    buf = torch.full((2 * B * ns * Cc,), float("nan"), device=DEV)      # the queried slots, then a guard of the same size
+    part = buf[:B * ns * Cc].view(B, ns, Cc)
+    ops.dwconv3x3_sum(to_act(nhwc(x), dtype), wa, scale.to(DEV), shift.to(DEV), out, part, B, H, W, s, pt, pl, Ho, Wo, act)
     torch.cuda.synchronize()
+    assert bool(buf[B * ns * Cc:].isnan().all()), "partial sums written past the slots cfp_dwconv3x3_strips reported"
     got = from_nhwc(out.torch(), B, Ho, Wo)
-    close(got, ref, dtype, f"dw3x3+sum {case}")
+    close(got, ref, dtype, f"dw3x3+sum {case} act {act}")
     sums = part.sum(1).cpu()
     want = ref.sum((2, 3))                      # sums of the activated tensor (taken before the storage rounding)
     assert torch.allclose(sums, want, rtol=1e-3, atol=3e-3 * float(want.abs().max())), float((sums - want).abs().max())
     part2 = torch.zeros_like(part)
-    ops.dwconv3x3_sum(to_act(nhwc(x), dtype), wa, scale.to(DEV), shift.to(DEV), out, part2, B, H, W, s, pt, pl, Ho, Wo, hip.ACT_SILU)
+    ops.dwconv3x3_sum(to_act(nhwc(x), dtype), wa, scale.to(DEV), shift.to(DEV), out, part2, B, H, W, s, pt, pl, Ho, Wo, act)
     torch.cuda.synchronize()
     assert torch.equal(part, part2)             # deterministic reduction order
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_dwconv3x3_rejects_an_unknown_activation(dtype):
+    """`act` outside CFP_ACT_NONE .. CFP_ACT_SIGMOID (99 and 100 + act once selected diagnostic kernel paths) is CFP_EINVAL on every depthwise
+    3x3 entry point, before any launch: output, partial sums and reduce-FC partials keep their contents."""
+    lib = hip.load()
+    B, H, W, Cc, s = 2, 15, 20, 224, 1
+    dt = ops.DT[dtype]
+    xin = to_act(nhwc(rnd(B, Cc, H, W, seed=1)), dtype)
+    wa = rnd(9, Cc, seed=2, scale=0.4).to(dtype).to(DEV)
+    scale, shift = torch.ones(Cc, device=DEV), torch.zeros(Cc, device=DEV)
+    out = ops.new_act(B * H * W, Cc, dtype, DEV)
+    out.buf.fill_(7)
+    RD = 16
+    wr = rnd(RD, Cc, seed=3).to(DEV)
+    part = torch.full((B * ops.dwconv3x3_strips(B, H, W, Cc, s, dt) * Cc,), float("nan"), device=DEV)
+    hpart = torch.full((B * ops.dwconv3x3_se_parts(B, H, W, Cc, s, dt) * RD,), float("nan"), device=DEV)
+    geo = (B, H, W, Cc, s, 1, 1, H, W)
+    for act in (6, 99, 103):
+        rcs = (lib.cfp_dwconv3x3_nhwc(xin.ptr, xin.ld, wa.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.ptr, out.ld, *geo, act, dt, 0),
+               lib.cfp_dwconv3x3_sum_nhwc(xin.ptr, xin.ld, wa.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.ptr, out.ld, part.data_ptr(),
+                                          *geo, act, dt, 0),
+               lib.cfp_dwconv3x3_se_nhwc(xin.ptr, xin.ld, wa.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.ptr, out.ld, wr.data_ptr(), RD,
+                                         hpart.data_ptr(), *geo, act, dt, 0))
+        assert rcs == (-1, -1, -1), (act, rcs)          # CFP_EINVAL
+        assert "activation" in hip.last_error()
+    torch.cuda.synchronize()
+    assert bool((out.buf == 7).all()) and bool(part.isnan().all()) and bool(hpart.isnan().all())
 
 
 @pytest.mark.parametrize("dtype", HALF)
@@ -1895,51 +1944,6 @@ def test_upsample_cat_conv3x3_through_the_halo_kernel(case, dtype):
 @pytest.mark.parametrize("dtype", HALF)
 @pytest.mark.parametrize("case", [(8, 30, 40, 816, 1), (8, 15, 20, 1392, 1), (8, 60, 80, 224, 2), (8, 30, 40, 816, 2), (8, 30, 40, 448, 1),
                                   (2, 26, 34, 672, 1), (2, 13, 17, 1392, 1), (2, 40, 60, 208, 1), (1, 20, 30, 1392, 1), (2, 52, 68, 224, 2),
-                                  (1, 7, 5, 16, 1), (3, 16, 16, 80, 1), (1, 33, 130, 48, 2)])
-def test_dwconv3x3_stream_kernel_equals_the_single_phase_kernel(case, dtype):
-    """dw3x3_stream_kernel (round 3: whole input image requested by LDS-DMA at kernel start, consumed in row steps behind counted
-    vmcnt waits, results stored beside the next step's compute) against dw3x3_mfma_kernel (load -> compute -> store), same
-    arithmetic: outputs BIT-identical on the encoder's shapes at the benched batch, the training / config-5 / smoke shapes
-    (row tails of 1 ... 14 pixels, ragged last row range, last channel block partly empty, stride 2 with TF-SAME padding), with
-    the tensors embedded in wider buffers (pitch > C); channel sums equal up to the order of the per-range partial sums."""
-    B, H, W, Cc, s = case
-    lib = hip.load()
-    Ho, Wo = -(-H // s), -(-W // s)
-    pt, pl = max((Ho - 1) * s + 3 - H, 0) // 2, max((Wo - 1) * s + 3 - W, 0) // 2
-    x = q(rnd(B, Cc, H, W, seed=11), dtype)
-    w = q(rnd(Cc, 1, 3, 3, seed=12, scale=0.4), dtype)
-    scale, shift = (rnd(Cc, seed=13).abs() + 0.5).to(DEV), rnd(Cc, seed=14).to(DEV)
-    wa = w.reshape(Cc, 9).t().contiguous().to(dtype).to(DEV)
-    xin = to_act(nhwc(x), dtype, ld=Cc + 24, c0=8)
-    res = []
-    try:
-        for old in (1, 0):
-            lib.cfp_debug_set(6, old)
-            buf = ops.new_act(B * Ho * Wo, Cc, dtype, DEV, ld=Cc + 16, zero=True)
-            out = ops.Act(buf.buf, 8, Cc)
-            ns = ops.dwconv3x3_strips(B, Ho, Wo, Cc, s, ops.DT[dtype])
-            part = torch.full((B, ns, Cc), float("nan"), device=DEV)
-            ops.dwconv3x3_sum(xin, wa, scale, shift, out, part, B, H, W, s, pt, pl, Ho, Wo, hip.ACT_SILU)
-            torch.cuda.synchronize()
-            res.append((buf.buf.clone(), part.sum(1).cpu(), ns))
-    finally:
-        lib.cfp_debug_set(6, 2)            # back to the default (the sliding-window kernel)
-    (o_old, s_old, _), (o_new, s_new, ns_new) = res
-    ref = F.silu(F.conv2d(F.pad(x, (pl, (Wo - 1) * s + 3 - W - pl, pt, (Ho - 1) * s + 3 - H - pt)), w, None, s, 0, 1, Cc)
-                 * scale.cpu()[None, :, None, None] + shift.cpu()[None, :, None, None])
-    close(from_nhwc(ops.Act(o_new, 8, Cc).torch(), B, Ho, Wo), ref, dtype, f"dw3x3 stream {case}")
-    close(from_nhwc(ops.Act(o_old, 8, Cc).torch(), B, Ho, Wo), ref, dtype, f"dw3x3 single-phase {case}")
-    if not torch.equal(o_old.view(torch.int16), o_new.view(torch.int16)):
-        d = (o_old.float() - o_new.float()).abs().reshape(B, Ho, Wo, -1)
-        idx = torch.nonzero(d > 0)
-        raise AssertionError(f"stream kernel output differs {case}: {idx.shape[0]} elements, first {idx[:6].tolist()}, max {float(d.max()):.3e}")
-    assert float(o_new[:, :8].float().abs().max()) == 0 and float(o_new[:, 8 + Cc:].float().abs().max()) == 0     # nothing outside the slice
-    assert torch.isfinite(s_new).all() and torch.allclose(s_new, s_old, rtol=2e-5, atol=2e-5 * float(s_old.abs().max()))
-
-
-@pytest.mark.parametrize("dtype", HALF)
-@pytest.mark.parametrize("case", [(8, 30, 40, 816, 1), (8, 15, 20, 1392, 1), (8, 60, 80, 224, 2), (8, 30, 40, 816, 2), (8, 30, 40, 448, 1),
-                                  (2, 26, 34, 672, 1), (2, 13, 17, 1392, 1), (2, 40, 60, 208, 1), (1, 20, 30, 1392, 1), (2, 52, 68, 224, 2),
                                   (1, 7, 5, 16, 1), (3, 16, 16, 80, 1), (1, 33, 130, 48, 2), (2, 17, 3, 32, 1)])
 def test_dwconv3x3_sliding_window_kernel(case, dtype):
     """dw3x3_slide_kernel (round 3: a wave owns 16 output rows of a 16-channel group and slides along x with a register window of three
@@ -1988,15 +1992,28 @@ def test_dwconv3x3_sliding_window_kernel(case, dtype):
     assert torch.isfinite(h_new).all() and torch.allclose(h_new, h_old, rtol=1e-4, atol=1e-4 * float(h_old.abs().max()))
 
 
-@pytest.mark.parametrize("case", [(8, 30, 40, 816, 1), (8, 15, 20, 1392, 1), (8, 60, 80, 224, 2), (8, 30, 40, 816, 2), (8, 30, 40, 448, 1),
-                                  (2, 26, 34, 672, 1), (2, 13, 17, 1392, 1), (2, 40, 60, 208, 1), (2, 52, 68, 224, 2),
-                                  (1, 7, 5, 16, 1), (3, 16, 16, 80, 1), (1, 33, 130, 48, 2), (2, 17, 3, 40, 1), (1, 1, 1, 8, 1), (2, 2, 9, 8, 2)])
+_ROWS_CASES = [(8, 30, 40, 816, 1), (8, 15, 20, 1392, 1), (8, 60, 80, 224, 2), (8, 30, 40, 816, 2), (8, 30, 40, 448, 1),
+               (2, 26, 34, 672, 1), (2, 13, 17, 1392, 1), (2, 40, 60, 208, 1), (2, 52, 68, 224, 2),
+               (1, 7, 5, 16, 1), (3, 16, 16, 80, 1), (1, 33, 130, 48, 2), (2, 17, 3, 40, 1), (1, 1, 1, 8, 1), (2, 2, 9, 8, 2)]
+
+
+@pytest.mark.parametrize("case", _ROWS_CASES)
 def test_dw3x3_rows_kernel_float32(case):
+    _dw3x3_rows_kernel_float32(case, hip.ACT_SILU)
+
+
+@pytest.mark.parametrize("act", [a for a in sorted(ACT_REF) if a != hip.ACT_SILU])
+@pytest.mark.parametrize("case", [_ROWS_CASES[2], _ROWS_CASES[6], _ROWS_CASES[11], _ROWS_CASES[12]])
+def test_dw3x3_rows_kernel_float32_every_activation(case, act):
+    _dw3x3_rows_kernel_float32(case, act)
+
+
+def _dw3x3_rows_kernel_float32(case, act):
     """dw3x3_rows_kernel (round 5; float32 storage = the default f16x3 mode's depthwise 3x3: a wave slides down the columns of 8 pixel
     slots with the 3x3 window in registers, borders through the buffer descriptor's out-of-range zeros, no LDS) against the round-1
     LDS-strip kernel it replaces and torch: the stored tensor is BIT-IDENTICAL to the old kernel's (same tap order, same epilogue),
-    at the plan's run length and at forced ones (1 row, 3 rows, the whole height); channel sums equal to float32 round-off; nothing
-    is written outside the output's column slice; input and output live in wider buffers."""
+    at the plan's run length and at forced ones (1 row, 3 rows, the whole height), for every activation; channel sums equal to float32
+    round-off; nothing is written outside the output's column slice; input and output live in wider buffers."""
     B, H, W, Cc, s = case
     lib = hip.load()
     dtype = torch.float32
@@ -2018,20 +2035,20 @@ def test_dw3x3_rows_kernel_float32(case):
             out = ops.Act(buf.buf, 4, Cc)
             ns = ops.dwconv3x3_strips(B, Ho, Wo, Cc, s, ops.DT[dtype])
             part = torch.full((B, ns, Cc), float("nan"), device=DEV)
-            ops.dwconv3x3_sum(xin, wa, scale, shift, out, part, B, H, W, s, pt, pl, Ho, Wo, hip.ACT_SILU)
+            ops.dwconv3x3_sum(xin, wa, scale, shift, out, part, B, H, W, s, pt, pl, Ho, Wo, act)
             buf2 = ops.new_act(B * Ho * Wo, Cc, dtype, DEV)
-            ops.dwconv3x3(xin, wa, scale, shift, buf2, B, H, W, s, pt, pl, Ho, Wo, hip.ACT_SILU)          # without sums: same tensor
+            ops.dwconv3x3(xin, wa, scale, shift, buf2, B, H, W, s, pt, pl, Ho, Wo, act)          # without sums: same tensor
             K = ops.dwconv3x3_se_parts(B, Ho, Wo, Cc, s, ops.DT[dtype])
             hpart = torch.full((B, K, RD), float("nan"), device=DEV)
             buf3 = ops.new_act(B * Ho * Wo, Cc, dtype, DEV)
-            ops.dwconv3x3_se(xin, wa, scale, shift, buf3, wr, hpart, B, H, W, s, pt, pl, Ho, Wo, hip.ACT_SILU)   # with the reduce FC's partial dot products
+            ops.dwconv3x3_se(xin, wa, scale, shift, buf3, wr, hpart, B, H, W, s, pt, pl, Ho, Wo, act)   # with the reduce FC's partial dot products
             torch.cuda.synchronize()
             assert torch.equal(buf2.buf, out.torch().contiguous()) and torch.equal(buf3.buf, buf2.buf)
             res.append((buf.buf.clone(), part.sum(1).cpu(), ns, hpart.sum(1).cpu()))
     finally:
         lib.cfp_debug_set(10, 1)
         lib.cfp_debug_set(11, 0)
-    ref = F.silu(F.conv2d(F.pad(x, (pl, (Wo - 1) * s + 3 - W - pl, pt, (Ho - 1) * s + 3 - H - pt)), w, None, s, 0, 1, Cc)
+    ref = ACT_REF[act](F.conv2d(F.pad(x, (pl, (Wo - 1) * s + 3 - W - pl, pt, (Ho - 1) * s + 3 - H - pt)), w, None, s, 0, 1, Cc)
                  * scale.cpu()[None, :, None, None] + shift.cpu()[None, :, None, None])
     o_old, s_old, _, h_old = res[0]
     close(from_nhwc(ops.Act(o_old, 4, Cc).torch(), B, Ho, Wo), ref, dtype, f"dw3x3 old {case}")
