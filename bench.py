@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: depth maps / second at 480x640, bf16, HIP kernels only.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--dump-outputs DIR] [--detail FILE]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 8] [--dump-outputs DIR] [--detail FILE] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -12,10 +12,18 @@ synthetic 480x640 images + 8x8 ToF zones that is already resident in HBM (BASELI
 configs[1]).  Inference does not shard: with N > 1 every rank runs an independent replica on its
 own batch (no data-path collective) and `value` is the sum over ranks = N*batch*K / max-rank-time.
 
+A plain run does only what its headline needs: it sets up (the concurrency candidates are timed there and the fastest is kept,
+`Engine.capture_best`), runs the `--warmup` steps, times the `--steps` steps, writes `--dump-outputs` and prints the line.  `--full`
+then measures and checks everything else, after the timed steps: five repeats of the timed region (`ms_per_step_repeats`), the other
+numerics under the same protocol (`f32x3`, `f16`, `f32`), parity against the CPU oracle on the benched batch and on other weight
+families, latency by the reference's protocol, the training step (`training`; at N > 1 the data-parallel leg on all ranks) and the
+objects below; with `--train` the all-reduce comparison and plan, with `--config5` the `f32x3` object.  The `--no-*` options leave
+single appendices out of a `--full` run.
+
 The run ends with ONE short JSON line (strict JSON, < 4 KB: `ms_per_step` = milliseconds of one of the `--steps` timed steps) that
 carries a summary of each of the objects below; `--detail FILE` writes them whole.  `--dump-outputs DIR` saves what the timed path
 returned in its last timed step (bin edges, pred, a fixed sample of prob) as .npy files, so that two builds can be compared on
-identical inputs.  The objects:
+identical inputs.  The objects (`--full`):
   roofline      the dominant kernel family by GPU time (timed with HIP events around every launch
                 of an instrumented pass on the same stream), algorithmic FLOPs / bytes vs peak
   dw3x3         the encoder's depthwise 3x3 kernels against the HBM roofline (north_star target)
@@ -74,6 +82,9 @@ def parse():
                     help="process-group backend of --train (nccl = RCCL over xGMI; gloo stages the gradient buckets through host memory: "
                          "several ranks can then share one GPU, and with --force-dist a single rank exercises the whole DDP path)")
     ap.add_argument("--force-dist", action="store_true", help="create the process group even for one rank (measures allreduce_ms / overlap_frac at N = 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline (the appendices listed in the module docstring); "
+                         "without it a run sets up, warms up, times the steps, dumps its outputs if asked and prints the line")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the timed path returned in its last timed step to DIR/<name>.npy (float32, float64 scalars as float64; rank 0; "
                          "<= 48 MB: prob and --train's parameters as fixed seeded samples)")
@@ -658,12 +669,13 @@ def allreduce_plan(tr, inp, target, measure_window: bool):
 
 
 def training_step_rate(batch: int, dev, steps: int = 6, dist=None, world: int = 1, warmup: int = 2, fidelity: bool = False, dtype=None,
-                       dump_dir=None):
+                       dump_dir=None, appendices: bool = True):
     """BASELINE.json configs[2..3] shape: 416x544 crops, 6x6 zones of 64 px, `batch` samples per GPU, 16-bit activations with
     float32 master parameters; one step = training forward + SILog + backward (+ gradient all-reduce) + AdamW/OneCycle, replayed as
     HIP graphs.  Headline storage type: fp16 (IEEE half, overflow-guarded optimizer) -- its gradient is the float32 one to a cosine
     of 0.98, bf16's only to 0.88 at the same speed (profiles/r3_train_fidelity.md); the bf16 step BASELINE.json names is timed
-    beside it (`bf16` sub-object) when `fidelity` is set."""
+    beside it (`bf16` sub-object) when `fidelity` is set.  `appendices=False` (a plain `--train` run) stops after the timed steps: no
+    all-reduce comparison runs, no all-reduce plan, no overflow-guard figure."""
     dtype = dtype or torch.float16
     dname = {torch.float16: "fp16", torch.bfloat16: "bf16"}[dtype]
     import numpy as np
@@ -696,7 +708,7 @@ def training_step_rate(batch: int, dev, steps: int = 6, dist=None, world: int = 
         dump_outputs(dump_dir, {"loss": loss.reshape(1), "lr": torch.tensor([float(lr)], dtype=torch.float64),
                                 "beta1": torch.tensor([float(beta1)], dtype=torch.float64), "params": tr.flat.param})
     extra = {}
-    if dist is not None:
+    if dist is not None and appendices:
         # what the gradient averaging costs and how much of it the split step hides: the same steps with the buckets reduced after
         # the whole backward ("sequential") and without any communication ("off")
         def run_mode(mode):
@@ -716,7 +728,7 @@ def training_step_rate(batch: int, dev, steps: int = 6, dist=None, world: int = 
                  "overlap_frac": (min(max((t_seq - dt * 1e3) / ar, 0.0), 1.0) if ar > 1e-3 else None),
                  "allreduce": "flat float32 gradient, 10x group (head/decoder/fusion/ToF encoder) reduced on a communication stream beside the "
                               "RGB-encoder backward (second HIP graph of the split step), 1x group after it; backend " + str(dist.get_backend())}
-    elif fidelity:
+    elif dist is None and fidelity:
         extra = {"fidelity_vs_f32_same_batch": training_fidelity(sd, layers, inp, target, dev)}
     if dist is None and fidelity:
         # roofline of the step's matrix-core families from one instrumented eager step of THIS trainer (after the timed region)
@@ -744,7 +756,7 @@ def training_step_rate(batch: int, dev, steps: int = 6, dist=None, world: int = 
                                                 "frac_of_hbm_peak": (train_pmc_step_bytes() / dt / 1e9 / PEAK_HBM_GBS) if train_pmc_step_bytes() else None},
                                  "protocol": "one instrumented EAGER step after the timed region: HIP events around every C-ABI call on the launch stream; "
                                              "algorithmic FLOPs 2 M N K of the forward / data-gradient / weight-gradient GEMMs, 16-bit operand bytes"}
-    if dtype == torch.float16:
+    if dtype == torch.float16 and appendices:
         try:
             extra["allreduce_plan"] = allreduce_plan(tr, inp, target, measure_window=dist is None)
         except Exception as e:                        # a diagnostic appendix must never take the line down
@@ -896,7 +908,7 @@ def main():
 
     if a.train:
         r = training_step_rate(a.train_batch, dev, steps=a.steps, dist=dist, world=world, warmup=a.warmup,
-                               dump_dir=a.dump_outputs if rank == 0 else None)
+                               dump_dir=a.dump_outputs if rank == 0 else None, appendices=a.full)
         if rank == 0:
             emit({"metric": "training samples/sec @ 416x544, 16-bit activations (whole job: forward + SILog + backward + gradient all-reduce + AdamW)",
                   "value": r["value"], "unit": "samples/s", "per_gpu": r["value"] / world, "n_gpus": world, "steps": a.steps,
@@ -964,6 +976,30 @@ def main():
         # the results of the last timed step, read before anything else replays (an in-flight slot's outputs live until its next turn)
         edges, pred, prob = last[0] if a.inflight > 1 and not a.eager else last
         dump_outputs(a.dump_outputs, {"bin_edges": edges, "pred": pred, "prob": prob})
+    if rank == 0:
+        value, per_gpu = job_value(world, a.batch, a.steps, elapsed)
+        line = {
+            "metric": f"depth maps/sec @ {a.height}x{a.width} {a.dtype} (whole job; per_gpu = value / n_gpus); abs_rel vs CPU oracle",
+            "value": value, "unit": "maps/s", "per_gpu": per_gpu,
+            "n_gpus": world, "ranks_seen": ranks_seen, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
+            "config": {"workload": f"batch={a.batch} {a.height}x{a.width} RGB + {zones}x{zones}-zone ToF, eval forward incl. the prob output "
+                                   f"[B,256,H/2,W/2] written in the storage dtype ({a.dtype}: 2 bytes/element"
+                                   + ("; the f32x3 object of this line is the same workload with the reference's float32 prob, 4 bytes/element)" if a.full else ")")
+                                   if return_prob else f"batch={a.batch} {a.height}x{a.width} RGB + {zones}x{zones}-zone ToF, eval forward, prob output skipped",
+                       "layers": "hist2image combine1 image x2 (CFPNet)", "launch": ("eager" if a.eager else "hipGraph replay") + (f", {a.lanes} concurrent batch lanes" if a.lanes > 1 else "")
+                                 + (f", {a.inflight} batches in flight on concurrently scheduled HIP streams (one graph, buffer set and output set per slot)" if a.inflight > 1 else ""),
+                       "parallelism": "replicas only" if world > 1 else "single GPU",
+                       "lane_choice_ms_per_step": lane_ms},
+        }
+    if not a.full:
+        # a plain run ends here: the headline is measured and every other figure of the line is --full's
+        if rank == 0:
+            emit(line)
+        if dist:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     # the line's own noise estimate: the same K-step region five more times (each synchronised), per-step time of each
     repeats = []
     for _ in range(5):
@@ -1031,23 +1067,8 @@ def main():
         torch.cuda.empty_cache()
 
     if rank == 0:
-        value, per_gpu = job_value(world, a.batch, a.steps, elapsed)
-        line = {
-            "metric": f"depth maps/sec @ {a.height}x{a.width} {a.dtype} (whole job; per_gpu = value / n_gpus); abs_rel vs CPU oracle",
-            "value": value, "unit": "maps/s", "per_gpu": per_gpu,
-            "n_gpus": world, "ranks_seen": ranks_seen, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
-            "config": {"workload": f"batch={a.batch} {a.height}x{a.width} RGB + {zones}x{zones}-zone ToF, eval forward incl. the prob output "
-                                   f"[B,256,H/2,W/2] written in the storage dtype ({a.dtype}: 2 bytes/element; the f32x3 object of this line is the same workload with the "
-                                   f"reference's float32 prob, 4 bytes/element)"
-                                   if return_prob else f"batch={a.batch} {a.height}x{a.width} RGB + {zones}x{zones}-zone ToF, eval forward, prob output skipped",
-                       "layers": "hist2image combine1 image x2 (CFPNet)", "launch": ("eager" if a.eager else "hipGraph replay") + (f", {a.lanes} concurrent batch lanes" if a.lanes > 1 else "")
-                                 + (f", {a.inflight} batches in flight on concurrently scheduled HIP streams (one graph, buffer set and output set per slot)" if a.inflight > 1 else ""),
-                       "parallelism": "replicas only" if world > 1 else "single GPU",
-                       "lane_choice_ms_per_step": lane_ms},
-            "ms_per_step_repeats": {"min": repeats[0], "median": repeats[2], "max": repeats[-1],
-                                    "what": f"5 further repeats of the {a.steps}-step timed region, ms per step of each"},
-        }
+        line["ms_per_step_repeats"] = {"min": repeats[0], "median": repeats[2], "max": repeats[-1],
+                                       "what": f"5 further repeats of the {a.steps}-step timed region, ms per step of each"}
         if not a.no_kernel_times:
             kt = kernel_times(engine, inputs, return_prob)
             dw_copy_ms = kt.pop("_dw3x3_copy", None)

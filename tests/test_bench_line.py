@@ -1,10 +1,11 @@
 """bench.py's output contract on CPU: the one result line (short, strict JSON, the headline keys) and --dump-outputs (float32 .npy
-files under the size limit, the same sample positions on every run)."""
+files under the size limit, the same sample positions on every run); on the GPU: a plain run (no --full) prints the headline alone."""
 import json
 import os
 import sys
 
 import numpy as np
+import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -109,3 +110,38 @@ def test_cli_takes_steps_dump_and_detail(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", "d", "--detail", "f.json"])
     a = bench.parse()
     assert (a.steps, a.warmup, a.dump_outputs, a.detail) == (7, 2, "d", "f.json")
+
+
+def test_full_is_off_by_default(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--full"])
+    assert bench.parse().full is True
+
+
+# what only `--full` measures or checks: none of it may appear in (or cost time in) a plain run
+FULL_ONLY_KEYS = ("ms_per_step_repeats", "f32x3", "f16", "f32", "cpu_baseline", "rel_l1", "gate_met", "roofline", "dw3x3", "latency",
+                  "training", "kernel_ms_total")
+
+
+@pytest.mark.gpu
+def test_a_plain_run_prints_the_headline_alone(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` as a fresh child process: one strict-JSON line with the headline, the last timed step's
+    outputs under --dump-outputs, and none of the --full objects."""
+    import subprocess
+    out = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = _strict(lines[0])
+    assert d["metric"].startswith("depth maps/sec @ 480x640 bf16") and d["unit"] == "maps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "bf16" and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1
+    assert abs(d["value"] - 8 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert d["config"]["launch"].startswith("hipGraph replay") and "non_finite" not in d
+    for k in FULL_ONLY_KEYS:
+        assert k not in d, k
+    assert sorted(os.listdir(out)) == ["bin_edges.npy", "pred.npy", "prob_sample.npy"]
+    pred = np.load(out / "pred.npy")
+    assert pred.shape == (8, 1, 240, 320) and np.isfinite(pred).all()

@@ -242,14 +242,14 @@ def test_one_rank_rccl_process_group_runs_the_overlapped_step(tmp_path):
 def test_the_driver_command_for_two_ranks_runs_end_to_end(tmp_path):
     """The exact command the driver runs at N > 1 (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`), here with
     two ranks on this box's one GPU over gloo (RCCL cannot put two ranks on one device), started as a FRESH child process before
-    anything in it touches the GPU: inference replicas with in-flight slots, teardown, then the data-parallel training leg with its
-    gradient all-reduce -- the whole sequence, parsed from the one JSON line rank 0 prints."""
+    anything in it touches the GPU: inference replicas with in-flight slots, teardown, then (`--full`) the data-parallel training leg
+    with its gradient all-reduce -- the whole sequence, parsed from the one JSON line rank 0 prints."""
     import json, math, os, socket, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-           os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--train-batch", "4"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--train-batch", "4", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -3,9 +3,9 @@
 TAG=${1:-final}
 O=gpurun_out/$TAG
 mkdir -p $O
-python bench.py > $O/bench_b8.json 2> $O/bench_b8.err; echo "bench rc=$?"
-python bench.py --config5 > $O/config5.json 2> $O/config5.err; echo "config5 rc=$?"
-python bench.py --train --steps 30 --warmup 5 > $O/train_line.json 2> $O/train_line.err; echo "train rc=$?"
+python bench.py --full > $O/bench_b8.json 2> $O/bench_b8.err; echo "bench rc=$?"
+python bench.py --config5 --full > $O/config5.json 2> $O/config5.err; echo "config5 rc=$?"
+python bench.py --train --steps 30 --warmup 5 --full > $O/train_line.json 2> $O/train_line.err; echo "train rc=$?"
 bash tools/profile_round.sh $TAG > $O/profile_round.log 2>&1; echo "profile rc=$?"
 bash tools/profile_train.sh $TAG f16 > $O/profile_train.log 2>&1; echo "profile train rc=$?"
 python - "$O" <<'PY'
