@@ -456,6 +456,49 @@ class Tape:
         self.bw.append(bw)
         return y
 
+    # ------------------------------------------------------------------ dynamic zone geometry (rectangle in a device record)
+    def zone_crop(self, x: V, rec: torch.Tensor, B, H, W, zn, p1, p2) -> V:
+        """Token map -> zone tokens of the record's rectangle (crop of the zero-extended map, resize, regroup)."""
+        y = V(train_ops.zone_crop(x.t, rec, B, H, W, zn, p1, p2))
+
+        def bw():
+            if y.g is not None:
+                self.acc(x, train_ops.zone_crop_bwd(y.g, rec, B, H, W, zn, p1, p2))
+        self.bw.append(bw)
+        return y
+
+    def zone_paste(self, x: V, z: V, rec: torch.Tensor, B, H, W, zn, p1, p2) -> V:
+        """x + zone tokens resized back onto the record's clipped rectangle."""
+        y = V(train_ops.zone_paste(x.t, z.t, rec, B, H, W, zn, p1, p2))
+
+        def bw():
+            if y.g is None:
+                return
+            self.acc(z, train_ops.zone_paste_bwd(y.g, rec, B, H, W, zn, p1, p2))
+            self.acc(x, y.g, own=False)
+        self.bw.append(bw)
+        return y
+
+    def zone_outside(self, x: V, rec: torch.Tensor, B, H, W) -> V:
+        """x with the record's rectangle zeroed (its own adjoint)."""
+        y = V(train_ops.zone_rect_rows(x.t, rec, B, H, W, train_ops.ZONE_MASK))
+
+        def bw():
+            if y.g is not None:
+                self.acc(x, train_ops.zone_rect_rows(y.g, rec, B, H, W, train_ops.ZONE_MASK))
+        self.bw.append(bw)
+        return y
+
+    def zone_inside(self, x: V, rec: torch.Tensor, B, H, W, cap) -> V:
+        """[B*cap, C]: per image the rows inside the record's rectangle, then zero rows up to the capacity."""
+        y = V(train_ops.zone_rect_rows(x.t, rec, B, H, W, train_ops.ZONE_INSIDE, cap))
+
+        def bw():
+            if y.g is not None:
+                self.acc(x, train_ops.zone_rect_rows(y.g, rec, B, H, W, train_ops.ZONE_INSIDE_BWD, cap))
+        self.bw.append(bw)
+        return y
+
     def resize(self, x: V, B, Hs, Ws, Hd, Wd) -> V:
         y = V(self.new(B * Hd * Wd, x.C, x.t.dtype))
         ops.resize_bilinear(_act(x.t), Hs, Ws, (0, 0, Hs, Ws), _act(y.t), Hd, Wd, (0, 0, Hd, Wd), B)
@@ -496,14 +539,15 @@ class Tape:
         return y
 
     # ------------------------------------------------------------------ attention / squeeze-excite / head
-    def attention(self, q: V, k: V, v: V, N, L, S, heads, d) -> V:
-        out, state = train_ops.linattn_fwd(q.t, k.t, v.t, N, L, S, heads, d)
+    def attention(self, q: V, k: V, v: V, N, L, S, heads, d, s_dev: Optional[torch.Tensor] = None) -> V:
+        """`s_dev`: the live key count as an int32 device scalar (dynamic zone geometry); S is then the capacity of k / v."""
+        out, state = train_ops.linattn_fwd(q.t, k.t, v.t, N, L, S, heads, d, s_dev=s_dev)
         y = V(out)
 
         def bw():
             if y.g is None:
                 return
-            dq, dk, dv = train_ops.linattn_bwd(q.t, k.t, v.t, y.g, state, N, L, S, heads, d)
+            dq, dk, dv = train_ops.linattn_bwd(q.t, k.t, v.t, y.g, state, N, L, S, heads, d, s_dev=s_dev)
             self.acc(q, dq); self.acc(k, dk); self.acc(v, dv)
         self.bw.append(bw)
         return y

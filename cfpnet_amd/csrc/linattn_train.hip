@@ -91,17 +91,21 @@ template <typename T, int D, int SPLIT, int NT>
 __global__ __launch_bounds__(NT) void linattn_fwd_kernel(const T* __restrict__ q, int q_ld, const T* __restrict__ k, int k_ld,
                                                           const T* __restrict__ v, int v_ld, T* __restrict__ out, int out_ld,
                                                           float* __restrict__ kv_save, int L, int S, int heads, float eps,
-                                                          float* __restrict__ partial, int nchunks, int chunk_len) {
+                                                          float* __restrict__ partial, int nchunks, int chunk_len,
+                                                          const int* __restrict__ s_dev) {
   using O = Outer<D, NT>;
   constexpr int RCH = O::RCH;
   __shared__ float sX[SPLIT == 2 ? 1 : RCH * D], sY[SPLIT == 2 ? 1 : RCH * (D + 1)], sM[O::NO], sRed[O::G > 1 ? O::G * O::NO : 1];
   const int tid = threadIdx.x;
   const int n = blockIdx.x / heads, h = blockIdx.x - n * heads;
-  const float fS = (float)S;
+  // s_dev (dynamic zone geometry): the live key count is read from the device; S stays the row pitch of k / v (the capacity), the
+  // rows from Sn on are left out of the sums and get zero gradients.  s_dev == nullptr: Sn = S, the static form unchanged
+  const int Sn = s_dev ? min(max(*s_dev, 0), S) : S;
+  const float fS = (float)(s_dev ? max(Sn, 1) : S);
   float acc[O::OPT];
 #pragma unroll
   for (int u = 0; u < O::OPT; ++u) acc[u] = 0.f;
-  const int s_begin = SPLIT == 1 ? blockIdx.y * chunk_len : 0, s_end = SPLIT == 1 ? min(S, s_begin + chunk_len) : (SPLIT == 2 ? 0 : S);
+  const int s_begin = SPLIT == 1 ? blockIdx.y * chunk_len : 0, s_end = SPLIT == 1 ? min(Sn, s_begin + chunk_len) : (SPLIT == 2 ? 0 : Sn);
   for (int s0 = s_begin; s0 < s_end; s0 += RCH) {
     const int nr = min(RCH, s_end - s0);
     __syncthreads();
@@ -158,14 +162,18 @@ __global__ __launch_bounds__(NT) void linattn_bwd_kernel(const T* __restrict__ q
                                                           const T* __restrict__ v, int v_ld, const T* __restrict__ dout, int do_ld,
                                                           const float* __restrict__ kv_save, T* __restrict__ dq, int dq_ld,
                                                           T* __restrict__ dk, int dk_ld, T* __restrict__ dv, int dv_ld, int L, int S,
-                                                          int heads, float eps, float* __restrict__ partial, int nchunks, int chunk_len) {
+                                                          int heads, float eps, float* __restrict__ partial, int nchunks, int chunk_len,
+                                                          const int* __restrict__ s_dev) {
   using O = Outer<D, NT>;
   constexpr int RCH = O::RCH;
   __shared__ float sX[SPLIT == 2 ? 1 : RCH * D], sY[SPLIT == 2 ? 1 : RCH * (D + 1)], sM[SPLIT == 2 ? 1 : O::NO], sG[O::NO],
       sRed[O::G > 1 ? O::G * O::NO : 1];
   const int tid = threadIdx.x;
   const int n = blockIdx.x / heads, h = blockIdx.x - n * heads;
-  const float fS = (float)S;
+  // s_dev (dynamic zone geometry): the live key count is read from the device; S stays the row pitch of k / v (the capacity), the
+  // rows from Sn on are left out of the sums and get zero gradients.  s_dev == nullptr: Sn = S, the static form unchanged
+  const int Sn = s_dev ? min(max(*s_dev, 0), S) : S;
+  const float fS = (float)(s_dev ? max(Sn, 1) : S);
   if (SPLIT != 2)
     for (int e = tid; e < O::NO; e += NT) sM[e] = kv_save[(long long)blockIdx.x * O::NO + e];
   float acc[O::OPT];
@@ -241,14 +249,14 @@ __global__ __launch_bounds__(NT) void linattn_bwd_kernel(const T* __restrict__ q
       float d = sG[i * (D + 1) + D];
 #pragma unroll
       for (int j = 0; j < D; ++j) d = fmaf(sG[i * (D + 1) + j], val[j], d);
-      dk[row * dk_ld + h * D + i] = from_f32<T>(d * elu1_grad(kr[i]));
+      dk[row * dk_ld + h * D + i] = from_f32<T>(s < Sn ? d * elu1_grad(kr[i]) : 0.f);
     }
 #pragma unroll
     for (int j = 0; j < D; ++j) {
       float d = 0.f;
 #pragma unroll
       for (int i = 0; i < D; ++i) d = fmaf(K[i], sG[i * (D + 1) + j], d);
-      dv[row * dv_ld + h * D + j] = from_f32<T>(d / fS);
+      dv[row * dv_ld + h * D + j] = from_f32<T>(s < Sn ? d / fS : 0.f);
     }
   }
 }
@@ -264,17 +272,21 @@ template <typename T, int D, int SPLIT, int NT>
 __global__ __launch_bounds__(NT) void linattn_fwd2_kernel(const T* __restrict__ q, int q_ld, const T* __restrict__ k, int k_ld,
                                                            const T* __restrict__ v, int v_ld, T* __restrict__ out, int out_ld,
                                                            float* __restrict__ kv_save, int L, int S, int heads, float eps,
-                                                           float* __restrict__ partial, int nchunks, int chunk_len) {
+                                                           float* __restrict__ partial, int nchunks, int chunk_len,
+                                                          const int* __restrict__ s_dev) {
   using O = Outer<D, NT>;
   constexpr int RCH = NT == 64 ? 32 : 64, P = D + 1;
   __shared__ float sX[RCH * P], sY[SPLIT == 2 ? 1 : RCH * P], sM[O::NO], sZ[RCH], sRed[O::G > 1 ? O::G * O::NO : 1];
   const int tid = threadIdx.x;
   const int n = blockIdx.x / heads, h = blockIdx.x - n * heads;
-  const float fS = (float)S;
+  // s_dev (dynamic zone geometry): the live key count is read from the device; S stays the row pitch of k / v (the capacity), the
+  // rows from Sn on are left out of the sums and get zero gradients.  s_dev == nullptr: Sn = S, the static form unchanged
+  const int Sn = s_dev ? min(max(*s_dev, 0), S) : S;
+  const float fS = (float)(s_dev ? max(Sn, 1) : S);
   float acc[O::OPT];
 #pragma unroll
   for (int u = 0; u < O::OPT; ++u) acc[u] = 0.f;
-  const int s_begin = SPLIT == 1 ? blockIdx.y * chunk_len : 0, s_end = SPLIT == 1 ? min(S, s_begin + chunk_len) : (SPLIT == 2 ? 0 : S);
+  const int s_begin = SPLIT == 1 ? blockIdx.y * chunk_len : 0, s_end = SPLIT == 1 ? min(Sn, s_begin + chunk_len) : (SPLIT == 2 ? 0 : Sn);
   for (int s0 = s_begin; s0 < s_end; s0 += RCH) {
     const int nr = min(RCH, s_end - s0);
     __syncthreads();
@@ -336,14 +348,18 @@ __global__ __launch_bounds__(NT) void linattn_bwd2_kernel(const T* __restrict__ 
                                                            const T* __restrict__ v, int v_ld, const T* __restrict__ dout, int do_ld,
                                                            const float* __restrict__ kv_save, T* __restrict__ dq, int dq_ld,
                                                            T* __restrict__ dk, int dk_ld, T* __restrict__ dv, int dv_ld, int L, int S,
-                                                           int heads, float eps, float* __restrict__ partial, int nchunks, int chunk_len) {
+                                                           int heads, float eps, float* __restrict__ partial, int nchunks, int chunk_len,
+                                                          const int* __restrict__ s_dev) {
   using O = Outer<D, NT>;
   constexpr int RCH = NT == 64 ? 32 : 64, P = D + 1;
   __shared__ float sX[RCH * P], sY[RCH * P], sT[SPLIT == 2 ? 1 : RCH * P], sM[SPLIT == 2 ? 1 : O::NO], sG[O::NO], sZ[RCH], sE[RCH],
       sRed[O::G > 1 ? O::G * O::NO : 1];
   const int tid = threadIdx.x;
   const int n = blockIdx.x / heads, h = blockIdx.x - n * heads;
-  const float fS = (float)S;
+  // s_dev (dynamic zone geometry): the live key count is read from the device; S stays the row pitch of k / v (the capacity), the
+  // rows from Sn on are left out of the sums and get zero gradients.  s_dev == nullptr: Sn = S, the static form unchanged
+  const int Sn = s_dev ? min(max(*s_dev, 0), S) : S;
+  const float fS = (float)(s_dev ? max(Sn, 1) : S);
   if (SPLIT != 2)
     for (int e = tid; e < O::NO; e += NT) sM[e] = kv_save[(long long)blockIdx.x * O::NO + e];
   float acc[O::OPT];
@@ -427,11 +443,11 @@ __global__ __launch_bounds__(NT) void linattn_bwd2_kernel(const T* __restrict__ 
       float a = sG[i * P + D];
 #pragma unroll 8
       for (int j = 0; j < D; ++j) a = fmaf(sG[i * P + j], sY[r * P + j], a);
-      dk[row * dk_ld + h * D + i] = from_f32<T>(a * elu1_grad(to_f32<T>(k[row * k_ld + h * D + i])));
+      dk[row * dk_ld + h * D + i] = from_f32<T>(s0 + r < Sn ? a * elu1_grad(to_f32<T>(k[row * k_ld + h * D + i])) : 0.f);
       float b = 0.f;                                   // here the output index is j = i
 #pragma unroll 8
       for (int ii = 0; ii < D; ++ii) b = fmaf(sX[r * P + ii], sG[ii * P + i], b);
-      dv[row * dv_ld + h * D + i] = from_f32<T>(b / fS);
+      dv[row * dv_ld + h * D + i] = from_f32<T>(s0 + r < Sn ? b / fS : 0.f);
     }
   }
 }
@@ -471,8 +487,9 @@ extern "C" size_t cfp_linattn_ws_bytes(int N, int L, int S, int heads, int d) {
   return need;
 }
 
-extern "C" int cfp_linattn_fwd(const void* q, int q_ld, const void* k, int k_ld, const void* v, int v_ld, void* out, int out_ld, float* state,
-                               int N, int L, int S, int heads, int d, float eps, int dtype, void* ws, size_t ws_bytes, cfp_stream_t stream) {
+static int linattn_fwd_impl(const void* q, int q_ld, const void* k, int k_ld, const void* v, int v_ld, void* out, int out_ld, float* state,
+                            int N, int L, int S, int heads, int d, float eps, int dtype, void* ws, size_t ws_bytes, const int* s_dev,
+                            cfp_stream_t stream) {
   CFP_REQUIRE(q && k && v && out && state, CFP_EINVAL, "cfp_linattn_fwd: null pointer");
   LA_CHECK("cfp_linattn_fwd");
   const int C = heads * d;
@@ -484,11 +501,11 @@ extern "C" int cfp_linattn_fwd(const void* q, int q_ld, const void* k, int k_ld,
   const bool wave = L <= 64 && S <= 64;      // zone / window groups of a few tokens: one wave per (group, head)
 #define FARGS(T) (const T*)q, q_ld, (const T*)k, k_ld, (const T*)v, v_ld, (T*)out, out_ld, state, L, S, heads, eps
 #define L1(T, DD, KERN) do {                                                                                                        \
-    if (!split && wave) hipLaunchKernelGGL((KERN<T, DD, 0, 64>), grid, dim3(64), 0, s, FARGS(T), nullptr, 0, 0);                     \
-    else if (!split) hipLaunchKernelGGL((KERN<T, DD, 0, 256>), grid, dim3(256), 0, s, FARGS(T), nullptr, 0, 0);                      \
+    if (!split && wave) hipLaunchKernelGGL((KERN<T, DD, 0, 64>), grid, dim3(64), 0, s, FARGS(T), nullptr, 0, 0, s_dev);                     \
+    else if (!split) hipLaunchKernelGGL((KERN<T, DD, 0, 256>), grid, dim3(256), 0, s, FARGS(T), nullptr, 0, 0, s_dev);                      \
     else {                                                                                                                          \
-      hipLaunchKernelGGL((KERN<T, DD, 1, 256>), dim3(grid.x, sp.c1), dim3(256), 0, s, FARGS(T), partial, sp.c1, sp.len1);            \
-      hipLaunchKernelGGL((KERN<T, DD, 2, 256>), dim3(grid.x, sp.c2), dim3(256), 0, s, FARGS(T), partial, sp.c1, sp.len2);            \
+      hipLaunchKernelGGL((KERN<T, DD, 1, 256>), dim3(grid.x, sp.c1), dim3(256), 0, s, FARGS(T), partial, sp.c1, sp.len1, s_dev);            \
+      hipLaunchKernelGGL((KERN<T, DD, 2, 256>), dim3(grid.x, sp.c2), dim3(256), 0, s, FARGS(T), partial, sp.c1, sp.len2, s_dev);            \
     }                                                                                                                               \
   } while (0)
 #define LD(T) do { if (d == 4) L1(T, 4, linattn_fwd_kernel); else if (d == 8) L1(T, 8, linattn_fwd2_kernel);                         \
@@ -500,9 +517,9 @@ extern "C" int cfp_linattn_fwd(const void* q, int q_ld, const void* k, int k_ld,
   return cfp_check_launch("cfp_linattn_fwd");
 }
 
-extern "C" int cfp_linattn_bwd(const void* q, int q_ld, const void* k, int k_ld, const void* v, int v_ld, const void* dout, int do_ld,
-                               const float* state, void* dq, int dq_ld, void* dk, int dk_ld, void* dv, int dv_ld, int N, int L, int S,
-                               int heads, int d, float eps, int dtype, void* ws, size_t ws_bytes, cfp_stream_t stream) {
+static int linattn_bwd_impl(const void* q, int q_ld, const void* k, int k_ld, const void* v, int v_ld, const void* dout, int do_ld,
+                            const float* state, void* dq, int dq_ld, void* dk, int dk_ld, void* dv, int dv_ld, int N, int L, int S,
+                            int heads, int d, float eps, int dtype, void* ws, size_t ws_bytes, const int* s_dev, cfp_stream_t stream) {
   CFP_REQUIRE(q && k && v && dout && state && dq && dk && dv, CFP_EINVAL, "cfp_linattn_bwd: null pointer");
   LA_CHECK("cfp_linattn_bwd");
   const int C = heads * d;
@@ -516,11 +533,11 @@ extern "C" int cfp_linattn_bwd(const void* q, int q_ld, const void* k, int k_ld,
 #define BARGS(T) (const T*)q, q_ld, (const T*)k, k_ld, (const T*)v, v_ld, (const T*)dout, do_ld, state, (T*)dq, dq_ld, (T*)dk, dk_ld, (T*)dv, \
                  dv_ld, L, S, heads, eps
 #define L1(T, DD, KERN) do {                                                                                                        \
-    if (!split && wave) hipLaunchKernelGGL((KERN<T, DD, 0, 64>), grid, dim3(64), 0, s, BARGS(T), nullptr, 0, 0);                     \
-    else if (!split) hipLaunchKernelGGL((KERN<T, DD, 0, 256>), grid, dim3(256), 0, s, BARGS(T), nullptr, 0, 0);                      \
+    if (!split && wave) hipLaunchKernelGGL((KERN<T, DD, 0, 64>), grid, dim3(64), 0, s, BARGS(T), nullptr, 0, 0, s_dev);                     \
+    else if (!split) hipLaunchKernelGGL((KERN<T, DD, 0, 256>), grid, dim3(256), 0, s, BARGS(T), nullptr, 0, 0, s_dev);                      \
     else {                                                                                                                          \
-      hipLaunchKernelGGL((KERN<T, DD, 1, 256>), dim3(grid.x, sp.c1), dim3(256), 0, s, BARGS(T), partial, sp.c1, sp.len1);            \
-      hipLaunchKernelGGL((KERN<T, DD, 2, 256>), dim3(grid.x, sp.c2), dim3(256), 0, s, BARGS(T), partial, sp.c1, sp.len2);            \
+      hipLaunchKernelGGL((KERN<T, DD, 1, 256>), dim3(grid.x, sp.c1), dim3(256), 0, s, BARGS(T), partial, sp.c1, sp.len1, s_dev);            \
+      hipLaunchKernelGGL((KERN<T, DD, 2, 256>), dim3(grid.x, sp.c2), dim3(256), 0, s, BARGS(T), partial, sp.c1, sp.len2, s_dev);            \
     }                                                                                                                               \
   } while (0)
 #define LD(T) do { if (d == 4) L1(T, 4, linattn_bwd_kernel); else if (d == 8) L1(T, 8, linattn_bwd2_kernel);                         \
@@ -530,4 +547,31 @@ extern "C" int cfp_linattn_bwd(const void* q, int q_ld, const void* k, int k_ld,
 #undef L1
 #undef BARGS
   return cfp_check_launch("cfp_linattn_bwd");
+}
+
+extern "C" int cfp_linattn_fwd(const void* q, int q_ld, const void* k, int k_ld, const void* v, int v_ld, void* out, int out_ld, float* state,
+                               int N, int L, int S, int heads, int d, float eps, int dtype, void* ws, size_t ws_bytes, cfp_stream_t stream) {
+  return linattn_fwd_impl(q, q_ld, k, k_ld, v, v_ld, out, out_ld, state, N, L, S, heads, d, eps, dtype, ws, ws_bytes, nullptr, stream);
+}
+
+extern "C" int cfp_linattn_bwd(const void* q, int q_ld, const void* k, int k_ld, const void* v, int v_ld, const void* dout, int do_ld,
+                               const float* state, void* dq, int dq_ld, void* dk, int dk_ld, void* dv, int dv_ld, int N, int L, int S,
+                               int heads, int d, float eps, int dtype, void* ws, size_t ws_bytes, cfp_stream_t stream) {
+  return linattn_bwd_impl(q, q_ld, k, k_ld, v, v_ld, dout, do_ld, state, dq, dq_ld, dk, dk_ld, dv, dv_ld, N, L, S, heads, d, eps, dtype, ws,
+                          ws_bytes, nullptr, stream);
+}
+
+extern "C" int cfp_linattn_fwd_dev(const void* q, int q_ld, const void* k, int k_ld, const void* v, int v_ld, void* out, int out_ld, float* state,
+                                   int N, int L, int S, int heads, int d, float eps, int dtype, void* ws, size_t ws_bytes, const int* s_dev,
+                                   cfp_stream_t stream) {
+  CFP_REQUIRE(s_dev, CFP_EINVAL, "cfp_linattn_fwd_dev: null key-count pointer");
+  return linattn_fwd_impl(q, q_ld, k, k_ld, v, v_ld, out, out_ld, state, N, L, S, heads, d, eps, dtype, ws, ws_bytes, s_dev, stream);
+}
+
+extern "C" int cfp_linattn_bwd_dev(const void* q, int q_ld, const void* k, int k_ld, const void* v, int v_ld, const void* dout, int do_ld,
+                                   const float* state, void* dq, int dq_ld, void* dk, int dk_ld, void* dv, int dv_ld, int N, int L, int S,
+                                   int heads, int d, float eps, int dtype, void* ws, size_t ws_bytes, const int* s_dev, cfp_stream_t stream) {
+  CFP_REQUIRE(s_dev, CFP_EINVAL, "cfp_linattn_bwd_dev: null key-count pointer");
+  return linattn_bwd_impl(q, q_ld, k, k_ld, v, v_ld, dout, do_ld, state, dq, dq_ld, dk, dk_ld, dv, dv_ld, N, L, S, heads, d, eps, dtype, ws,
+                          ws_bytes, s_dev, stream);
 }

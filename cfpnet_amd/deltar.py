@@ -81,6 +81,9 @@ class Deltar(_Store):
         self.zone_sample_num: int = int(_flag(a, "zone_sample_num", 16))
         self.change_embedding: bool = bool(_flag(a, "change_embedding", False))
         self.no_skip_inside: bool = bool(_flag(a, "no_skip_inside", False))
+        # --train_zone_random_offset k > 0: the zone rectangle of a training batch moves per step; the training graphs read it from
+        # device records (TrainNet's dynamic-geometry form) and leave it out of their capture key
+        self.zone_offset_bound: int = int(_flag(a, "train_zone_random_offset", 0) or 0)
         self.hist_encoder_10x: bool = bool(_flag(a, "hist_encoder_10x", False))
         for ln in self.layer_names:
             if ln not in ("hist2image", "image", "combine1"):
@@ -261,7 +264,12 @@ class Deltar(_Store):
 _OFFSET_NAMES = ("cross_atten3", "cross_atten2", "cross_atten1")
 
 
-def _patch_signature(pinfo) -> tuple:
+def _patch_signature(pinfo, rectangle: bool = True) -> tuple:
+    """The batch geometry a training capture is specific to; `rectangle=False` (dynamic zone geometry): only the zone count and
+    the per-zone token extents, which no grid offset changes."""
+    if not rectangle:
+        return tuple(tuple(int(v) for v in torch.as_tensor((pinfo[s] if s in pinfo else pinfo[float(s)])["patch_size"]).reshape(-1).tolist())
+                     for s in (4, 8, 16)) + (tuple(int(v) for v in torch.as_tensor(pinfo["zone_num"]).reshape(-1).tolist()),)
     out = []
     for s in (4, 8, 16):
         e = pinfo[s] if s in pinfo else pinfo[float(s)]
@@ -290,7 +298,13 @@ class _CapturedTrainStep:
         sd = {k: v.detach() for k, v in model.state_dict(keep_vars=True).items()}
         self.net = TrainNet(sd, model.layer_names, dev, n_bins=model.num_classes, min_val=model.min_val, max_val=model.max_val,
                             stem_act=model.stem_act, change_embedding=model.change_embedding, share_buffers=True, dtype=_train_numerics(model),
-                            no_skip_inside=model.no_skip_inside, norm=model.norm, base_resolution=model.base_resolution)
+                            no_skip_inside=model.no_skip_inside, norm=model.norm, base_resolution=model.base_resolution,
+                            zone_offset_bound=model.zone_offset_bound)
+        self.zone, zone_dev = None, None
+        if model.zone_offset_bound > 0:              # the batch's zone rectangles, rewritten by every forward
+            self.zone = torch.zeros(3, 9, dtype=torch.int32, device=dev)
+            zone_dev = {n: self.zone[i] for i, (n, _) in enumerate(self.net.fusion_scales())}
+            self._write_zone(input_data)
         self.names = list(names)
         # one real execution before the capture (sets kernel attributes, builds the index maps); its update of the running
         # statistics is undone, capture itself only records
@@ -299,7 +313,7 @@ class _CapturedTrainStep:
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
             t = self.net.new_tape()
-            pred, _, (B, h, w) = self.net.forward(t, self.inp, offs_dev)
+            pred, _, (B, h, w) = self.net.forward(t, self.inp, offs_dev, zone_dev)
             pred.g = torch.zeros(B * h * w, 1, dtype=torch.float32, device=dev)
             t.backward()
             self.net.zero_grad()
@@ -310,7 +324,7 @@ class _CapturedTrainStep:
         self.gf, self.gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.gf):
             self.tape = self.net.new_tape()
-            self.pred, self.edges, (B, h, w) = self.net.forward(self.tape, self.inp, offs_dev)
+            self.pred, self.edges, (B, h, w) = self.net.forward(self.tape, self.inp, offs_dev, zone_dev)
         self.shape = (B, 1, h, w)
         self.gpred = torch.zeros(B * h * w, 1, dtype=torch.float32, device=dev)
         with torch.cuda.graph(self.gb, pool=self.gf.pool()):
@@ -321,9 +335,15 @@ class _CapturedTrainStep:
         self.ptrs = tuple(p.data_ptr() for p in params)
         self.generation = 0              # the captured activations belong to the LAST forward only
 
+    def _write_zone(self, input_data):
+        H, W = (int(v) for v in input_data["rgb"].shape[-2:])
+        self.zone.copy_(torch.from_numpy(self.net.zone_records_host(input_data["additional"]["patch_info"], H, W)), non_blocking=True)
+
     def forward(self, input_data, pos_offsets):
         self.generation += 1
         add = input_data["additional"]
+        if self.zone is not None:
+            self._write_zone(input_data)
         self.inp["rgb"].copy_(input_data["rgb"], non_blocking=True)
         self.inp["additional"]["hist_data"].copy_(add["hist_data"], non_blocking=True)
         self.inp["additional"]["mask"].copy_(add["mask"], non_blocking=True)
@@ -352,7 +372,8 @@ class _TrainStep(torch.autograd.Function):
         ctx.names = names
         if model.train_graphs:
             add = input_data["additional"]
-            key = (tuple(input_data["rgb"].shape), tuple(add["hist_data"].shape), _patch_signature(add["patch_info"]), _train_numerics(model))
+            key = (tuple(input_data["rgb"].shape), tuple(add["hist_data"].shape), _patch_signature(add["patch_info"], model.zone_offset_bound <= 0),
+                   _train_numerics(model))
             cap = model._train_captures.get(key)
             if cap is None or cap.ptrs != tuple(p.data_ptr() for p in params):
                 model._train_captures.clear()                     # one geometry at a time: a capture pins ~25 GB of activations
@@ -366,7 +387,8 @@ class _TrainStep(torch.autograd.Function):
         sd = {k: v.detach() for k, v in model.state_dict(keep_vars=True).items()}
         net = TrainNet(sd, model.layer_names, dev, n_bins=model.num_classes, min_val=model.min_val, max_val=model.max_val,
                        stem_act=model.stem_act, change_embedding=model.change_embedding, share_buffers=True, dtype=_train_numerics(model),
-                       no_skip_inside=model.no_skip_inside, norm=model.norm, base_resolution=model.base_resolution)
+                       no_skip_inside=model.no_skip_inside, norm=model.norm, base_resolution=model.base_resolution,
+                       zone_offset_bound=model.zone_offset_bound)
         tape = net.new_tape()
         pred, edges, (B, h, w) = net.forward(tape, input_data, pos_offsets)
         ctx.net, ctx.tape, ctx.pred = net, tape, pred

@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import math
 from dataclasses import dataclass
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 
@@ -169,3 +169,67 @@ def lsa_padding(H: int, W: int, ws: int) -> Tuple[int, int]:
 def gsa_keys(H: int, W: int, ws: int) -> Tuple[int, int]:
     """Output size of the stride-ws, kernel-ws, no-padding conv (floors; transformer.py:132,146)."""
     return (H - ws) // ws + 1, (W - ws) // ws + 1
+
+
+# ---------------------------------------------------------------------------------------------- zone-geometry record
+# Per-step zone rectangle of one fusion scale as the device record the dynamic-geometry training kernels read
+# (csrc/zone_window.hip).  With per-sample grid offsets (`--train_zone_random_offset`) the batch's rectangle moves and
+# changes size from step to step; the captured training step reads it from device memory instead of freezing it.
+ZONE_REC_FIELDS = ("sy_wo", "sx_wo", "tzh", "tzw", "y0", "y1", "x0", "x1", "n_inside")
+ZONE_REC_LEN = len(ZONE_REC_FIELDS)
+FUSION_SCALES = (16, 8, 4)          # cross_atten3, cross_atten2, cross_atten1
+
+
+def token_hw(H: int, W: int, scale: int) -> Tuple[int, int]:
+    """Token-map size of the decoder level at `scale` (the encoder's 'same'-padded stride-2 stages: ceilings)."""
+    return -(-H // scale), -(-W // scale)
+
+
+def zone_record(patch_info, scale, H: int, W: int) -> np.ndarray:
+    """Collated `patch_info` + one fusion scale + that level's token-map size (H, W) -> int32[ZONE_REC_LEN]:
+    (sy_wo, sx_wo, tzh, tzw, y0, y1, x0, x1, n_inside), where (y0, y1, x0, x1) is the clipped rectangle of
+    fusion.py:104 and n_inside its per-sample token count.  Host integers only: it never waits for the device."""
+    g = FusionGeometry.from_patch_info(patch_info, scale)
+    y0, y1, x0, x1 = g.clipped(H, W)
+    return np.array([g.sy_wo, g.sx_wo, g.tzh, g.tzw, y0, y1, x0, x1, (y1 - y0) * (x1 - x0)], dtype=np.int32)
+
+
+def offsets_patch_info(offsets, zone_layout, image_hw: Tuple[int, int], cache: Optional[Dict] = None) -> Dict:
+    """Collated patch_info of a batch whose sample b has its zone grid shifted by offsets[b] pixels in y and in x
+    (dataloader.py:94-103); `zone_layout` = tof.zone_layout(...) = (zone_num, zone_px, sy0, sx0).  `cache`: offset ->
+    per-sample patch_info, kept by a caller that builds many batches of one layout."""
+    zn, zp = int(zone_layout[0]), int(zone_layout[1])
+    H, W = image_hw
+    cache = {} if cache is None else cache
+    infos = []
+    for o in np.asarray(offsets).reshape(-1).tolist():
+        o = int(o)
+        if o not in cache:
+            cache[o] = patch_info_from_rect_data(centered_zone_rects(H, W, zn, zp, o), (H, W))
+        infos.append(cache[o])
+    return collate_patch_info(infos)
+
+
+def zone_records_from_offsets(offsets, zone_layout, image_hw: Tuple[int, int], scales=FUSION_SCALES) -> np.ndarray:
+    """Per-sample grid offsets -> int32[len(scales), ZONE_REC_LEN], one `zone_record` per fusion scale."""
+    pi = offsets_patch_info(offsets, zone_layout, image_hw)
+    H, W = image_hw
+    return np.stack([zone_record(pi, s, *token_hw(H, W, s)) for s in scales])
+
+
+def capacity(zone_layout, H: int, W: int, bound: int) -> Dict[int, Tuple[int, int, int]]:
+    """scale -> (max tzh, max tzw, max n_inside) over every batch of offsets drawn from [-bound, bound] (H x W image).
+    The batch rectangle is the union of translated copies of one grid, so it depends only on the smallest and the largest
+    offset of the batch: enumerating those pairs covers every draw."""
+    bound = int(bound)
+    cache: Dict[int, Dict] = {}
+    out: Dict[int, Tuple[int, int, int]] = {}
+    for s in FUSION_SCALES:
+        h, w = token_hw(H, W, s)
+        best = (0, 0, 0)
+        for lo in range(-bound, bound + 1):
+            for hi in range(lo, bound + 1):
+                r = zone_record(offsets_patch_info([lo, hi], zone_layout, (H, W), cache), s, h, w)
+                best = (max(best[0], int(r[2])), max(best[1], int(r[3])), max(best[2], int(r[8])))
+        out[s] = best
+    return out

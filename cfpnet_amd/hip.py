@@ -124,6 +124,13 @@ SIGNATURES = {
     "cfp_linattn_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "cfp_linattn_fwd": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _f, _i, _p, _sz, _p]),
     "cfp_linattn_bwd": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p, _sz, _p]),
+    "cfp_linattn_fwd_dev": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _f, _i, _p, _sz, _p, _p]),
+    "cfp_linattn_bwd_dev": (_i, [_p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _i, _f, _i, _p, _sz, _p, _p]),
+    "cfp_zone_crop": (_i, [_p, _i, _p, _p, _i] + [_i] * 7 + [_i, _p]),
+    "cfp_zone_crop_bwd": (_i, [_p, _i, _p, _p, _i] + [_i] * 7 + [_i, _p]),
+    "cfp_zone_paste": (_i, [_p, _i, _p, _i, _p, _p, _i] + [_i] * 7 + [_i, _p]),
+    "cfp_zone_paste_bwd": (_i, [_p, _i, _p, _p, _i] + [_i] * 7 + [_i, _p]),
+    "cfp_zone_rect_rows": (_i, [_p, _i, _p, _p, _i] + [_i] * 6 + [_i, _p]),
     "cfp_dwconv_large_wgrad_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "cfp_dwconv_large_wgrad": (_i, [_p, _i, _p, _i, _p, _i, _i, _i, _i, _i, _f, _i, _p, _sz, _p]),
     "cfp_row_normalize": (_i, [_p, _p, _p, _i, _i, _p]),

@@ -46,11 +46,16 @@ class TrainNet:
 
     def __init__(self, state_dict: Dict[str, torch.Tensor], layer_names: Sequence[str], device="cuda:0", n_bins=256, min_val=1e-3,
                  max_val=10.0, stem_act: bool = False, change_embedding: bool = True, share_buffers: bool = False, dtype=torch.float32,
-                 no_skip_inside: bool = False, norm: str = "linear", base_resolution=spec.BASE_RESOLUTION):
+                 no_skip_inside: bool = False, norm: str = "linear", base_resolution=spec.BASE_RESOLUTION, zone_offset_bound: int = 0,
+                 zone_layout: Optional[Tuple[int, int, int, int]] = None):
         """`dtype`: storage of activations and of the matrix-core weight operands (float32 = parity mode; bfloat16 /
         float16 = mixed precision: float32 master parameters, float32 gradients of the parameters, 16-bit activations
         and activation gradients, float32 accumulation everywhere; "f32x3" = float32 storage with the dense conv / Linear GEMMs of the
-        forward and of both gradients in split precision, autograd_hip.Tape(x3=True))."""
+        forward and of both gradients in split precision, autograd_hip.Tape(x3=True)).
+        `zone_offset_bound` k > 0: dynamic zone geometry -- the batch's zone rectangle of every fusion scale comes from a device
+        record (geometry.zone_record, `forward(zone_records=...)`), so per-sample grid offsets in [-k, k] need no new index maps and
+        one captured step serves every draw; the DAPM inside buffer is sized by geometry.capacity over all such draws.
+        `zone_layout` = tof.zone_layout(...) of the training crop; None: read once from the first batch's rect_data."""
         self.dev = torch.device(device)
         self.x3 = isinstance(dtype, str)
         if self.x3 and dtype.lower() != "f32x3":
@@ -73,6 +78,9 @@ class TrainNet:
             if k.endswith(("running_mean", "running_var")):
                 self.buf[k] = v if share_buffers else v.clone()       # share_buffers: update the caller's running statistics in place
         self._idx_cache: Dict = {}
+        self.zone_offset_bound = int(zone_offset_bound)
+        self.zone_layout = tuple(zone_layout) if zone_layout is not None else None
+        self._zone_cap: Dict = {}                        # (H, W) image -> geometry.capacity
         self.res_fused = os.environ.get("CFP_RES_FUSED_TRAIN", "1") != "0"    # skip connections added inside the BatchNorm-apply / LayerNorm pass
         self.se_fused = os.environ.get("CFP_SE_FUSED_TRAIN", "1") != "0"      # squeeze-excite gate + its backward as three kernels (csrc/se_train.hip)
         self.side_stream: Optional[torch.cuda.Stream] = None      # set by the trainer: parameter gradients beside the dY -> dX chain
@@ -321,6 +329,46 @@ class TrainNet:
             return self._bn(t, self._conv3(t, f, p + ".conv2.weight", None, B, H, W, stats=True), p + ".bn2", hip.ACT_NONE, residual=tok)     # bn2(conv2) + feat
         return t.add(self._bn(t, self._conv3(t, f, p + ".conv2.weight", None, B, H, W, stats=True), p + ".bn2", hip.ACT_NONE), tok)
 
+    def _dapm_dyn(self, t: Tape, p: str, tok: V, B, H, W, rec: torch.Tensor, cap: int, heads) -> V:
+        """_dapm with the rectangle in a device record: the inside rows go to a [B*cap] buffer (rows from n_inside on zero), the
+        attention reads its key count from the record and skips those rows, and the outside-only mask comes from the record."""
+        D = tok.C
+        inside = t.zone_inside(tok, rec, B, H, W, cap)
+        q = t.linear(tok, self._conv_w(p + ".q_proj.weight"))
+        k = t.linear(inside, self._conv_w(p + ".k_proj.weight"))
+        v = t.linear(inside, self._conv_w(p + ".v_proj.weight"))
+        msg = t.attention(q, k, v, B, H * W, cap, heads, D // heads, s_dev=rec[8:9])
+        msg = t.zone_outside(msg, rec, B, H, W)                            # only outside tokens receive a message
+        f = t.concat(tok, msg)
+        f = self._bn(t, self._conv3(t, f, p + ".conv1.weight", None, B, H, W, stats=True), p + ".bn1", hip.ACT_NONE)
+        if self.res_fused:
+            return self._bn(t, self._conv3(t, f, p + ".conv2.weight", None, B, H, W, stats=True), p + ".bn2", hip.ACT_NONE, residual=tok)
+        return t.add(self._bn(t, self._conv3(t, f, p + ".conv2.weight", None, B, H, W, stats=True), p + ".bn2", hip.ACT_NONE), tok)
+
+    # ------------------------------------------------------------------ dynamic zone geometry
+    def fusion_scales(self) -> List[Tuple[str, int]]:
+        """(fusion layer, patch_info scale) in the order of a record array (cross_atten3, 2, 1)."""
+        return [(n, int(self.base_resolution[1] // self.fusion[n][1][1])) for n in ("cross_atten3", "cross_atten2", "cross_atten1")]
+
+    def zone_records_host(self, patch_info, H: int, W: int) -> np.ndarray:
+        """Collated patch_info of an H x W batch -> int32 [3, 9], one geometry.zone_record per fusion scale (host only)."""
+        from .geometry import token_hw, zone_record
+        return np.stack([zone_record(patch_info, s, *token_hw(H, W, s)) for _, s in self.fusion_scales()])
+
+    def zone_capacity(self, input_data: dict) -> Dict[int, Tuple[int, int, int]]:
+        from .geometry import capacity
+        H, W = input_data["rgb"].shape[-2:]
+        key = (int(H), int(W))
+        if key not in self._zone_cap:
+            if self.zone_layout is None:
+                add = input_data["additional"]
+                zn = int(np.asarray(add["patch_info"]["zone_num"]).reshape(-1)[0])
+                r0 = add["rect_data"].reshape(-1, 4)[0].float().cpu()          # once: the zone size of the grid
+                zp = int(round(float(r0[2] - r0[0])))
+                self.zone_layout = (zn, zp, int((H - zp * zn) / 2), int((W - zp * zn) / 2))
+            self._zone_cap[key] = capacity(self.zone_layout, key[0], key[1], self.zone_offset_bound)
+        return self._zone_cap[key]
+
     def _lkpm(self, t: Tape, p: str, tok: V, B, H, W) -> V:
         k = self.sd[p + ".dwconv2.weight"].shape[-1]
         y = t.dwlarge(tok, self._dwl(p + ".dwconv2.weight"), self._vec(p + ".dwconv2.bias"), B, H, W, k)
@@ -330,11 +378,13 @@ class TrainNet:
         y = t.linear(y, self._conv_w(p + ".pwconv2.weight"), self._vec(p + ".pwconv2.bias"))
         return t.add(tok, y)
 
-    def _fusion(self, t: Tape, name: str, x: V, feat1: V, mask: torch.Tensor, patch_info, B, H, W, Z, N, pos_offset) -> V:
+    def _fusion(self, t: Tape, name: str, x: V, feat1: V, mask: torch.Tensor, patch_info, B, H, W, Z, N, pos_offset,
+                zone: Optional[Tuple[torch.Tensor, int]] = None) -> V:
+        """`zone` = (device record, DAPM inside capacity): the dynamic-geometry form, the rectangle is read on the device."""
         p = f"decoder.{name}"
         D, (Hm, Wm), _ = self.fusion[name]
         ws = spec.window_size((Hm, Wm))
-        geo = FusionGeometry.from_patch_info(patch_info, self.base_resolution[1] / Wm)
+        geo = FusionGeometry.from_patch_info(patch_info, self.base_resolution[1] / Wm)     # dynamic form: zn, p1, p2 only (offset-invariant)
         zn, p1, p2 = geo.zone_num, geo.p1, geo.p2
         sy, sx, ey, ex = geo.sy_wo, geo.sx_wo, geo.ey_wo, geo.ex_wo
         tzh, tzw = geo.tzh, geo.tzw
@@ -349,6 +399,17 @@ class TrainNet:
             if lname == "image":
                 tok = self._lsa(t, q + ".lga", tok, B, H, W, ws)
                 tok = self._gsa(t, q + ".gsa", tok, B, H, W, ws)
+            elif lname == "hist2image" and zone is not None:
+                grid = tok if self.change_embedding else emb0
+                z = t.zone_crop(grid, zone[0], B, H, W, zn, p1, p2)
+                z = self._loftr(t, q, z, src, B * zn * zn, p1 * p2, N, X2I_HEADS)
+                z = t.mul_bcast(z, valid_gate, B * zn * zn, p1 * p2)
+                if self.no_skip_inside:
+                    tok = t.zone_outside(tok, zone[0], B, H, W)
+                tok = t.zone_paste(tok, z, zone[0], B, H, W, zn, p1, p2)
+            elif lname == "combine1" and zone is not None:
+                tok = self._dapm_dyn(t, q + ".transformer_path", tok, B, H, W, zone[0], zone[1], 4)
+                tok = self._lkpm(t, q + ".large_kernel_path", tok, B, H, W)
             elif lname == "hist2image":
                 grid = tok if self.change_embedding else emb0
 
@@ -404,13 +465,21 @@ class TrainNet:
         return x
 
     # ------------------------------------------------------------------ the step
-    def forward(self, t: Tape, input_data: dict, pos_offsets: Optional[dict] = None):
-        """Training-mode forward on tape `t`: -> (pred as a tape value [B*h*w, 1], bin edges [B, n_bins+1], (B, h, w))."""
+    def forward(self, t: Tape, input_data: dict, pos_offsets: Optional[dict] = None, zone_records: Optional[dict] = None):
+        """Training-mode forward on tape `t`: -> (pred as a tape value [B*h*w, 1], bin edges [B, n_bins+1], (B, h, w)).
+        `zone_records` (zone_offset_bound > 0): fusion layer -> int32[9] device record; None: built from the batch's patch_info."""
         dev = self.dev
         rgb = input_data["rgb"].to(dev, torch.float32).contiguous()
         add = input_data["additional"]
         B, _, H, W = rgb.shape
         pos_offsets = pos_offsets or {}
+        zones = {}
+        if self.zone_offset_bound > 0:
+            cap = self.zone_capacity(input_data)
+            if zone_records is None:
+                recs = torch.from_numpy(self.zone_records_host(add["patch_info"], H, W)).to(dev)
+                zone_records = {n: recs[i] for i, (n, _) in enumerate(self.fusion_scales())}
+            zones = {n: (zone_records[n], max(1, cap[s][2])) for n, s in self.fusion_scales()}
         x8 = ops.new_act(B * H * W, 8, self.dtype, dev)
         ops.rgb_to_nhwc8(rgb, x8, B, H, W)
         taps = self._encoder(t, V(x8.buf, needs_grad=False), B, H, W)
@@ -426,7 +495,7 @@ class TrainNet:
             return t.conv(x, self._conv_w(name + ".weight"), self._vec(name + ".bias"), B, Hh, Ww, 1, 1, 0, 0, Hh, Ww)
 
         def fuse(name, x, feat, Hh, Ww):
-            return self._fusion(t, name, x, feat, mask, pinfo, B, Hh, Ww, Z, N, pos_offsets.get(name, (0, 0)))
+            return self._fusion(t, name, x, feat, mask, pinfo, B, Hh, Ww, Z, N, pos_offsets.get(name, (0, 0)), zones.get(name))
 
         x = pw(b4, "decoder.conv4", h4, w4)
         x = self._up(t, "decoder.up1", x, h4, w4, b3, B, h3, w3)
@@ -455,7 +524,8 @@ class TrainNet:
         return pred, edges, (B, h0, w0)
 
     def forward_backward(self, input_data: dict, target: torch.Tensor, loss_mask: Optional[torch.Tensor] = None, pos_offsets: Optional[dict] = None,
-                         stop_before_encoder: bool = False, loss_sync=None, stop: Optional[str] = None, defer_param_grads: bool = False):
+                         stop_before_encoder: bool = False, loss_sync=None, stop: Optional[str] = None, defer_param_grads: bool = False,
+                         zone_records: Optional[dict] = None):
         """One forward in training mode + SILog + backward.  Returns (loss as a device scalar, pred [B,1,H/2,W/2], edges);
         gradients are in `self.grads()`, running statistics in `self.buf`.  `stop_before_encoder`: the backward stops where the
         RGB encoder's begins (every non-encoder parameter gradient is final) and `finish_backward()` runs the rest.
@@ -465,7 +535,7 @@ class TrainNet:
         dev = self.dev
         t = self.new_tape(side=self.side_stream)
         t.defer = defer_param_grads
-        pred, edges, (B, h0, w0) = self.forward(t, input_data, pos_offsets)
+        pred, edges, (B, h0, w0) = self.forward(t, input_data, pos_offsets, zone_records)
         # SILog (loss.py:9-19) on the half-resolution prediction against the full-resolution target
         crit = train_ops.SILogLoss()
         pred4 = pred.t.reshape(B, 1, h0, w0)

@@ -672,24 +672,33 @@ def _linattn_ws(N, L, S, heads, d, device, split: bool):
     return (torch.empty(nbytes // 4, dtype=torch.float32, device=device), nbytes) if nbytes else (None, 0)
 
 
-def linattn_fwd(q2d, k2d, v2d, N, L, S, heads, d, eps=1e-6, split: bool = True):
-    """-> (out [N*L, heads*d], state) for linattn_bwd.  `split=False`: one workgroup per (group, head) whatever the shape."""
+def linattn_fwd(q2d, k2d, v2d, N, L, S, heads, d, eps=1e-6, split: bool = True, s_dev: Optional[torch.Tensor] = None):
+    """-> (out [N*L, heads*d], state) for linattn_bwd.  `split=False`: one workgroup per (group, head) whatever the shape.
+    `s_dev`: int32 device scalar, the live key count (cfp_linattn_fwd_dev); S is then the capacity, the row pitch of k / v."""
     from . import hip, ops
     out = torch.empty(N * L, heads * d, dtype=q2d.dtype, device=q2d.device)
     state = torch.empty(hip.load().cfp_linattn_state_bytes(N, heads, d) // 4, dtype=torch.float32, device=q2d.device)
     ws, nbytes = _linattn_ws(N, L, S, heads, d, q2d.device, split)
-    hip.call("cfp_linattn_fwd", q2d.data_ptr(), q2d.stride(0), k2d.data_ptr(), k2d.stride(0), v2d.data_ptr(), v2d.stride(0), out.data_ptr(),
-             out.stride(0), state.data_ptr(), N, L, S, heads, d, eps, ops.DT[q2d.dtype], hip.ptr(ws), nbytes, hip.current_stream())
+    args = (q2d.data_ptr(), q2d.stride(0), k2d.data_ptr(), k2d.stride(0), v2d.data_ptr(), v2d.stride(0), out.data_ptr(),
+            out.stride(0), state.data_ptr(), N, L, S, heads, d, eps, ops.DT[q2d.dtype], hip.ptr(ws), nbytes)
+    if s_dev is None:
+        hip.call("cfp_linattn_fwd", *args, hip.current_stream())
+    else:
+        hip.call("cfp_linattn_fwd_dev", *args, s_dev.data_ptr(), hip.current_stream())
     return out, state
 
 
-def linattn_bwd(q2d, k2d, v2d, dout2d, state, N, L, S, heads, d, eps=1e-6, split: bool = True):
+def linattn_bwd(q2d, k2d, v2d, dout2d, state, N, L, S, heads, d, eps=1e-6, split: bool = True, s_dev: Optional[torch.Tensor] = None):
     from . import hip, ops
     dq, dk, dv = torch.empty_like(q2d), torch.empty_like(k2d), torch.empty_like(v2d)
     ws, nbytes = _linattn_ws(N, L, S, heads, d, q2d.device, split)
-    hip.call("cfp_linattn_bwd", q2d.data_ptr(), q2d.stride(0), k2d.data_ptr(), k2d.stride(0), v2d.data_ptr(), v2d.stride(0), dout2d.data_ptr(),
-             dout2d.stride(0), state.data_ptr(), dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(), dv.stride(0), N, L, S,
-             heads, d, eps, ops.DT[q2d.dtype], hip.ptr(ws), nbytes, hip.current_stream())
+    args = (q2d.data_ptr(), q2d.stride(0), k2d.data_ptr(), k2d.stride(0), v2d.data_ptr(), v2d.stride(0), dout2d.data_ptr(),
+            dout2d.stride(0), state.data_ptr(), dq.data_ptr(), dq.stride(0), dk.data_ptr(), dk.stride(0), dv.data_ptr(), dv.stride(0), N, L, S,
+            heads, d, eps, ops.DT[q2d.dtype], hip.ptr(ws), nbytes)
+    if s_dev is None:
+        hip.call("cfp_linattn_bwd", *args, hip.current_stream())
+    else:
+        hip.call("cfp_linattn_bwd_dev", *args, s_dev.data_ptr(), hip.current_stream())
     return dq, dk, dv
 
 
@@ -704,3 +713,57 @@ def dwconv_large_wgrad(x2d, dy2d, B, H, W, k, dw=None, beta: float = 0.0):
     hip.call("cfp_dwconv_large_wgrad", x2d.data_ptr(), x2d.stride(0), dy2d.data_ptr(), dy2d.stride(0), dw.data_ptr(), B, H, W, C, k, beta,
              ops.DT[x2d.dtype], ws.data_ptr(), nbytes, hip.current_stream())
     return dw
+
+
+# ---- dynamic zone geometry (csrc/zone_window.hip): `rec` is an int32[9] device record (geometry.zone_record) ----
+def _zone_call(name, *args):
+    from . import hip
+    hip.call(name, *args, hip.current_stream())
+
+
+def zone_crop(tok, rec, B, H, W, zn, p1, p2):
+    """[B*H*W, C] token map -> [(B*zn*zn)*(p1*p2), C] zone tokens of the record's rectangle (fusion.py:129-133)."""
+    from . import ops
+    out = torch.empty(B * zn * zn * p1 * p2, tok.shape[1], dtype=tok.dtype, device=tok.device)
+    _zone_call("cfp_zone_crop", tok.data_ptr(), tok.stride(0), rec.data_ptr(), out.data_ptr(), out.stride(0), B, H, W, tok.shape[1], zn, p1, p2,
+               ops.DT[tok.dtype])
+    return out
+
+
+def zone_crop_bwd(dz, rec, B, H, W, zn, p1, p2):
+    from . import ops
+    dtok = torch.empty(B * H * W, dz.shape[1], dtype=dz.dtype, device=dz.device)
+    _zone_call("cfp_zone_crop_bwd", dz.data_ptr(), dz.stride(0), rec.data_ptr(), dtok.data_ptr(), dtok.stride(0), B, H, W, dz.shape[1], zn, p1,
+               p2, ops.DT[dz.dtype])
+    return dtok
+
+
+def zone_paste(tok, z, rec, B, H, W, zn, p1, p2):
+    """tok + the zone tokens resized back onto the record's clipped rectangle (fusion.py:136-157)."""
+    from . import ops
+    out = torch.empty_like(tok)
+    _zone_call("cfp_zone_paste", tok.data_ptr(), tok.stride(0), z.data_ptr(), z.stride(0), rec.data_ptr(), out.data_ptr(), out.stride(0), B, H, W,
+               tok.shape[1], zn, p1, p2, ops.DT[tok.dtype])
+    return out
+
+
+def zone_paste_bwd(dy, rec, B, H, W, zn, p1, p2):
+    from . import ops
+    dz = torch.empty(B * zn * zn * p1 * p2, dy.shape[1], dtype=dy.dtype, device=dy.device)
+    _zone_call("cfp_zone_paste_bwd", dy.data_ptr(), dy.stride(0), rec.data_ptr(), dz.data_ptr(), dz.stride(0), B, H, W, dy.shape[1], zn, p1, p2,
+               ops.DT[dy.dtype])
+    return dz
+
+
+ZONE_MASK, ZONE_INSIDE, ZONE_INSIDE_BWD = 0, 1, 2
+
+
+def zone_rect_rows(x, rec, B, H, W, mode, cap=0):
+    """mode ZONE_MASK: x with the rectangle's rows zeroed; ZONE_INSIDE: [B*cap, C] rows inside the rectangle (rows >= n_inside
+    zero); ZONE_INSIDE_BWD: the adjoint of ZONE_INSIDE, [B*cap, C] -> [B*H*W, C]."""
+    from . import ops
+    rows = B * cap if mode == ZONE_INSIDE else B * H * W
+    out = torch.empty(rows, x.shape[1], dtype=x.dtype, device=x.device)
+    _zone_call("cfp_zone_rect_rows", x.data_ptr(), x.stride(0), rec.data_ptr(), out.data_ptr(), out.stride(0), B, H, W, x.shape[1], cap, mode,
+               ops.DT[x.dtype])
+    return out

@@ -26,7 +26,11 @@ class Trainer:
                  div_factor: float = 25.0, final_div_factor: float = 100.0, hist_encoder_10x: bool = True, clip_grad_norm: Optional[float] = None,
                  device="cuda:0", dist=None, world: int = 1, n_bins: int = 256, min_val: float = 1e-3, max_val: float = 10.0,
                  change_embedding: bool = True, dtype=torch.float32, no_skip_inside: bool = False, norm: str = "linear", kernel_layout: bool = True,
-                 base_resolution=spec.BASE_RESOLUTION, overlap_param_grads: bool = False, comm: str = "overlap", sync_loss: bool = False):
+                 base_resolution=spec.BASE_RESOLUTION, overlap_param_grads: bool = False, comm: str = "overlap", sync_loss: bool = False,
+                 zone_offset_bound: int = 0, zone_layout=None):
+        """`zone_offset_bound` k > 0: per-sample zone-grid offsets in [-k, k] (`--train_zone_random_offset`).  The batch's zone
+        rectangle of each fusion scale is then a device record written by every `step` (TrainNet's dynamic-geometry form), so the
+        captured step follows it; `zone_layout` = tof.zone_layout(...) (None: read from the first batch)."""
         self.dev = torch.device(device)
         # dtype "f32x3": float32 storage (as torch.float32) with the dense conv / Linear GEMMs of the step in split precision (TrainNet)
         self.x3 = isinstance(dtype, str) and dtype.lower() == "f32x3"
@@ -35,7 +39,8 @@ class Trainer:
         self.dtype = torch.float32 if self.x3 else dtype
         self.kernel_layout, self._hist10 = kernel_layout, hist_encoder_10x
         self._net_kw = dict(n_bins=n_bins, min_val=min_val, max_val=max_val, change_embedding=change_embedding, dtype="f32x3" if self.x3 else dtype,
-                            no_skip_inside=no_skip_inside, norm=norm, base_resolution=base_resolution)
+                            no_skip_inside=no_skip_inside, norm=norm, base_resolution=base_resolution, zone_offset_bound=zone_offset_bound,
+                            zone_layout=zone_layout)
         self._layers = list(layer_names)
         self._opt_kw = dict(lr=lr, total_steps=total_steps, div_factor=div_factor, final_div_factor=final_div_factor, weight_decay=weight_decay,
                             clip_grad_norm=clip_grad_norm)
@@ -68,6 +73,11 @@ class Trainer:
                                        clip_grad_norm=clip_grad_norm, overflow_guard=self.dtype == torch.float16)
         self.min_val = min_val
         self._graph = None
+        # dynamic zone geometry: one int32[9] record per fusion scale, rewritten (stream-ordered, no host wait) by every step
+        self.zone_offset_bound = int(zone_offset_bound)
+        self._szone = torch.zeros(3, 9, dtype=torch.int32, device=self.dev) if self.zone_offset_bound > 0 else None
+        self._zone_pi: Dict = {}            # (H, W) -> offset -> per-sample patch_info
+        self._zone_dev = ({n: self._szone[i] for i, (n, _) in enumerate(self.net.fusion_scales())} if self._szone is not None else None)
         if overlap_param_grads:        # measured SLOWER inside a captured step (48.8 vs 45.2 ms): off by default, see DESIGN 4.0
             self.net.side_stream = torch.cuda.Stream(device=self.dev)
 
@@ -77,7 +87,7 @@ class Trainer:
         from .autograd_hip import Tape
         scratch = TrainNet(self.net.sd, self._layers, self.dev, **self._net_kw)              # own copy of the running statistics
         scratch.discovered = {}
-        scratch.forward(scratch.new_tape(), input_data, offs)
+        scratch.forward(scratch.new_tape(), input_data, offs, self._zone_dev)
         found = scratch.discovered
         kflat = train_ops.FlatParams([(n, tuple(t32.shape)) for n, (t32, _, _) in found.items()], train_ops.lr_group_of(self._hist10),
                                      device=self.dev, align=128)                                # 128 elements: every tensor starts on a 256-byte line in the 16-bit shadow too
@@ -202,11 +212,12 @@ class Trainer:
                 self._refresh_weight_flips()
             loss, _, _ = self.net.forward_backward(input_data, target, target > self.min_val, pos_offsets=offs,
                                                    stop_before_encoder=stop_before_encoder, loss_sync=self._loss_sync(), stop=stop,
-                                                   defer_param_grads=defer)
+                                                   defer_param_grads=defer, zone_records=self._zone_dev)
             if self._flip_jobs is None:
                 self._plan_weight_flips()
             return loss                                             # every gradient is already at its flat address
-        loss, pred, _ = self.net.forward_backward(input_data, target, target > self.min_val, pos_offsets=offs, loss_sync=self._loss_sync())
+        loss, pred, _ = self.net.forward_backward(input_data, target, target > self.min_val, pos_offsets=offs, loss_sync=self._loss_sync(),
+                                                  zone_records=self._zone_dev)
         self.flat.grad.zero_()
         for name, g in self.net.grads().items():
             self.flat.view(name, "grad").copy_(g)
@@ -249,6 +260,8 @@ class Trainer:
                                     "mask": add["mask"].to(dev).contiguous().clone(), "rect_data": add.get("rect_data"),
                                     "patch_info": add["patch_info"]}}
         self._starget = target.to(dev, torch.float32).contiguous().clone()
+        if self._szone is not None:
+            self._write_zone(input_data)
         self._soffs = torch.zeros(3, 2, dtype=torch.int32, device=dev)
         self._offs_dev = {name: self._soffs[i] for i, name in enumerate(("cross_atten3", "cross_atten2", "cross_atten1"))}
         side = torch.cuda.Stream(device=dev)
@@ -331,10 +344,29 @@ class Trainer:
         else:
             self._reduce_group(None)
 
-    def step(self, input_data: dict, target: torch.Tensor, pos_offsets: Optional[dict] = None):
-        """-> (loss as a device scalar, lr, beta1).  `target` [B,1,H,W]; the loss mask is target > min_depth (train.py:121)."""
+    def _write_zone(self, input_data: dict, zone_geometry=None, zone_offsets=None) -> None:
+        """Fill the zone records for this batch: from per-sample grid offsets, from a collated patch_info, or from the batch's own
+        patch_info.  Host integers only; the copy is ordered on the stream, the host does not wait."""
+        import numpy as np
+        from . import geometry
+        H, W = (int(v) for v in input_data["rgb"].shape[-2:])
+        if zone_offsets is not None:
+            self.net.zone_capacity(input_data)                               # fixes the zone layout
+            zone_geometry = geometry.offsets_patch_info(np.asarray(zone_offsets.cpu() if torch.is_tensor(zone_offsets) else zone_offsets),
+                                                        self.net.zone_layout, (H, W), self._zone_pi.setdefault((H, W), {}))
+        pi = zone_geometry if zone_geometry is not None else input_data["additional"]["patch_info"]
+        self._szone.copy_(torch.from_numpy(self.net.zone_records_host(pi, H, W)), non_blocking=True)
+
+    def step(self, input_data: dict, target: torch.Tensor, pos_offsets: Optional[dict] = None, zone_geometry=None, zone_offsets=None):
+        """-> (loss as a device scalar, lr, beta1).  `target` [B,1,H,W]; the loss mask is target > min_depth (train.py:121).
+        With zone_offset_bound > 0 the zone rectangles come from `zone_offsets` (per-sample grid offsets, host integers), else
+        from `zone_geometry` (a collated patch_info), else from the batch's patch_info."""
         H, W = input_data["rgb"].shape[-2:]
         offs = pos_offsets if pos_offsets is not None else self.draw_pos_offsets(H, W)
+        if self._szone is not None:
+            self._write_zone(input_data, zone_geometry, zone_offsets)
+        elif zone_geometry is not None or zone_offsets is not None:
+            raise ValueError("zone_geometry / zone_offsets need Trainer(zone_offset_bound > 0)")
         if self._graph is not None:
             add = input_data["additional"]
             self._sin["rgb"].copy_(input_data["rgb"], non_blocking=True)

@@ -674,6 +674,41 @@ int cfp_linattn_fwd(const void* q, int q_ld, const void* k, int k_ld, const void
 int cfp_linattn_bwd(const void* q, int q_ld, const void* k, int k_ld, const void* v, int v_ld, const void* dout, int do_ld,
                     const float* state, void* dq, int dq_ld, void* dk, int dk_ld, void* dv, int dv_ld, int N, int L, int S,
                     int heads, int d, float eps, int dtype, void* ws, size_t ws_bytes, cfp_stream_t stream);
+/* cfp_linattn_fwd / _bwd with the live key count read from DEVICE memory (`s_dev`, the n_inside field of a zone record):
+ * S stays the row pitch of k / v (the capacity of the inside buffer), rows >= *s_dev are left out of KV and Ksum, the
+ * v / S ... * S pair uses *s_dev, and their dk / dv rows are written as zeros (transformer.py:215-234 with the zone rectangle
+ * of a dynamic-geometry training step: the DAPM keys are the inside tokens, whose count changes between replays). */
+int cfp_linattn_fwd_dev(const void* q, int q_ld, const void* k, int k_ld, const void* v, int v_ld, void* out, int out_ld, float* state,
+                        int N, int L, int S, int heads, int d, float eps, int dtype, void* ws, size_t ws_bytes, const int* s_dev,
+                        cfp_stream_t stream);
+int cfp_linattn_bwd_dev(const void* q, int q_ld, const void* k, int k_ld, const void* v, int v_ld, const void* dout, int do_ld,
+                        const float* state, void* dq, int dq_ld, void* dk, int dk_ld, void* dv, int dv_ld, int N, int L, int S,
+                        int heads, int d, float eps, int dtype, void* ws, size_t ws_bytes, const int* s_dev, cfp_stream_t stream);
+
+/* Dynamic zone geometry of the training step (csrc/zone_window.hip).  `rec` is an int32[9] DEVICE record
+ * (geometry.zone_record): sy, sx, tzh, tzw (the batch zone rectangle in token coordinates, fusion.py:70-84), y0, y1, x0, x1
+ * (its part inside the H x W map, fusion.py:104), n_inside; it may change between replays of a captured step.  Token maps
+ * are [B*H*W, C] rows, zone tokens [(B*zn*zn)*(p1*p2), C] (grid Gh x Gw = zn*p1 x zn*p2).  Backwards are gather-form
+ * (deterministic, no atomics).  f32 / bf16 / f16, C a multiple of the 16-byte vector.
+ * cfp_zone_crop      -- fusion.py:129-133: F.pad + crop [sy:sy+tzh, sx:sx+tzw], bilinear (align_corners) resize to Gh x Gw
+ *                       when the extent differs, rearrange into zones; extent == grid: an exact copy.
+ * cfp_zone_crop_bwd  -- its adjoint into a full [B*H*W, C] map (zero outside the rectangle).
+ * cfp_zone_paste     -- fusion.py:136-157: out = tok + resize(zone grid -> tzh x tzw) on the clipped rectangle, tok elsewhere
+ *                       (no_skip_inside: the caller zeroes the rectangle of tok first, cfp_zone_rect_rows mode 0).
+ * cfp_zone_paste_bwd -- dz of the pasted term (dtok is the incoming gradient itself).
+ * cfp_zone_rect_rows -- transformer.py:215-234 / fusion.py:156: mode 0 out = x with the rectangle's rows zeroed [B*H*W];
+ *                       mode 1 out [B*cap] = the rectangle's rows per image, row-major, rows >= n_inside zero; mode 2 the
+ *                       adjoint of mode 1 (x [B*cap] -> out [B*H*W], zero outside the rectangle). */
+int cfp_zone_crop(const void* tok, int tok_ld, const int* rec, void* out, int out_ld, int B, int H, int W, int C, int zn, int p1, int p2,
+                  int dtype, cfp_stream_t stream);
+int cfp_zone_crop_bwd(const void* dz, int dz_ld, const int* rec, void* dtok, int dtok_ld, int B, int H, int W, int C, int zn, int p1, int p2,
+                      int dtype, cfp_stream_t stream);
+int cfp_zone_paste(const void* tok, int tok_ld, const void* z, int z_ld, const int* rec, void* out, int out_ld, int B, int H, int W, int C,
+                   int zn, int p1, int p2, int dtype, cfp_stream_t stream);
+int cfp_zone_paste_bwd(const void* dy, int dy_ld, const int* rec, void* dz, int dz_ld, int B, int H, int W, int C, int zn, int p1, int p2,
+                       int dtype, cfp_stream_t stream);
+int cfp_zone_rect_rows(const void* x, int x_ld, const int* rec, void* out, int out_ld, int B, int H, int W, int C, int cap, int mode,
+                       int dtype, cfp_stream_t stream);
 
 /* Weight gradient of the large-kernel depthwise convolution of LKPM (convnext.py:30, k = 7/15/31, zero padding (k-1)/2):
  * dw[C][k][k] f32 = beta*dw + sum over pixels of dy * x(tap).  The data gradient is cfp_dwconv_large_nhwc with the kernel

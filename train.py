@@ -21,6 +21,13 @@ metrics) runs at the end of every epoch whose step count is a multiple of `--val
 `<epoch>_<rmse>.pt` and `best.pt` next to `--save`, and once more at the end.
 bf16 activations with float32 master parameters by default (`--dtype`); the step is replayed as one HIP graph unless
 `--eager`.  There is no PyTorch autograd or fallback anywhere in the step.
+
+`--train_zone_random_offset K` jitters the ToF zone grid like dataloader.py:94-103: every step draws one offset per sample with
+`random.randint(-K, K)` (seeded by `--seed`), shifts that sample's grid by it in y and in x, simulates its histograms there and
+trains on the batch's union rectangle (the device records of TrainNet's dynamic-geometry form, so the captured step follows the
+draw).  Under DDP each rank draws for its own samples and takes the union over its local batch, as the reference's
+nn.DataParallel replicas do.  Validation keeps the fixed, centred grid of the eval loader on purpose: the reference's
+online_eval mode never offsets it either.
 """
 import os
 import sys
@@ -154,6 +161,13 @@ def drop_zones(sim, s, drop, rng):
 TRAIN_DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16, "f16": torch.float16, "f32x3": "f32x3"}
 
 
+def _torch_patch_info(pi):
+    """Collated numpy patch_info -> the torch-tensor form the reference's collate produces."""
+    out = {s: {k: torch.from_numpy(v) for k, v in pi[s].items()} for s in (4, 8, 16)}
+    out["zone_num"] = torch.from_numpy(pi["zone_num"])
+    return out
+
+
 def main(argv=None):
     from cfpnet_amd import config, geometry, spec, weights
     from cfpnet_amd.tof import TofSimulator, zone_layout
@@ -191,10 +205,7 @@ def main(argv=None):
         local = local_gpu
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
-    # flags of the reference's CLI that this loop cannot honour are refused, not ignored
-    if int(getattr(args, "train_zone_random_offset", 0) or 0) > 0:
-        raise NotImplementedError("--train_zone_random_offset > 0 changes the zone geometry per step; the captured step has it fixed "
-                                  "(the ToF simulator itself supports per-sample offsets: cfpnet_amd.tof.TofSimulator.simulate(offsets=...))")
+    zone_offset = int(getattr(args, "train_zone_random_offset", 0) or 0)
     if float(getattr(args, "noise_prob", 0.0) or 0.0) > 1e-3 and rank == 0:
         print("note: --noise_prob has no effect in the reference either (nyu.py:159-163 adds the noise to a copy); nothing is added here", flush=True)
 
@@ -234,7 +245,8 @@ def main(argv=None):
                  final_div_factor=float(args.final_div_factor), hist_encoder_10x=bool(args.hist_encoder_10x),
                  clip_grad_norm=None if args.disable_clip_grad else 0.1, device=dev, dist=dist, world=world, n_bins=int(args.n_bins),
                  min_val=float(args.min_depth), max_val=float(args.max_depth), change_embedding=bool(args.change_embedding), dtype=dtype, no_skip_inside=bool(getattr(args, "no_skip_inside", False)),
-                 norm=str(args.norm), sync_loss=sync_loss)
+                 norm=str(args.norm), sync_loss=sync_loss, zone_offset_bound=zone_offset,
+                 zone_layout=zone_layout(args, H, W) if zone_offset > 0 else None)
     if opt_state is not None:
         tr.load_optimizer_state_dict(opt_state)
     elif start_step > 0:
@@ -251,9 +263,8 @@ def main(argv=None):
     sim = TofSimulator(args, dev)
     zn, zp, _, _ = zone_layout(args, H, W)
     rects = geometry.centered_zone_rects(H, W, zn, zp)
-    pi = geometry.collate_patch_info([geometry.patch_info_from_rect_data(rects, (H, W))] * per_rank)
-    patch_info = {s: {k: torch.from_numpy(v) for k, v in pi[s].items()} for s in (4, 8, 16)}
-    patch_info["zone_num"] = torch.from_numpy(pi["zone_num"])
+    patch_info = _torch_patch_info(geometry.collate_patch_info([geometry.patch_info_from_rect_data(rects, (H, W))] * per_rank))
+    zone_cache = {}                                   # offset -> per-sample patch_info (--train_zone_random_offset)
     ds = SyntheticTrainSet(n_syn, H, W, seed=1000 + rank)
     rng = np.random.default_rng(4242 + rank)
     resumed_rng = None
@@ -334,14 +345,19 @@ def main(argv=None):
                 if args.do_random_rotate:
                     raw_rgb, raw_dep = augment.rotate(raw_rgb, raw_dep, angles)
                 img, depd = augment.augment(raw_rgb, raw_dep, params, H, W)
-            s = sim.simulate(depd)
+            zoffs, step_info = None, patch_info
+            if zone_offset > 0:                               # dataloader.py:98-100, one draw per sample
+                import random
+                zoffs = [random.randint(-zone_offset, zone_offset) for _ in range(per_rank)]
+                step_info = _torch_patch_info(geometry.offsets_patch_info(zoffs, (zn, zp), (H, W), zone_cache))
+            s = sim.simulate(depd, offsets=torch.tensor(zoffs, dtype=torch.int32).to(dev) if zoffs is not None else None)
             mask, hist_data = s["mask"], s["hist_data"]
             if drop > 1e-3:
                 mask, hist_data = drop_zones(sim, s, drop, rng)
-            inp = {"rgb": img, "additional": {"hist_data": hist_data, "rect_data": s["rect_data"], "mask": mask, "patch_info": patch_info}}
+            inp = {"rgb": img, "additional": {"hist_data": hist_data, "rect_data": s["rect_data"], "mask": mask, "patch_info": step_info}}
             if not eager and tr._graph is None:
                 tr.capture(inp, depd)                         # the whole step as one HIP graph from here on
-            loss, lr, beta1 = tr.step(inp, depd)
+            loss, lr, beta1 = tr.step(inp, depd, zone_offsets=zoffs)
             step += 1
             steps_here += 1
             seen += per_rank * world
