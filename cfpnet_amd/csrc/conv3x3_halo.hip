@@ -22,6 +22,8 @@
 //
 // Same products, float32 accumulation in a different order than the implicit GEMM: results agree to float32 re-association
 // (tests: <= 1 ulp of the storage type against cfp_conv2d_nhwc's other kernels, bit-exact on small integers).
+#include <algorithm>
+
 #include "igemm_core.h"
 
 namespace {
@@ -41,6 +43,14 @@ struct HaloP {
   int tiles_x, tiles_y;
   int n_blocks;    // workgroups per pixel tile: each owns NT * WN * 16 output channels (they re-read the halo from L2)
   FastDiv dcpt;    // piece -> (pixel, chunk)
+  // --- PW = true only (cfp_conv3x3_pw_fused): the 1x1 convolution that consumes this one's output in the same launch ---
+  const void* w2;          // [16 ceil(Cout2 / 16)][Kp] 16-bit, zero padded (ops.pad_pw_w)
+  const float* scale2;     // folded BatchNorm / bias of the 1x1 convolution [Cout2] (null = 1 / 0)
+  const float* shift2;
+  int Cout2, Kp;           // Kp = mid channels rounded up to 32
+  float slope2;            // the 1x1's activation as y > 0 ? y : slope2 * y: 1 = none, 0.01 = LeakyReLU
+  int w2_kb;               // size of w2 in KB (a whole number: 16 rows x 32 K-values are 1 KB)
+  int koff;                // byte offset of the epilogue constants in LDS: behind the stages + halo and behind the `mid` tile of the tail
 };
 
 // UP = true (cfp_upsample_cat_conv3x3, decoder.py:51-58 UpSampleBN): the 16-byte pieces of the halo that belong to channels below p.up_C
@@ -48,7 +58,22 @@ struct HaloP {
 // type as the stored upsampled tensor would have been); the other channels come from the skip tensor.
 // STRIDE = 2 (the stem and the first block of an encoder stage, TF-"same" padding): the halo is (2 TH + 1) x 33 input pixels, an output pixel's
 // tap (dy, dx) is input pixel (2 y + dy, 2 x + dx) of it.
-template <typename H, int NT, int WN, int STAGES, bool UP = false, int STRIDE = 1>
+// PW = true (cfp_conv3x3_pw_fused: timm EdgeResidual conv_exp -> bn1 -> SiLU -> conv_pwl -> bn2 [+ shortcut], and any other 3x3 whose only
+// reader is a 1x1): the workgroup owns ALL mid channels of its pixels (n_blocks == 1) and `mid` never leaves the chip.  After the K loop
+// the accumulators get this convolution's epilogue, are rounded to the storage type exactly as the stored tensor would have been and go to
+// LDS as the workgroup's [pixels][mid] tile (the stage the last K-step read and the halo are free by then).  The second GEMM
+// out^T[Cout2][px] = W2 * mid^T then runs per wave over ALL mid channels of two (WN = 2) or four pixel rows: its B fragments are plain
+// 16-byte reads of that tile, its K blocks run in the channel order into ONE accumulator -- the summation order of the 1x1 launch this
+// replaces (conv_igemm.hip, conv_igemm2.hip), so the result is that launch's bit for bit, not merely to re-association.  (Feeding the packed
+// accumulators to the MFMA directly, as head_fused.hip does, needs no LDS round trip but permutes K inside a block and, with the mid
+// channels split over two waves, adds two partial sums: 0.01-0.07 % of the outputs then differ by an ulp, and this network spreads such
+// flips into a different forward.)  W2 [16 ceil(Cout2 / 16)][Kp], zero padded, comes by LDS-DMA into stage 0 during the last K-step (the
+// stages rotate by nk & 1 so that this step reads stage 1).  p.out / out_ld / res / res_ld describe the 1x1 convolution's output,
+// p.Cout / scale / shift / act the 3x3 one's.  The tail runs once per workgroup, so its cost is latency and code size: the per-channel
+// vectors of both epilogues wait in LDS from the start, and the tail is ONE straight path with the 1x1's activation as a slope -- with
+// a copy of the epilogue per wave half and a runtime activation switch per element an earlier form measured 4-6 us slower per launch for
+// identical arithmetic.
+template <typename H, int NT, int WN, int STAGES, bool UP = false, int STRIDE = 1, bool PW = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp) {
   constexpr int WM = 4 / WN;
   constexpr int TH = 4 * WM;                 // output rows per workgroup (a wave owns 4)
@@ -61,6 +86,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
   constexpr int WSTAGE = NPAD * 128;
   constexpr int LB = UP ? 4 : 6;             // halo pieces per thread and loader pass (UP: four taps each)
   static_assert((STAGES - 2) * NB <= 63, "vmcnt field");
+  static_assert(!PW || (STAGES == 2 && !UP && WN <= 2), "the fused 1x1 takes stage 0 of two weight stages");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* sW = smem;                              // STAGES weight stages
   unsigned char* sX = smem + STAGES * WSTAGE;            // the halo tile
@@ -105,9 +131,27 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
       glds16(ok ? b_ptr[j] + kk : zsrc, s + ((j * 4 + wave) % NBG) * 1024);
     }
   };
+  const int sb = PW ? (nk & 1) : 0;      // PW: the stages rotate so that the LAST K-step reads stage 1 and W2 lands in stage 0
+  auto issue_w2 = [&](int buf) {      // PW: the whole permuted 1x1 weight, 1 KB per instruction, linear
+    const unsigned char* g = reinterpret_cast<const unsigned char*>(hp.w2) + lane * 16;
+    for (int i = wave; i < hp.w2_kb; i += 4) glds16(g + i * 1024, sW + buf * WSTAGE + i * 1024);
+  };
 #pragma unroll
   for (int s = 0; s < STAGES - 1; ++s)
-    if (s < nk) issue(s, s);
+    if (s < nk) issue(s, (s + sb) % STAGES);
+
+  // PW: the per-channel vectors of both epilogues go to LDS -- fetched now, stored behind the halo (their global latency hides behind its
+  // loads), where loading them at their use costs one exposed round trip each per workgroup (head_fused.hip found the same).
+  // [NPAD] scale | [NPAD] shift | [64] scale2 | [64] shift2
+  float* sK = reinterpret_cast<float*>(smem + hp.koff);
+  float k_sc = 1.f, k_sh = 0.f, k_sc2 = 1.f, k_sh2 = 0.f;
+  static_assert(!PW || NPAD <= 256, "one channel per thread");
+  if constexpr (PW) {
+    if (tid < p.Cout && p.scale) k_sc = p.scale[tid];
+    if (tid < p.Cout && p.shift) k_sh = p.shift[tid];
+    if (tid < hp.Cout2 && hp.scale2) k_sc2 = hp.scale2[tid];
+    if (tid < hp.Cout2 && hp.shift2) k_sh2 = hp.shift2[tid];
+  }
 
   // ---- the halo: all pieces of the thread in flight, then the LDS stores (the compiler drains the DMA queue before them; both are
   //      needed before the first MFMA anyway) ---------------------------------------------------------------------------------------
@@ -171,6 +215,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
     }
   }
 
+  if constexpr (PW) {
+    if (tid < NPAD) { sK[tid] = k_sc; sK[NPAD + tid] = k_sh; }
+    if (tid < 64) { sK[2 * NPAD + tid] = k_sc2; sK[2 * NPAD + 64 + tid] = k_sh2; }
+  }
+
   f32x4 acc[4][NT];
 #pragma unroll
   for (int g = 0; g < 4; ++g)
@@ -191,7 +240,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
   const int growb = STRIDE * HC * hp.PP;                                                 // one output row further
 
   for (int ks = 0; ks < nk; ++ks) {
-    const int buf = ks % STAGES;
+    const int buf = (ks + sb) % STAGES;
     const int ahead = min(nk - 1 - ks, STAGES - 2);
     if (ahead >= 2) wait_vmcnt<(STAGES > 3 ? 2 : 1) * NB>();
     else if (ahead == 1) wait_vmcnt<NB>();
@@ -199,7 +248,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's halo stores (first time round) and fragment reads of the previous step
     __builtin_amdgcn_s_barrier();          // stage `buf` (and the halo) landed for every wave; stage buf-1 fully consumed.  Raw: a __syncthreads() would drain the DMA queue
     asm volatile("" ::: "memory");
-    if (ks + STAGES - 1 < nk) issue(ks + STAGES - 1, (ks + STAGES - 1) % STAGES);
+    if (ks + STAGES - 1 < nk) issue(ks + STAGES - 1, (ks + STAGES - 1 + sb) % STAGES);
+    else if constexpr (PW) issue_w2(0);      // the last K-step: stage 0 is free
     const unsigned char* cW = sW + buf * WSTAGE + (wn * NT * 16) * 128;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -226,6 +276,125 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
         if (++c_dx == 3) { c_dx = 0; c_off += (HC - 3) * hp.PP; }
       }
     }
+  }
+
+  if constexpr (PW) {
+    H* __restrict__ out = reinterpret_cast<H*>(p.out) + (long long)b * p.Ho * p.Wo * p.out_ld;
+    const H* __restrict__ res = p.res ? reinterpret_cast<const H*>(p.res) + (long long)b * p.Ho * p.Wo * p.res_ld : nullptr;
+    const int x = x0 + fr;
+    constexpr int NG = WN == 2 ? 2 : 4;          // pixel rows a wave finishes: [g0, g0 + NG)
+    const int g0 = WN == 2 ? 2 * wn : 0;
+    // ---- this convolution's epilogue on the accumulators, rounded as the stored tensor would be: pk[g][j] = channels 16 j + 4 fq + {0..3} ----
+    uint2 pk[4][NT];
+    {
+      f32x4 sc[NT], sh[NT];
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        const int n = (wn * NT + j) * 16 + fq * 4;
+        sc[j] = *reinterpret_cast<const f32x4*>(sK + n);
+        sh[j] = *reinterpret_cast<const f32x4*>(sK + NPAD + n);
+      }
+      with_act(p.act, [&](auto A) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+          for (int j = 0; j < NT; ++j) {
+            float yv[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) yv[r] = act_c16<decltype(A)::value>(acc[g][j][r] * sc[j][r] + sh[j][r]);
+            pk[g][j].x = pack2<H>(yv[0], yv[1]);
+            pk[g][j].y = pack2<H>(yv[2], yv[3]);
+          }
+      });
+    }
+    // ---- the workgroup's `mid` tile [TH * 16 pixels][Kp channels] in LDS, behind W2 (stage 0): stage 1 and the halo are free once every
+    //      wave has left the last K-step.  Pixel pitch Kp * 2 + 16 bytes: the 16 pixels of a fragment read fall on 16 different slots ----
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    const int mpitch = hp.Kp * 2 + 16;
+    unsigned char* sM = smem + hp.w2_kb * 1024;
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+      for (int j = 0; j < NT; ++j) {
+        const int n = (wn * NT + j) * 16 + fq * 4;
+        if (n < hp.Kp) *reinterpret_cast<uint2*>(sM + ((wm * 4 + g) * 16 + fr) * mpitch + n * 2) = pk[g][j];
+      }
+    wait_vmcnt<0>();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();          // W2 landed and `mid` written for every wave
+    asm volatile("" ::: "memory");
+    // the skip values of the pixel rows this wave finishes: in flight across the second GEMM (issued behind the wait for W2, which would
+    // otherwise wait for them too)
+    uint2 rres[NG][4];
+#pragma unroll
+    for (int gi = 0; gi < NG; ++gi)
+#pragma unroll
+      for (int ti = 0; ti < 4; ++ti) {
+        const int y = y0 + wm * 4 + g0 + gi, n = ti * 16 + fq * 4;
+        rres[gi][ti] = (res && y < p.Ho && x < p.Wo && n < hp.Cout2) ? *reinterpret_cast<const uint2*>(res + ((long long)y * p.Wo + x) * p.res_ld + n) : uint2{0u, 0u};
+      }
+    const int t2n = (hp.Cout2 + 15) >> 4;
+    const int rowb = hp.Kp * 2;
+
+    // ---- GEMM2: out^T[Cout2][px] for this wave's NG pixel rows over ALL mid channels, K blocks in order into one accumulator ----
+    f32x4 fin[NG][4];
+#pragma unroll
+    for (int gi = 0; gi < NG; ++gi)
+#pragma unroll
+      for (int ti = 0; ti < 4; ++ti) fin[gi][ti] = f32x4{0.f, 0.f, 0.f, 0.f};
+    const unsigned char* mrow = sM + ((wm * 4 + g0) * 16 + fr) * mpitch + fq * 16;
+    const unsigned char* wrow = smem + fr * rowb + fq * 16;
+#pragma unroll
+    for (int kb = 0; kb < NPAD / 32; ++kb) {
+      if (kb * 32 >= hp.Kp) continue;
+      s16x8 bfr[NG];
+#pragma unroll
+      for (int gi = 0; gi < NG; ++gi) bfr[gi] = *reinterpret_cast<const s16x8*>(mrow + gi * 16 * mpitch + kb * 64);
+#pragma unroll
+      for (int ti = 0; ti < 4; ++ti) {
+        if (ti >= t2n) continue;
+        const s16x8 af = *reinterpret_cast<const s16x8*>(wrow + ti * 16 * rowb + kb * 64);
+#pragma unroll
+        for (int gi = 0; gi < NG; ++gi) fin[gi][ti] = mfma16<H>(af, bfr[gi], fin[gi][ti]);
+      }
+    }
+
+    // ---- the 1x1 convolution's epilogue: scale / shift, none / LeakyReLU as a slope, the skip added to the ROUNDED value as every
+    //      conv kernel here does, 8-byte stores ----
+#pragma unroll
+    for (int ti = 0; ti < 4; ++ti) {
+      const int n = ti * 16 + fq * 4;
+      if (n >= hp.Cout2) continue;
+      const f32x4 sc2 = *reinterpret_cast<const f32x4*>(sK + 2 * NPAD + n);
+      const f32x4 sh2 = *reinterpret_cast<const f32x4*>(sK + 2 * NPAD + 64 + n);
+#pragma unroll
+      for (int gi = 0; gi < NG; ++gi) {
+        const int y = y0 + wm * 4 + g0 + gi;
+        if (!(y < p.Ho && x < p.Wo)) continue;
+        const long long pix = (long long)y * p.Wo + x;
+        float yv[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float v = fin[gi][ti][r] * sc2[r] + sh2[r];
+          yv[r] = v > 0.f ? v : v * hp.slope2;
+        }
+        uint2 o2;
+        o2.x = pack2<H>(yv[0], yv[1]);
+        o2.y = pack2<H>(yv[2], yv[3]);
+        if (res) {
+          const H* ph = reinterpret_cast<const H*>(&o2);
+          const H* rh = reinterpret_cast<const H*>(&rres[gi][ti]);
+          H oh[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) oh[r] = from_f32<H>(to_f32<H>(ph[r]) + to_f32<H>(rh[r]));
+          o2 = *reinterpret_cast<const uint2*>(oh);
+        }
+        *reinterpret_cast<uint2*>(out + pix * p.out_ld + n) = o2;
+      }
+    }
+    return;
   }
 
   // ---- epilogue: folded BatchNorm / bias, activation, optional skip; 8-byte stores from the accumulators -------------------------------
@@ -291,11 +460,20 @@ constexpr HCfg kHCfg[] = {
 };
 constexpr int kNumHCfg = sizeof(kHCfg) / sizeof(kHCfg[0]);
 
-template <typename H, int NT, int WN, bool UP = false, int STRIDE = 1>
-int launch_h(const ConvP& p, hipStream_t s) {
+// LDS bytes of a fused 3x3 -> 1x1 (PW) workgroup before its epilogue constants: the K loop's two weight stages + halo, or W2 (in stage 0) + the
+// `mid` tile of the tail, whichever is larger
+static size_t pw_lds_body(int npad, int th, size_t halo, int mid, int cout2) {
+  const size_t kp = (size_t)cdiv(mid, 32) * 32;
+  const size_t tail = (size_t)cdiv(cout2, 16) * 16 * kp * 2 + (size_t)th * 16 * (kp * 2 + 16);
+  return std::max((size_t)2 * npad * 128 + halo, tail);
+}
+static size_t pw_const_bytes(int npad) { return (size_t)(2 * npad + 128) * 4; }      // scale | shift of the 3x3, scale2 | shift2 [64] of the 1x1
+
+template <typename H, int NT, int WN, bool UP = false, int STRIDE = 1, bool PW = false>
+int launch_h(const ConvP& p, hipStream_t s, const ConvPwP* pw = nullptr) {
   constexpr int TH = 4 * (4 / WN);
   constexpr int NPAD = NT * WN * 16;
-  HaloP hp;
+  HaloP hp{};
   hp.n_blocks = cdiv(p.Cout, NPAD);
   hp.CPT = p.Cin / 8;
   hp.dcpt = make_fastdiv((unsigned)hp.CPT);
@@ -314,22 +492,31 @@ int launch_h(const ConvP& p, hipStream_t s) {
   hp.PP = slots * 16;
   hp.tiles_x = cdiv(p.Wo, 16); hp.tiles_y = cdiv(p.Ho, TH);
   const int hpix = ((TH - 1) * STRIDE + 3) * (15 * STRIDE + 3);
-  const size_t halo = (size_t)hpix * hp.PP;
+  size_t halo = (size_t)hpix * hp.PP;
+  if constexpr (PW) {
+    if (!pw || hp.n_blocks != 1 || pw->Cout2 > 64 || pw->Cout2 % 8 != 0) return -1;
+    hp.w2 = pw->w2; hp.scale2 = pw->scale2; hp.shift2 = pw->shift2; hp.Cout2 = pw->Cout2; hp.slope2 = pw->act2 == CFP_ACT_LRELU ? 0.01f : 1.f;
+    hp.Kp = cdiv(p.Cout, 32) * 32;
+    hp.w2_kb = cdiv(pw->Cout2, 16) * 16 * hp.Kp * 2 / 1024;
+    if ((size_t)hp.w2_kb * 1024 > (size_t)NPAD * 128) return -1;      // W2 must fit one weight stage
+    hp.koff = (int)pw_lds_body(NPAD, TH, halo, p.Cout, pw->Cout2);
+    halo = (size_t)hp.koff - (size_t)2 * NPAD * 128 + pw_const_bytes(NPAD);
+  }
   const long long tiles = (long long)p.B * hp.tiles_x * hp.tiles_y * hp.n_blocks;
   // weight stages: two.  More would hide more of the DMA latency behind MFMAs, but measured (tools/conv_bench.py --halo, us with
   // 2 / 3 / 4 stages: 614400 px x 128 ch 82 / 93 / 96, 153600 x 160 36 / 38 / 52, 614400 x 16 23 / 25 / 25, 38400 x 224 19 / 24 / 32)
   // the LDS they take costs more in resident workgroups than it gains -- the same finding as for the implicit GEMM's tiles
-  int stages = g_halo_stages ? g_halo_stages : 2;
+  int stages = g_halo_stages && !PW ? g_halo_stages : 2;
   const size_t lds = (size_t)stages * NPAD * 128 + halo;
   if (lds > 160 * 1024 || tiles >= (1ll << 31)) return -1;
 #define HL(ST)                                                                                                                      \
   do {                                                                                                                              \
-    auto k = conv3x3_halo_kernel<H, NT, WN, ST, UP, STRIDE>;                                                                        \
+    auto k = conv3x3_halo_kernel<H, NT, WN, ST, UP, STRIDE, PW>;                                                                      \
     static bool attr = false;                                                                                                       \
     if (!attr) { if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -2; attr = true; } \
     hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(256), lds, s, p, hp);                                                         \
   } while (0)
-  if constexpr (UP || STRIDE != 1) { HL(2); } else { if (stages == 4) HL(4); else if (stages == 3) HL(3); else HL(2); }
+  if constexpr (UP || STRIDE != 1 || PW) { HL(2); } else { if (stages == 4) HL(4); else if (stages == 3) HL(3); else HL(2); }
 #undef HL
   return 0;
 }
@@ -401,4 +588,64 @@ int conv3x3_halo_launch(int v, const ConvP& p, hipStream_t s) {
     default: return -3;
   }
 #undef HV
+}
+
+// ---- cfp_conv3x3_pw_fused: 3x3 -> 1x1 in one launch (the kernel above with PW = true) ----
+// The single-block variant for `mid` channels, or -1 when the problem is not taken: W2 must fit one weight stage and the workgroup's LDS
+// the 160 KB of a CU.  (Cin, stride) decide the halo size, nothing else about the problem does.
+int conv3x3_pw_variant(int Cin, int mid, int Cout2, int stride) {
+  if (Cin < 8 || Cin > 128 || Cin % 8 != 0 || mid < 8 || mid % 8 != 0 || Cout2 < 8 || Cout2 > 64 || Cout2 % 8 != 0 || (stride != 1 && stride != 2)) return -1;
+  const int v = mid <= 64 ? 2 : mid <= 160 ? 5 : mid <= 224 ? 6 : -1;
+  if (v < 0 || (stride == 2 && v == 6)) return -1;
+  const int wn = kHCfg[v].wn, npad = kHCfg[v].nt * wn * 16, th = 4 * (4 / wn);
+  if ((size_t)cdiv(Cout2, 16) * 16 * (cdiv(mid, 32) * 32) * 2 > (size_t)npad * 128) return -1;
+  int slots = Cin / 8;
+  if (stride == 1 && slots > 1) { while ((slots & 3) != 2) ++slots; }
+  else if ((slots & 1) == 0) ++slots;
+  const size_t halo = (size_t)((th - 1) * stride + 3) * (15 * stride + 3) * slots * 16;
+  return pw_lds_body(npad, th, halo, mid, Cout2) + pw_const_bytes(npad) <= 160 * 1024 ? v : -1;
+}
+
+int conv3x3_pw_launch(const ConvP& p, const ConvPwP& pw, hipStream_t s) {
+  const int v = conv3x3_pw_variant(p.Cin, p.Cout, pw.Cout2, p.stride);
+  if (v < 0 || !conv3x3_halo_takes(p) || p.up_src != nullptr) return -3;
+#define HP(NT, WN, ST) (p.f16 ? launch_h<f16_t, NT, WN, false, ST, true>(p, s, &pw) : launch_h<bf16_t, NT, WN, false, ST, true>(p, s, &pw))
+  if (p.stride == 2) return v == 2 ? HP(4, 1, 2) : HP(5, 2, 2);
+  return v == 2 ? HP(4, 1, 1) : v == 5 ? HP(5, 2, 1) : HP(7, 2, 1);
+#undef HP
+}
+
+extern "C" int cfp_conv3x3_pw_fused_variant(int Cin, int Cmid, int Cout, int stride, int dtype) {
+  return is16(dtype) ? conv3x3_pw_variant(Cin, Cmid, Cout, stride) : -1;
+}
+
+extern "C" int cfp_conv3x3_pw_fused(const void* in, int in_ld, const void* w1, const float* scale1, const float* shift1, int act1,
+                                    const void* w2_pad, const float* scale2, const float* shift2, int act2, const void* residual, int res_ld,
+                                    void* out, int out_ld, int B, int H, int W, int Cin, int Cmid, int Cout, int stride, int pad_t, int pad_l,
+                                    int Ho, int Wo, int dtype, cfp_stream_t stream) {
+  CFP_REQUIRE(in && w1 && w2_pad && out, CFP_EINVAL, "cfp_conv3x3_pw_fused: null pointer");
+  CFP_REQUIRE(is16(dtype), CFP_EINVAL, "cfp_conv3x3_pw_fused: bf16 / f16 storage only");
+  CFP_REQUIRE(act1 >= CFP_ACT_NONE && act1 <= CFP_ACT_SIGMOID && (act2 == CFP_ACT_NONE || act2 == CFP_ACT_LRELU), CFP_EINVAL,
+              "cfp_conv3x3_pw_fused: bad activation (the 1x1 takes CFP_ACT_NONE or CFP_ACT_LRELU)");
+  CFP_REQUIRE(B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && Cin > 0 && Cmid > 0 && Cout > 0, CFP_ESHAPE, "cfp_conv3x3_pw_fused: non-positive dimension");
+  CFP_REQUIRE(cfp_conv3x3_pw_fused_variant(Cin, Cmid, Cout, stride, dtype) >= 0, CFP_ESHAPE,
+              "cfp_conv3x3_pw_fused: shape not taken (cfp_conv3x3_pw_fused_variant: Cin % 8 == 0 and <= 128, Cmid % 8 == 0 and <= 224 (160 at stride 2), "
+              "Cout % 8 == 0 and <= 64, stride 1 or 2, the 1x1 weights within one weight stage)");
+  CFP_REQUIRE(in_ld % 8 == 0 && in_ld >= Cin && out_ld % 8 == 0 && out_ld >= Cout && (!residual || (res_ld % 8 == 0 && res_ld >= Cout)), CFP_ESHAPE,
+              "cfp_conv3x3_pw_fused: row pitches must be multiples of the 16-byte vector and cover the channels");
+  CFP_REQUIRE(pad_t >= 0 && pad_l >= 0 && pad_t <= 2 && pad_l <= 2 && (Ho - 1) * stride - pad_t + 2 < H + 3 && (Wo - 1) * stride - pad_l + 2 < W + 3, CFP_ESHAPE,
+              "cfp_conv3x3_pw_fused: output size inconsistent with input size");
+  CFP_REQUIRE((long long)B * Ho * Wo < (1ll << 31) && (long long)H * W * in_ld < (1ll << 31), CFP_ESHAPE, "cfp_conv3x3_pw_fused: problem too large");
+  CFP_REQUIRE(aligned16(in) && aligned16(w1) && aligned16(w2_pad) && aligned16(out) && aligned16(residual) && aligned16(scale1) && aligned16(shift1) &&
+                  aligned16(scale2) && aligned16(shift2), CFP_EINVAL, "cfp_conv3x3_pw_fused: pointers must be 16-byte aligned");
+  ConvP p{};
+  p.in = in; p.w = w1; p.out = out; p.res = residual; p.scale = scale1; p.shift = shift1;
+  p.in_ld = in_ld; p.out_ld = out_ld; p.res_ld = res_ld;
+  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.Cout = Cmid;
+  p.KH = 3; p.KW = 3; p.stride = stride; p.pad_t = pad_t; p.pad_l = pad_l;
+  p.M = B * Ho * Wo; p.K = 9 * Cin; p.act = act1; p.f16 = dtype == CFP_F16; p.dil = 1;
+  ConvPwP pw{w2_pad, scale2, shift2, Cout, act2};
+  const int rc = conv3x3_pw_launch(p, pw, reinterpret_cast<hipStream_t>(stream));
+  CFP_REQUIRE(rc == 0, CFP_EHIP, "cfp_conv3x3_pw_fused: kernel launch failed");
+  return cfp_check_launch("cfp_conv3x3_pw_fused");
 }

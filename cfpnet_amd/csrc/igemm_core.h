@@ -66,6 +66,16 @@ void conv3x3_halo_debug_stages(int v);
 void conv3x3_halo_debug_odd_pitch(int v);
 bool conv3x3_halo_takes(const ConvP& p);
 int conv3x3_halo_launch(int v, const ConvP& p, hipStream_t s);
+// ... followed by a 1x1 convolution in the same launch (cfp_conv3x3_pw_fused): `p` describes the 3x3 convolution except that out / out_ld /
+// res / res_ld are the 1x1 convolution's, whose own operands are these
+struct ConvPwP {
+  const void* w2;          // [16 ceil(Cout2 / 16)][32 ceil(mid / 32)], zero padded
+  const float* scale2;
+  const float* shift2;
+  int Cout2, act2;
+};
+int conv3x3_pw_variant(int Cin, int mid, int Cout2, int stride);
+int conv3x3_pw_launch(const ConvP& p, const ConvPwP& pw, hipStream_t s);
 
 // Channel moments of a 16-bit output tile that sits in LDS as [rows][CP] (the values as STORED, i.e. rounded: what a statistics pass
 // over the tensor would read).  TPC = NTHR / BN adjacent lanes share a channel: each takes every TPC-th row with sums shifted by the

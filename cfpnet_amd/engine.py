@@ -171,6 +171,10 @@ class Engine:
         self.lkpm_min_rows = int(os.environ.get("CFP_LKPM_MIN_ROWS", "30000"))      # token rows from which the LKPM tail runs fused
         self.sr_ln_fused = os.environ.get("CFP_SR_LN_FUSED", "1") == "1"      # f16x3: the global attention's LayerNorm inside its patch conv (0: a launch of its own)
         self.head_fused = os.environ.get("CFP_HEAD_FUSED", "1") != "0"
+        # EdgeResidual blocks (encoder stages conv1 / conv2): 3x3 expand + BN + SiLU + 1x1 project + BN (+ skip) as ONE launch with the expanded
+        # tensor kept on the chip (cfp_conv3x3_pw_fused), 16-bit modes.  Characters: "1" = the four stride-1 blocks, "2" = the two stride-2
+        # blocks, "d" = the decoder's up3.b -> conv1 pair; CFP_ER_FUSED=0 runs every pair as two launches.
+        self.er_fused = os.environ.get("CFP_ER_FUSED", "12")
         hl = os.environ.get("CFP_HEAD_HILO", "00")
         self.head_hilo = (hl[0] == "1", hl[1] == "1")
         self.half = dtype in (torch.bfloat16, torch.float16)     # 16-bit storage: the MFMA fast paths
@@ -276,6 +280,9 @@ class Engine:
             elif b.kind == "er":
                 self._conv(sd, q + ".exp", q + ".conv_exp.weight", bn=q + ".bn1", eps=EPS)
                 self._conv(sd, q + ".pwl", q + ".conv_pwl.weight", bn=q + ".bn2", eps=EPS)
+                if self.half and not self.weights2:
+                    # the same rounded project weights zero-padded to the fused kernel's LDS image (cfp_conv3x3_pw_fused)
+                    self.P[q + ".pwl.wp"] = ops.pad_pw_w(self.P[q + ".pwl.w"])
             else:
                 self._conv(sd, q + ".pw", q + ".conv_pw.weight", bn=q + ".bn1", eps=EPS)
                 if self.half and self.mbconv_fused and b.stride == 1 and not self.weights2:
@@ -331,6 +338,8 @@ class Engine:
             self._conv(sd, f"{d}.up{i}.b", q + ".3.weight", q + ".3.bias", bn=q + ".4")
         for n in ("conv3", "conv2", "conv1", "conv0"):
             self._conv(sd, f"{d}.{n}", f"{d}.{n}.weight", f"{d}.{n}.bias")
+        if self.half and not self.weights2:
+            self.P[d + ".conv1.wp"] = ops.pad_pw_w(self.P[d + ".conv1.w"])      # operand of cfp_conv3x3_pw_fused (up3.b -> conv1)
         for name in self.fusion:
             q = f"{d}.{name}"
             self.P[q + ".pe"] = self._dev(sd[q + ".positional_encodings"])
@@ -466,10 +475,17 @@ class Engine:
             if b.kind == "cn":
                 self._cv(q + ".conv", x, out, B, h, w, 3, b.stride, pads, hip.ACT_SILU, res)
             elif b.kind == "er":
-                mid = self._act(plan, f"enc{bi}.mid", B * ho * wo, b.mid)
-                self._cv(q + ".exp", x, mid, B, h, w, 3, b.stride, pads, hip.ACT_SILU)
-                self._dbg(f"enc{bi}.mid", mid)
-                self._cv(q + ".pwl", mid, out, B, ho, wo, 1, 1, None, hip.ACT_NONE, res)
+                if (self.half and (q + ".pwl.wp") in self.P and ("1" if b.stride == 1 else "2") in self.er_fused and taps is None
+                        and not self._dbg_round and ops.conv3x3_pw_fused_variant(x.C, b.mid, b.cout, b.stride, ops.DT[self.dtype]) >= 0):
+                    # one launch, the expanded tensor stays on the chip (no enc{bi}.mid buffer); bit-identical to the pair below
+                    ops.conv3x3_pw_fused(x, self.P[q + ".exp.w"], self.P[q + ".exp.s"], self.P[q + ".exp.t"], hip.ACT_SILU, self.P[q + ".pwl.wp"],
+                                         self.P[q + ".pwl.s"], self.P[q + ".pwl.t"], out, B, h, w, b.stride, pads[0][0], pads[1][0], ho, wo,
+                                         hip.ACT_NONE, res)
+                else:
+                    mid = self._act(plan, f"enc{bi}.mid", B * ho * wo, b.mid)
+                    self._cv(q + ".exp", x, mid, B, h, w, 3, b.stride, pads, hip.ACT_SILU)
+                    self._dbg(f"enc{bi}.mid", mid)
+                    self._cv(q + ".pwl", mid, out, B, ho, wo, 1, 1, None, hip.ACT_NONE, res)
             else:
                 mid2 = self._act(plan, f"enc{bi}.dw", B * ho * wo, b.mid)
                 mbp = ops.mbconv_plan(B, h, w, x.C, b.mid) if (q + ".pw.wimg") in self.P else None
@@ -1107,7 +1123,7 @@ class Engine:
             assert geo.zone_num * geo.zone_num == Z
             self._fusion(plan, name, x, feat, zone_valid, geo, B, hh, ww, out, pos_offsets.get(name, (0, 0)), taps)
 
-        def up(i, src: Act, hs_, ws_, hd, wd):
+        def up(i, src: Act, hs_, ws_, hd, wd, first_only=False):
             M = B * hd * wd
             t1 = self._act(plan, f"up{i}.a", M, c[i])
             # the fused kernel's own preconditions (cfp_upsample_cat_conv3x3 returns CFP_ESHAPE otherwise): 32-bit byte offsets, H, W > 1
@@ -1133,6 +1149,8 @@ class Engine:
                                None, self._ws(M, t1.C, 9 * cat[i].C))
                 else:
                     self._cv(n, cat[i].slice(0, src.C + e[i]), t1, B, hd, wd, 3, act=hip.ACT_LRELU)
+            if first_only:      # the caller runs the stage's second conv together with its reader
+                return t1
             t2 = self._act(plan, f"up{i}.b", M, c[i])
             self._cv(f"decoder.up{i}.b", t1, t2, B, hd, wd, 3, act=hip.ACT_LRELU)
             return t2
@@ -1144,12 +1162,20 @@ class Engine:
         ph, pw = hs[4], wsz[4]
         for i, (fname, feat) in enumerate((("cross_atten3", hfeat[2]), ("cross_atten2", hfeat[1]), ("cross_atten1", hfeat[0])), start=1):
             hh, ww = hs[4 - i], wsz[4 - i]
-            t = up(i, x, ph, pw, hh, ww)
-            if taps is not None:
-                taps[f"up{i}"] = self._nchw(t, B, hh, ww)
             D = c[i + 1]
             dcat = self._act(plan, f"dcat{i}", B * hh * ww, 2 * D)
-            self._cv(f"decoder.conv{4 - i}", t, dcat.slice(0, D), B, hh, ww, 1)
+            n3, n1 = f"decoder.up{i}.b", f"decoder.conv{4 - i}"
+            if (i == 3 and self.half and (n1 + ".wp") in self.P and "d" in self.er_fused and taps is None
+                    and ops.conv3x3_pw_fused_variant(c[i], c[i], D, 1, ops.DT[self.dtype]) >= 0):
+                # up3.b (3x3, LeakyReLU) -> conv1 (1x1 + bias) in one launch: the 1/4-scale `up3.b` tensor is read by nothing else
+                t1 = up(i, x, ph, pw, hh, ww, first_only=True)
+                ops.conv3x3_pw_fused(t1, self.P[n3 + ".w"], self.P[n3 + ".s"], self.P[n3 + ".t"], hip.ACT_LRELU, self.P[n1 + ".wp"],
+                                     self.P[n1 + ".s"], self.P[n1 + ".t"], dcat.slice(0, D), B, hh, ww, 1, 1, 1, hh, ww)
+            else:
+                t = up(i, x, ph, pw, hh, ww)
+                if taps is not None:
+                    taps[f"up{i}"] = self._nchw(t, B, hh, ww)
+                self._cv(n1, t, dcat.slice(0, D), B, hh, ww, 1)
             fuse(fname, dcat.slice(0, D), feat, hh, ww, dcat.slice(D, D))
             if taps is not None:
                 taps[f"conv{4 - i}"] = self._nchw(dcat.slice(0, D), B, hh, ww)

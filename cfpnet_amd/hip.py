@@ -144,6 +144,8 @@ SIGNATURES = {
     "cfp_lkpm_tail": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _f, _i, _i, _i, _p]),
     "cfp_mbconv_plan": (_i, [_i, _i, _i, _i, _i, _p, _p]),
     "cfp_mbconv_expand_dw": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "cfp_conv3x3_pw_fused_variant": (_i, [_i] * 5),
+    "cfp_conv3x3_pw_fused": (_i, [_p, _i, _p, _p, _p, _i, _p, _p, _p, _i, _p, _i, _p, _i] + [_i] * 12 + [_p]),
     "cfp_hist_encoder": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "cfp_depth_head_fused": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "cfp_bin_head_fused": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),

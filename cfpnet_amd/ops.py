@@ -497,15 +497,49 @@ def permute_wout(w: torch.Tensor, dtype, hilo: bool = True, diffuse: bool = Fals
     fragment order, stored as [planes, 256, 128] in `dtype` (plane 0 = round(W), plane 1 = round(W - plane 0) when `hilo`)."""
     w = w.detach().float().reshape(w.shape[0], -1)
     assert w.shape == (256, 128)
-    pos = torch.arange(128)
-    kb, q, e = pos // 32, (pos % 32) // 8, pos % 8
-    src = 32 * kb + 16 * (e // 4) + 4 * q + (e % 4)
+    src = pw_k_order(128)
     wp = w[:, src]
     hi = (round_taps(w.reshape(256, 1, 128), dtype).reshape(256, 128)[:, src] if diffuse else wp).to(dtype)
     planes = [hi]
     if hilo:
         planes.append((wp - hi.float()).to(dtype))
     return torch.stack(planes).contiguous()
+
+
+def pw_k_order(K: int) -> torch.Tensor:
+    """Fragment order of the K axis of a GEMM whose B operand is a pair of packed accumulator tiles (cfp_depth_head_fused): position 32 kb + 8 q + e (q in 0..3, e in 0..7) holds channel 32 kb + 16 (e >> 2) + 4 q + (e & 3).  -> int64
+    [Kp], Kp = K rounded up to 32; -1 where that channel is >= K (padding).  For K % 32 == 0 a permutation of 0..K-1."""
+    pos = torch.arange((K + 31) // 32 * 32)
+    kb, q, e = pos // 32, (pos % 32) // 8, pos % 8
+    src = 32 * kb + 16 * (e // 4) + 4 * q + (e % 4)
+    return torch.where(src < K, src, torch.full_like(src, -1))
+
+
+def pad_pw_w(w: torch.Tensor) -> torch.Tensor:
+    """1x1 weights [Cout, K] (any dtype, already rounded) -> the w2 operand of cfp_conv3x3_pw_fused: [16 ceil(Cout / 16), 32 ceil(K / 32)],
+    zero rows / columns as padding, the K axis in its own order (the kernel copies it to LDS linearly)."""
+    co, K = w.shape
+    out = torch.zeros((co + 15) // 16 * 16, (K + 31) // 32 * 32, dtype=w.dtype, device=w.device)
+    out[:co, :K] = w
+    return out.contiguous()
+
+
+def conv3x3_pw_fused_variant(Cin: int, Cmid: int, Cout: int, stride: int, dt: int) -> int:
+    """The halo variant cfp_conv3x3_pw_fused runs for this shape, -1 = not taken (ask before graph capture)."""
+    return int(hip.load().cfp_conv3x3_pw_fused_variant(Cin, Cmid, Cout, stride, dt))
+
+
+def conv3x3_pw_fused(x: Act, w1: torch.Tensor, s1, t1, act1, w2_pad: torch.Tensor, s2, t2, out: Act, B, H, W, stride, pad_t, pad_l, Ho, Wo,
+                     act2=hip.ACT_NONE, residual: Optional[Act] = None):
+    """conv3x3 (x.C -> mid) + scale / shift + act1 -> conv1x1 (mid -> out.C) + scale / shift + act2 (+ residual) in one launch; `mid`
+    stays on the chip.  w1 [mid, 9 * x.C]; w2_pad = pad_pw_w of the [out.C, mid] weights."""
+    mid = w1.shape[0]
+    assert x.rows >= B * H * W and out.rows >= B * Ho * Wo and x.dt == out.dt
+    assert w1.dtype == x.buf.dtype and tuple(w1.shape) == (mid, 9 * x.C) and w1.is_contiguous()
+    assert w2_pad.dtype == x.buf.dtype and tuple(w2_pad.shape) == ((out.C + 15) // 16 * 16, (mid + 31) // 32 * 32) and w2_pad.is_contiguous()
+    hip.call("cfp_conv3x3_pw_fused", x.ptr, x.ld, w1.data_ptr(), hip.ptr(s1), hip.ptr(t1), act1, w2_pad.data_ptr(), hip.ptr(s2), hip.ptr(t2), act2,
+             residual.ptr if residual else 0, residual.ld if residual else 0, out.ptr, out.ld, B, H, W, x.C, mid, out.C, stride, pad_t, pad_l,
+             Ho, Wo, x.dt, _s())
 
 
 def depth_head_fused(x: Act, w3, scale3, shift3, wout_perm: torch.Tensor, bias_out, centers, prob, pred, B, H, W, ram_out: Optional[Act] = None,

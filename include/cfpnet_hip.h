@@ -212,6 +212,27 @@ int cfp_mbconv_expand_dw(const void* x, int x_ld, const void* wpw, const float* 
                          const float* s2, const float* t2, void* out, int out_ld, float* partial, int B, int H, int W, int Cin,
                          int mid, int dtype, cfp_stream_t stream);
 
+/* A 3x3 convolution and the 1x1 convolution that is its only reader in one launch (csrc/conv3x3_halo.hip, PW = true):
+ *   out = act2(scale2 * conv1x1(round16(act1(scale1 * conv3x3(in) + shift1))) + shift2) (+ residual, added to the rounded value).
+ * Replaces timm EdgeResidual's conv_exp + bn1 + SiLU + conv_pwl + bn2 (+ shortcut) (encoder.py:57-69, the blocks of stages conv1 / conv2;
+ * oracle/cfpnet_oracle.py:85-89) as two cfp_conv2d_nhwc launches; the expanded tensor [B,Ho,Wo,Cmid] never reaches HBM, and the value
+ * fed to the 1x1 is bit for bit the one the first launch would have stored, and the 1x1 sums its K blocks in the order of
+ * cfp_conv2d_nhwc's kernels into one accumulator: the result is the pair's bit for bit.
+ *   in [B,H,W,in_ld] (Cin channels); w1 [Cmid][3*3*Cin] as cfp_conv2d_nhwc lays weights out; w2_pad [16 ceil(Cout / 16)][Kp], Kp = Cmid
+ *   rounded up to 32: the [Cout][Cmid] weights with zero rows / columns as padding; scale / shift [Cmid] and [Cout] f32 (may be NULL = 1 / 0);
+ *   residual / out [B,Ho,Wo,res_ld / out_ld] (Cout channels; out may be a channel slice of a wider buffer); stride 1 or 2 with
+ *   explicit top / left padding as cfp_conv2d_nhwc.  act1 any CFP_ACT_*, act2 CFP_ACT_NONE or CFP_ACT_LRELU (CFP_EINVAL otherwise).
+ *   bf16 / f16 only.
+ * cfp_conv3x3_pw_fused_variant -> the whole-depth-halo variant (cfp_debug_set(0, 300 + v)) the launch runs for this shape, or -1 when
+ * it does not take it: every Cmid channel must live in one workgroup (Cmid <= 224, <= 160 at stride 2; Cout <= 64; channel counts
+ * multiples of 8; Cin <= 128; the 1x1 weights within one weight stage; LDS within a CU).  The launch returns CFP_ESHAPE for such a
+ * shape: the caller keeps the two launches, nothing falls back silently. */
+int cfp_conv3x3_pw_fused_variant(int Cin, int Cmid, int Cout, int stride, int dtype);
+int cfp_conv3x3_pw_fused(const void* in, int in_ld, const void* w1, const float* scale1, const float* shift1, int act1,
+                         const void* w2_pad, const float* scale2, const float* shift2, int act2, const void* residual, int res_ld,
+                         void* out, int out_ld, int B, int H, int W, int Cin, int Cmid, int Cout, int stride, int pad_t, int pad_l,
+                         int Ho, int Wo, int dtype, cfp_stream_t stream);
+
 /* cfp_se_hidden + cfp_se_fold in one launch (mean -> FC -> SiLU -> FC -> sigmoid -> per-image project weights),
  * structured for latency: this is what the engine calls between the depthwise conv and the project conv of every
  * inverted-residual block.  Same arguments as the two calls it replaces; C <= 2048, R <= 64. */
