@@ -21,6 +21,7 @@
 //     padded to whole K-steps -- the B fragments are plain 16-byte LDS reads.
 //   * the epilogue stores float32 straight from the accumulators (a lane owns 4 consecutive output channels of one pixel: 16 bytes).
 #include "igemm_core.h"
+#include "head_stats.h"
 
 namespace {
 
@@ -756,9 +757,14 @@ constexpr int HB_N = 256, HB_PP = 64 + 4;      // HB_PP: floats per bin row of t
 
 // HB_M = 64: 80 KB of LDS, two workgroups per CU -- one's softmax / store phase overlaps the other's K loop (measured against HB_M = 128,
 // one workgroup per CU with a third fewer weight re-reads: tools/head_bench.py --x3)
-template <int HB_M>
+// STATS: the uncertainty planes (head_stats.h).  t = sum e d joins the exponential loop, the centred variance is a second walk over the
+// probabilities in the accumulators and the (L1-resident) centres; after the two shuffle steps a pixel's sums sit in all four lane
+// quarters, so fq = 1, 2, 3 store the planes beside fq = 0's pred, each as coalesced as pred.  A compile-time switch: STATS = false
+// is the kernel as it was.
+template <int HB_M, bool STATS>
 __global__ __launch_bounds__(256) void bin_head_x3_kernel(ConvP p, const float* __restrict__ bias, const float* __restrict__ centers,
-                                                          float* __restrict__ prob, float* __restrict__ pred, int HW) {
+                                                          float* __restrict__ prob, float* __restrict__ pred, float* __restrict__ stats,
+                                                          int HW) {
   constexpr int TM = HB_M / 64, TN = 16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -782,14 +788,25 @@ __global__ __launch_bounds__(256) void bin_head_x3_kernel(ConvP p, const float* 
     }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float s = 0.f;
+    float s = 0.f, t = 0.f;
 #pragma unroll
     for (int j = 0; j < TN; ++j)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { acc[i][j][r] = __expf(acc[i][j][r] - mx); s += acc[i][j][r]; }
+      for (int r = 0; r < 4; ++r) {
+        const float d = acc[i][j][r] - mx;
+        acc[i][j][r] = __expf(d);
+        s += acc[i][j][r];
+        if constexpr (STATS) t = fmaf(acc[i][j][r], d, t);
+      }
     s += __shfl_xor(s, 16, 64);
     s += __shfl_xor(s, 32, 64);
+    if constexpr (STATS) {
+      t += __shfl_xor(t, 16, 64);
+      t += __shfl_xor(t, 32, 64);
+    }
     const float inv = 1.f / s;
+    float ent = 0.f;
+    if constexpr (STATS) ent = unc_entropy(s, t, inv);
     float dot = 0.f;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -800,6 +817,18 @@ __global__ __launch_bounds__(256) void bin_head_x3_kernel(ConvP p, const float* 
     dot += __shfl_xor(dot, 16, 64);
     dot += __shfl_xor(dot, 32, 64);
     if (fq == 0 && m < p.M) pred[m] = dot;
+    if constexpr (STATS) {
+      float var = 0.f;
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        const f32x4 cen = *reinterpret_cast<const f32x4*>(centers + (long long)bidx * HB_N + j * 16 + fq * 4);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { const float dc = cen[r] - dot; var = fmaf(acc[i][j][r] * dc, dc, var); }
+      }
+      var += __shfl_xor(var, 16, 64);
+      var += __shfl_xor(var, 32, 64);
+      if (fq != 0 && m < p.M) stats[((long long)bidx * 3 + (fq - 1)) * HW + (m - bidx * HW)] = unc_plane(fq - 1, var, ent, inv);
+    }
     if (prob == nullptr) continue;
     const int pl = wave * 16 + fr;
 #pragma unroll
@@ -960,8 +989,8 @@ extern "C" int cfp_pack_w_x3(const float* w, void* out, long long rows, int K, c
 
 int g_bin_head_x3_rows = 64;      // cfp_debug_set key 25: pixel rows per workgroup of the fused f16x3 bin head (64 / 128)
 // cfp_bin_head_fused for dtype CFP_F32X3 (head.hip dispatches here): x float32 [B*HW, x_ld], w = cfp_pack_w_x3 of conv_out's [256, Cin].
-int bin_head_x3_launch(const void* x, int x_ld, const void* w, const float* bias, const float* centers, float* prob, float* pred, int B, int HW,
-                       int Cin, hipStream_t s) {
+int bin_head_x3_launch(const void* x, int x_ld, const void* w, const float* bias, const float* centers, float* prob, float* pred, float* stats, int B,
+                       int HW, int Cin, hipStream_t s) {
   ConvP p;
   p.in = x; p.w = w; p.out = nullptr; p.res = nullptr; p.scale = nullptr; p.shift = nullptr;
   p.in_ld = x_ld; p.out_ld = 0; p.res_ld = 0;
@@ -972,13 +1001,19 @@ int bin_head_x3_launch(const void* x, int x_ld, const void* w, const float* bias
   static_assert((size_t)HB_N * HB_PP * 4 <= (size_t)2 * (64 + HB_N) * 128, "probability tile must fit in the operand LDS");
   static bool attr = false;
   if (!attr) {
-    if (hipFuncSetAttribute((const void*)bin_head_x3_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -2;
-    if (hipFuncSetAttribute((const void*)bin_head_x3_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -2;
+    if (hipFuncSetAttribute((const void*)bin_head_x3_kernel<64, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -2;
+    if (hipFuncSetAttribute((const void*)bin_head_x3_kernel<128, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -2;
+    if (hipFuncSetAttribute((const void*)bin_head_x3_kernel<64, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -2;
+    if (hipFuncSetAttribute((const void*)bin_head_x3_kernel<128, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -2;
     attr = true;
   }
-  if (g_bin_head_x3_rows == 128)
-    hipLaunchKernelGGL(bin_head_x3_kernel<128>, dim3(cdiv(p.M, 128)), dim3(256), (size_t)2 * (128 + HB_N) * 128, s, p, bias, centers, prob, pred, HW);
-  else
-    hipLaunchKernelGGL(bin_head_x3_kernel<64>, dim3(cdiv(p.M, 64)), dim3(256), (size_t)2 * (64 + HB_N) * 128, s, p, bias, centers, prob, pred, HW);
+  const size_t lds128 = (size_t)2 * (128 + HB_N) * 128, lds64 = (size_t)2 * (64 + HB_N) * 128;
+  if (g_bin_head_x3_rows == 128) {
+    if (stats) hipLaunchKernelGGL((bin_head_x3_kernel<128, true>), dim3(cdiv(p.M, 128)), dim3(256), lds128, s, p, bias, centers, prob, pred, stats, HW);
+    else hipLaunchKernelGGL((bin_head_x3_kernel<128, false>), dim3(cdiv(p.M, 128)), dim3(256), lds128, s, p, bias, centers, prob, pred, (float*)nullptr, HW);
+  } else {
+    if (stats) hipLaunchKernelGGL((bin_head_x3_kernel<64, true>), dim3(cdiv(p.M, 64)), dim3(256), lds64, s, p, bias, centers, prob, pred, stats, HW);
+    else hipLaunchKernelGGL((bin_head_x3_kernel<64, false>), dim3(cdiv(p.M, 64)), dim3(256), lds64, s, p, bias, centers, prob, pred, (float*)nullptr, HW);
+  }
   return 0;
 }

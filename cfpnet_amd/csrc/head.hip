@@ -1,6 +1,7 @@
 // Adaptive-bins head: bin-width regressor (tiny, one workgroup per image) and the per-pixel
 // 256-way softmax + expectation over bin centres.
 #include "igemm_core.h"
+#include "head_stats.h"
 
 namespace {
 
@@ -102,9 +103,13 @@ __global__ __launch_bounds__(1024) void bin_regressor_kernel(const float* __rest
 
 // One wave per pixel: lane holds NB/64 consecutive logits.  Probabilities of a 64-pixel tile are
 // transposed through LDS so the NCHW prob write is 16-byte vectors along the pixel axis.
-template <typename T, int NBINS>
+// STATS: the uncertainty planes of cfpnet_hip.h (std, entropy, pmax) from the values the softmax holds anyway: one more sum in the
+// exponential loop (t = sum e d, the only place the shifted logit d exists), a second walk over the probabilities for the centred
+// variance once pred is known, and lanes 1-3 store beside lane 0.  A compile-time switch: the STATS = false kernels are the code
+// they were before the planes existed.
+template <typename T, int NBINS, bool STATS>
 __global__ __launch_bounds__(256) void bin_softmax_kernel(const T* __restrict__ logits, int ld, const float* __restrict__ centers,
-                                                          T* __restrict__ prob, float* __restrict__ pred, int HW) {
+                                                          T* __restrict__ prob, float* __restrict__ pred, float* __restrict__ stats, int HW) {
   constexpr int PL = NBINS / 64;            // logits per lane
   constexpr int TP = sizeof(T) == 2 ? 64 : 32;   // pixels per tile
   constexpr int PITCH = TP + (sizeof(T) == 2 ? 8 : 4);
@@ -127,16 +132,32 @@ __global__ __launch_bounds__(256) void bin_softmax_kernel(const T* __restrict__ 
 #pragma unroll
     for (int j = 1; j < PL; ++j) mx = fmaxf(mx, v[j]);
     mx = wave_max(mx);
-    float s = 0.f;
+    float s = 0.f, t = 0.f;
 #pragma unroll
-    for (int j = 0; j < PL; ++j) { v[j] = __expf(v[j] - mx); s += v[j]; }
+    for (int j = 0; j < PL; ++j) {
+      const float d = v[j] - mx;
+      v[j] = __expf(d);
+      s += v[j];
+      if constexpr (STATS) t = fmaf(v[j], d, t);
+    }
     s = wave_sum(s);
+    if constexpr (STATS) t = wave_sum(t);
     const float inv = 1.f / s;
+    float ent = 0.f;
+    if constexpr (STATS) ent = unc_entropy(s, t, inv);
     float dot = 0.f;
 #pragma unroll
     for (int j = 0; j < PL; ++j) { v[j] *= inv; dot = fmaf(v[j], cen[j], dot); }
     dot = wave_sum(dot);
     if (lane == 0) pred[(long long)b * HW + pix] = dot;
+    if constexpr (STATS) {
+      float var = 0.f;
+#pragma unroll
+      for (int j = 0; j < PL; ++j) { const float dc = cen[j] - dot; var = fmaf(v[j] * dc, dc, var); }
+      var = wave_sum(var);
+      if (lane >= 1 && lane <= 3)
+        stats[((long long)b * 3 + (lane - 1)) * HW + pix] = unc_plane(lane - 1, var, ent, inv);
+    }
     if (prob) {
 #pragma unroll
       for (int j = 0; j < PL; ++j) sP[(lane * PL + j) * PITCH + pi] = from_f32<T>(v[j]);
@@ -173,8 +194,8 @@ extern "C" int cfp_bin_regressor(const float* partial, int nsplit, float inv_hw,
   return cfp_check_launch("cfp_bin_regressor");
 }
 
-extern "C" int cfp_bin_softmax(const void* logits, int ld, const float* centers, void* prob, float* pred, int B, int HW,
-                               int nbins, int dtype, cfp_stream_t stream) {
+extern "C" int cfp_bin_softmax_stats(const void* logits, int ld, const float* centers, void* prob, float* pred, float* stats, int B, int HW,
+                                     int nbins, int dtype, cfp_stream_t stream) {
   CFP_REQUIRE(dtype_ok(dtype), CFP_EINVAL, "cfp_bin_softmax: bad dtype");
   CFP_REQUIRE(logits && centers && pred, CFP_EINVAL, "cfp_bin_softmax: null pointer");
   CFP_REQUIRE(B > 0 && B <= 65535 && HW > 0 && (nbins == 256 || nbins == 128 || nbins == 64) && ld >= nbins, CFP_ESHAPE,
@@ -186,14 +207,23 @@ extern "C" int cfp_bin_softmax(const void* logits, int ld, const float* centers,
     constexpr int TP = sizeof(T) == 2 ? 64 : 32;                                                                   \
     constexpr int PITCH = TP + (sizeof(T) == 2 ? 8 : 4);                                                           \
     size_t lds = (size_t)NBI * PITCH * sizeof(T);                                                                  \
-    hipLaunchKernelGGL((bin_softmax_kernel<T, NBI>), dim3(cdiv(HW, TP), B), dim3(256), lds, s, (const T*)logits, ld, \
-                       centers, (T*)prob, pred, HW);                                                               \
+    if (stats)                                                                                                     \
+      hipLaunchKernelGGL((bin_softmax_kernel<T, NBI, true>), dim3(cdiv(HW, TP), B), dim3(256), lds, s, (const T*)logits, ld, \
+                         centers, (T*)prob, pred, stats, HW);                                                      \
+    else                                                                                                           \
+      hipLaunchKernelGGL((bin_softmax_kernel<T, NBI, false>), dim3(cdiv(HW, TP), B), dim3(256), lds, s, (const T*)logits, ld, \
+                         centers, (T*)prob, pred, (float*)nullptr, HW);                                            \
   } while (0)
 #define SM_SWITCH(T) switch (nbins) { case 256: SM_LAUNCH(T, 256); break; case 128: SM_LAUNCH(T, 128); break; default: SM_LAUNCH(T, 64); break; }
   if (dtype == CFP_BF16) { SM_SWITCH(bf16_t); } else if (dtype == CFP_F16) { SM_SWITCH(f16_t); } else { SM_SWITCH(float); }
 #undef SM_SWITCH
 #undef SM_LAUNCH
   return cfp_check_launch("cfp_bin_softmax");
+}
+
+extern "C" int cfp_bin_softmax(const void* logits, int ld, const float* centers, void* prob, float* pred, int B, int HW,
+                               int nbins, int dtype, cfp_stream_t stream) {
+  return cfp_bin_softmax_stats(logits, ld, centers, prob, pred, nullptr, B, HW, nbins, dtype, stream);
 }
 
 // ---- fused bin head ----------------------------------------------------------------------
@@ -204,10 +234,12 @@ extern "C" int cfp_bin_softmax(const void* logits, int ld, const float* centers,
 namespace {
 constexpr int HBM_ = 128, HBN_ = 256, HPITCH = HBM_ + 8;
 
-template <typename H>
+// STATS: the uncertainty planes as in bin_softmax_kernel; a row's reduced values sit in all 16 `fr` lanes after the butterflies, so
+// fr = 1, 2, 3 store the three planes beside fr = 0's pred.
+template <typename H, bool STATS>
 __global__ __launch_bounds__(256) void bin_head_fused_kernel(ConvP p, const float* __restrict__ bias,
                                                              const float* __restrict__ centers, H* __restrict__ prob,
-                                                             float* __restrict__ pred, int HW) {
+                                                             float* __restrict__ pred, float* __restrict__ stats, int HW) {
   constexpr int TM = 2, TN = 16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -236,18 +268,38 @@ __global__ __launch_bounds__(256) void bin_head_fused_kernel(ConvP p, const floa
       for (int j = 0; j < TN; ++j) { pr[r][j] = acc[i][j][r] + bs[j]; mx = fmaxf(mx, pr[r][j]); }
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
-      float s = 0.f;
+      float s = 0.f, t = 0.f;
 #pragma unroll
-      for (int j = 0; j < TN; ++j) { pr[r][j] = __expf(pr[r][j] - mx); s += pr[r][j]; }
+      for (int j = 0; j < TN; ++j) {
+        const float d = pr[r][j] - mx;
+        pr[r][j] = __expf(d);
+        s += pr[r][j];
+        if constexpr (STATS) t = fmaf(pr[r][j], d, t);
+      }
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) s += __shfl_xor(s, o, 64);
+      if constexpr (STATS) {
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) t += __shfl_xor(t, o, 64);
+      }
       const float inv = 1.f / s;
+      float ent = 0.f;
+      if constexpr (STATS) ent = unc_entropy(s, t, inv);
       float dot = 0.f;
 #pragma unroll
       for (int j = 0; j < TN; ++j) { pr[r][j] *= inv; dot = fmaf(pr[r][j], cen[j], dot); }
 #pragma unroll
       for (int o = 1; o < 16; o <<= 1) dot += __shfl_xor(dot, o, 64);
       if (fr == 0 && mrow + r < p.M) pred[mrow + r] = dot;
+      if constexpr (STATS) {
+        float var = 0.f;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) { const float dc = cen[j] - dot; var = fmaf(pr[r][j] * dc, dc, var); }
+#pragma unroll
+        for (int o = 1; o < 16; o <<= 1) var += __shfl_xor(var, o, 64);
+        if (fr >= 1 && fr <= 3 && mrow + r < p.M)
+          stats[((long long)bidx * 3 + (fr - 1)) * HW + (mrow + r - bidx * HW)] = unc_plane(fr - 1, var, ent, inv);
+      }
     }
     if (prob) {
 #pragma unroll
@@ -272,14 +324,14 @@ __global__ __launch_bounds__(256) void bin_head_fused_kernel(ConvP p, const floa
 }
 }  // namespace
 
-extern "C" int cfp_bin_head_fused(const void* x, int x_ld, const void* w, const float* bias, const float* centers,
-                                  void* prob, float* pred, int B, int HW, int Cin, int dtype, cfp_stream_t stream) {
+extern "C" int cfp_bin_head_fused_stats(const void* x, int x_ld, const void* w, const float* bias, const float* centers,
+                                        void* prob, float* pred, float* stats, int B, int HW, int Cin, int dtype, cfp_stream_t stream) {
   if (dtype == CFP_F32X3) {      // float32 tensors, f16x3 matrix math, float32 prob: conv_igemm_x3.hip
     CFP_REQUIRE(x && w && bias && centers && pred, CFP_EINVAL, "cfp_bin_head_fused: null pointer");
     CFP_REQUIRE(B > 0 && HW > 0 && HW % 4 == 0 && Cin > 0 && Cin % 4 == 0 && x_ld % 4 == 0 && x_ld >= Cin && (long long)B * HW < (1ll << 31), CFP_ESHAPE,
                 "cfp_bin_head_fused: bad shape (HW and Cin must be multiples of 4)");
     CFP_REQUIRE(aligned16(x) && aligned16(w) && aligned16(prob) && aligned16(bias) && aligned16(centers), CFP_EINVAL, "cfp_bin_head_fused: pointers must be 16-byte aligned");
-    int rc = bin_head_x3_launch(x, x_ld, w, bias, centers, (float*)prob, pred, B, HW, Cin, reinterpret_cast<hipStream_t>(stream));
+    int rc = bin_head_x3_launch(x, x_ld, w, bias, centers, (float*)prob, pred, stats, B, HW, Cin, reinterpret_cast<hipStream_t>(stream));
     CFP_REQUIRE(rc == 0, CFP_EHIP, "cfp_bin_head_fused: f16x3 kernel launch failed");
     return cfp_check_launch("cfp_bin_head_fused");
   }
@@ -297,17 +349,22 @@ extern "C" int cfp_bin_head_fused(const void* x, int x_ld, const void* w, const 
   size_t lds = (size_t)HBN_ * HPITCH * sizeof(bf16_t);
   size_t ops_lds = 2 * (HBM_ + HBN_) * 64;
   if (lds < ops_lds) lds = ops_lds;
-  hipError_t e = dtype == CFP_F16
-      ? hipFuncSetAttribute((const void*)bin_head_fused_kernel<f16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)
-      : hipFuncSetAttribute((const void*)bin_head_fused_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) { cfp_set_error(std::string("cfp_bin_head_fused: ") + hipGetErrorString(e)); return CFP_EHIP; }
-  if (dtype == CFP_F16)
-    hipLaunchKernelGGL(bin_head_fused_kernel<f16_t>, dim3(cdiv(p.M, HBM_)), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), p, bias,
-                       centers, (f16_t*)prob, pred, HW);
-  else
-    hipLaunchKernelGGL(bin_head_fused_kernel<bf16_t>, dim3(cdiv(p.M, HBM_)), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), p, bias,
-                       centers, (bf16_t*)prob, pred, HW);
+#define BH_LAUNCH(T, ST)                                                                                                                  \
+  do {                                                                                                                                    \
+    hipError_t e = hipFuncSetAttribute((const void*)bin_head_fused_kernel<T, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);  \
+    if (e != hipSuccess) { cfp_set_error(std::string("cfp_bin_head_fused: ") + hipGetErrorString(e)); return CFP_EHIP; }                  \
+    hipLaunchKernelGGL((bin_head_fused_kernel<T, ST>), dim3(cdiv(p.M, HBM_)), dim3(256), lds, reinterpret_cast<hipStream_t>(stream), p,   \
+                       bias, centers, (T*)prob, pred, stats, HW);                                                                         \
+  } while (0)
+  if (dtype == CFP_F16) { if (stats) BH_LAUNCH(f16_t, true); else BH_LAUNCH(f16_t, false); }
+  else { if (stats) BH_LAUNCH(bf16_t, true); else BH_LAUNCH(bf16_t, false); }
+#undef BH_LAUNCH
   return cfp_check_launch("cfp_bin_head_fused");
+}
+
+extern "C" int cfp_bin_head_fused(const void* x, int x_ld, const void* w, const float* bias, const float* centers,
+                                  void* prob, float* pred, int B, int HW, int Cin, int dtype, cfp_stream_t stream) {
+  return cfp_bin_head_fused_stats(x, x_ld, w, bias, centers, prob, pred, nullptr, B, HW, Cin, dtype, stream);
 }
 
 // ---- spatial mean of a 3x3 convolution's output WITHOUT running the convolution -----------------------------------------

@@ -27,7 +27,11 @@
 //     GEMM2 tile: +11 % / +22 % matrix work of a kernel that is not matrix-bound) remove the rounding of `ram` and of the
 //     conv_out weights from the logits.
 //   * prob leaves through LDS transposed to [bin][pixel] so the NCHW write is 16-byte vectors along the pixel axis.
+//   * optional uncertainty planes (STATS, head_stats.h): t = sum e d in the exponential loop, the centred variance as a second walk over
+//     the exponentials in the accumulators and the centres in LDS (scaled by 1 / s at the end), stored by the lane quarters fq = 1, 2, 3
+//     beside fq = 0's pred.  A compile-time switch: the STATS = false kernels are the code they were.
 #include "common.h"
+#include "head_stats.h"
 
 namespace {
 
@@ -54,6 +58,7 @@ struct HeadP {
   int wout_lo;      // Wout carries a second plane (lo = W - hi) right after the first
   int ram_lo;       // feed ram to GEMM2 as hi + lo
   int probe;        // timing probes (tools/head_bench.py --probe): 1 = descriptors with zero records (no fetch), 2 = stop after GEMM1, 4 = stop after GEMM2
+  float* stats;     // [B][3][HW] uncertainty planes (STATS kernels only; last, so that every other field keeps its kernel-argument offset)
 };
 
 #ifdef HF_GLDS
@@ -72,7 +77,7 @@ template <int N> __device__ __forceinline__ void hf_wait_vmcnt() { asm volatile(
 template <int N> __device__ __forceinline__ void hf_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory"); }
 #endif
 
-template <typename H, bool RAMLO>
+template <typename H, bool RAMLO, bool STATS>
 __global__ __launch_bounds__(256, 2) void depth_head_fused_kernel(HeadP p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
@@ -320,14 +325,26 @@ __global__ __launch_bounds__(256, 2) void depth_head_fused_kernel(HeadP p) {
       for (int r = 0; r < 4; ++r) mx = fmaxf(mx, acc2[ti][j][r]);
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float s = 0.f;
+    float s = 0.f, t = 0.f;
 #pragma unroll
     for (int ti = 0; ti < 16; ++ti)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { const float e = __expf(acc2[ti][j][r] - mx); acc2[ti][j][r] = e; s += e; }
+      for (int r = 0; r < 4; ++r) {
+        const float d = acc2[ti][j][r] - mx;
+        const float e = __expf(d);
+        acc2[ti][j][r] = e;
+        s += e;
+        if constexpr (STATS) t = fmaf(e, d, t);
+      }
     s += __shfl_xor(s, 16, 64);
     s += __shfl_xor(s, 32, 64);
+    if constexpr (STATS) {
+      t += __shfl_xor(t, 16, 64);
+      t += __shfl_xor(t, 32, 64);
+    }
     const float inv = 1.f / s;
+    float ent = 0.f;
+    if constexpr (STATS) ent = unc_entropy(s, t, inv);
     float dot = 0.f;
 #pragma unroll
     for (int ti = 0; ti < 16; ++ti) {
@@ -337,12 +354,31 @@ __global__ __launch_bounds__(256, 2) void depth_head_fused_kernel(HeadP p) {
       for (int r = 0; r < 4; ++r) {
         const float pr = acc2[ti][j][r] * inv;
         dot = fmaf(pr, cen[r], dot);
-        if (prob) sP[(ti * 16 + fq * 4 + r) * HF_PPITCH + pl] = from_f32<H>(pr);
+        if constexpr (!STATS) { if (prob) sP[(ti * 16 + fq * 4 + r) * HF_PPITCH + pl] = from_f32<H>(pr); }
       }
     }
     dot += __shfl_xor(dot, 16, 64);
     dot += __shfl_xor(dot, 32, 64);
     if (fq == 0 && m < p.M) p.pred[m] = dot;
+    if constexpr (STATS) {
+      float var = 0.f;      // sum e (c - mu)^2: the accumulators hold the exponentials, 1 / s is applied once at the end
+#pragma unroll
+      for (int ti = 0; ti < 16; ++ti) {
+        float cen[4];
+        Vec<float>::load(sK + (bimg == img0 ? 512 : 768) + ti * 16 + fq * 4, cen);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float dc = cen[r] - dot;
+          var = fmaf(acc2[ti][j][r] * dc, dc, var);
+          // the staging store waits for this walk, where the accumulators die one by one as they do in the plain kernel's expectation
+          // loop: with it up there all 128 stay live across both loops and the allocator spills
+          if (prob) sP[(ti * 16 + fq * 4 + r) * HF_PPITCH + pl] = from_f32<H>(acc2[ti][j][r] * inv);
+        }
+      }
+      var += __shfl_xor(var, 16, 64);
+      var += __shfl_xor(var, 32, 64);
+      if (fq != 0 && m < p.M) p.stats[((long long)bimg * 3 + (fq - 1)) * p.HW + (m - bimg * p.HW)] = unc_plane(fq - 1, var * inv, ent, inv);
+    }
   }
   if (!prob) return;
   __syncthreads();
@@ -359,9 +395,9 @@ __global__ __launch_bounds__(256, 2) void depth_head_fused_kernel(HeadP p) {
 
 }  // namespace
 
-extern "C" int cfp_depth_head_fused(const void* x, int x_ld, const void* w3, const float* scale3, const float* shift3,
-                                    const void* wout_perm, const float* bias_out, const float* centers, void* prob, float* pred,
-                                    void* ram_out, int B, int H, int W, int flags, int dtype, cfp_stream_t stream) {
+extern "C" int cfp_depth_head_fused_stats(const void* x, int x_ld, const void* w3, const float* scale3, const float* shift3,
+                                          const void* wout_perm, const float* bias_out, const float* centers, void* prob, float* pred,
+                                          float* stats, void* ram_out, int B, int H, int W, int flags, int dtype, cfp_stream_t stream) {
   CFP_REQUIRE(is16(dtype), CFP_EINVAL, "cfp_depth_head_fused: bf16/f16 only (f32 parity mode runs conv + bin_softmax)");
   CFP_REQUIRE(x && w3 && wout_perm && bias_out && centers && pred, CFP_EINVAL, "cfp_depth_head_fused: null pointer");
   CFP_REQUIRE(B > 0 && H > 0 && W > 0 && x_ld >= HF_C && x_ld % 8 == 0, CFP_ESHAPE, "cfp_depth_head_fused: bad shape (128 channels, x_ld % 8 == 0)");
@@ -373,25 +409,34 @@ extern "C" int cfp_depth_head_fused(const void* x, int x_ld, const void* w3, con
   CFP_REQUIRE((flags & ~(3 | (7 << 8))) == 0, CFP_EINVAL, "cfp_depth_head_fused: unknown flags");
   HeadP p;
   p.x = x; p.w3 = w3; p.scale3 = scale3; p.shift3 = shift3; p.wout = wout_perm; p.bias_out = bias_out; p.centers = centers;
-  p.prob = prob; p.pred = pred; p.ram_out = ram_out;
+  p.prob = prob; p.pred = pred; p.ram_out = ram_out; p.stats = stats;
   p.x_ld = x_ld; p.B = B; p.H = H; p.W = W; p.M = (int)M; p.HW = H * W;
   p.wout_lo = (flags & CFP_HEAD_WOUT_HILO) ? 1 : 0; p.ram_lo = (flags & CFP_HEAD_RAM_HILO) ? 1 : 0; p.probe = (flags >> 8) & 7;
   const int grid = cdiv(M, HF_BM);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define HF_LAUNCH(T, RL)                                                                                                              \
+#define HF_LAUNCH_(T, RL, ST)                                                                                                            \
   do {                                                                                                                                \
     static bool attr = false;                                                                                                         \
     if (!attr) {                                                                                                                      \
-      if (hipFuncSetAttribute((const void*)depth_head_fused_kernel<T, RL>, hipFuncAttributeMaxDynamicSharedMemorySize, HF_LDS) != hipSuccess) { \
+      if (hipFuncSetAttribute((const void*)depth_head_fused_kernel<T, RL, ST>, hipFuncAttributeMaxDynamicSharedMemorySize, HF_LDS) != hipSuccess) { \
         cfp_set_error("cfp_depth_head_fused: cannot set the LDS size");                                                               \
         return CFP_EHIP;                                                                                                              \
       }                                                                                                                               \
       attr = true;                                                                                                                    \
     }                                                                                                                                 \
-    hipLaunchKernelGGL((depth_head_fused_kernel<T, RL>), dim3(grid), dim3(256), HF_LDS, s, p);                                        \
+    hipLaunchKernelGGL((depth_head_fused_kernel<T, RL, ST>), dim3(grid), dim3(256), HF_LDS, s, p);                                        \
   } while (0)
+#define HF_LAUNCH(T, RL) do { if (stats) HF_LAUNCH_(T, RL, true); else HF_LAUNCH_(T, RL, false); } while (0)
   if (dtype == CFP_F16) { if (p.ram_lo) HF_LAUNCH(f16_t, true); else HF_LAUNCH(f16_t, false); }
   else { if (p.ram_lo) HF_LAUNCH(bf16_t, true); else HF_LAUNCH(bf16_t, false); }
 #undef HF_LAUNCH
+#undef HF_LAUNCH_
   return cfp_check_launch("cfp_depth_head_fused");
+}
+
+extern "C" int cfp_depth_head_fused(const void* x, int x_ld, const void* w3, const float* scale3, const float* shift3,
+                                    const void* wout_perm, const float* bias_out, const float* centers, void* prob, float* pred,
+                                    void* ram_out, int B, int H, int W, int flags, int dtype, cfp_stream_t stream) {
+  return cfp_depth_head_fused_stats(x, x_ld, w3, scale3, shift3, wout_perm, bias_out, centers, prob, pred, nullptr, ram_out, B, H, W, flags,
+                                    dtype, stream);
 }

@@ -184,21 +184,31 @@ class Deltar(_Store):
         return out
 
     def forward(self, input_data: Dict, **kwargs):
+        """-> (bin_edges, pred, prob, unc).  `return_uncertainty=True` (eval mode only) fills the fourth element -- None otherwise, the
+        reference's unused `prob_residual` slot -- with the per-pixel uncertainty of the bin distribution: float32 [B,3,H/2,W/2], planes
+        hip.UNC_STD (metres), hip.UNC_ENTROPY (nats), hip.UNC_PMAX, from the head kernel itself (`Engine.forward(uncertainty=True)`)."""
+        return_unc = bool(kwargs.get("return_uncertainty", False))
         if self.training:
+            if return_unc:
+                raise ValueError("return_uncertainty=True needs eval mode: the training head keeps no uncertainty statistics")
             return self._forward_train(input_data, kwargs.get("pos_offsets"))
         eng = self.engine(input_data["rgb"].device if input_data["rgb"].is_cuda else None)
         pos_offsets = kwargs.get("pos_offsets")
         if pos_offsets is None:
             pos_offsets = self.draw_pos_offsets(input_data["rgb"].shape[-2], input_data["rgb"].shape[-1])
         return_prob = kwargs.get("return_prob", True)
+        unc = None
         if self.eval_graphs:
-            edges, pred, prob = self._forward_eval_graph(eng, input_data, pos_offsets, return_prob)
+            edges, pred, prob, *rest = self._forward_eval_graph(eng, input_data, pos_offsets, return_prob, return_unc)
             if not self.eval_static_outputs:
                 edges, pred = edges.clone(), pred.clone()
                 if prob is not None and (self.prob_dtype is None or prob.dtype == self.prob_dtype):
                     prob = prob.clone()                    # (a dtype cast below is a fresh tensor already)
+                rest = [t.clone() for t in rest]
         else:
-            edges, pred, prob = eng.forward(input_data, return_prob=return_prob, pos_offsets=pos_offsets)
+            edges, pred, prob, *rest = eng.forward(input_data, return_prob=return_prob, pos_offsets=pos_offsets, uncertainty=return_unc)
+        if return_unc:
+            unc = rest[0]
         # the reference returns `prob` in float32 (deltar.py:51,64-67).  The default mode (f32x3) and the float32 mode write it in that
         # type themselves; only the opt-in 16-bit speed modes store 2 bytes per element and pay this cast (prob_dtype=None: as stored)
         if prob is not None and self.prob_dtype is not None and prob.dtype != self.prob_dtype:
@@ -206,9 +216,9 @@ class Deltar(_Store):
         if self.check_finite and not bool(torch.isfinite(pred).all()):
             raise FloatingPointError("cfpnet_amd: non-finite depth map" + (" -- the f32x3 mode holds values as two IEEE halves (|activation| < 1.31e5); "
                                      "build the model with dtype=torch.float32 for inputs / weights of this magnitude" if self.x3 else ""))
-        return edges, pred, prob, None
+        return edges, pred, prob, unc
 
-    def _forward_eval_graph(self, eng, input_data: Dict, pos_offsets, return_prob: bool):
+    def _forward_eval_graph(self, eng, input_data: Dict, pos_offsets, return_prob: bool, return_unc: bool = False):
         """Eval forward as a HIP-graph replay.  Two kinds of graph per input geometry and output-ring slot: one that reads PRIVATE copies
         of the inputs (any caller: three device copies, then the replay) and -- from the second consecutive call with the very same
         device tensors on -- one that reads the CALLER'S tensors in place: that replay is pure host logic + one graph launch, no torch
@@ -219,7 +229,7 @@ class Deltar(_Store):
             self._sig_cache = (pinfo, _patch_signature(pinfo))
         # the positional windows (random per forward below the table size: fusion.py:87-91) are NOT part of the key: the graphs read them
         # from a device buffer, rewritten only when the drawn values change (never at 480x640, where they are all zero)
-        key = (tuple(rgb.shape), tuple(add["hist_data"].shape), self._sig_cache[1], bool(return_prob))
+        key = (tuple(rgb.shape), tuple(add["hist_data"].shape), self._sig_cache[1], bool(return_prob), bool(return_unc))
         if self._eval_offs is None or self._eval_offs.device != eng.device:
             self._eval_offs = torch.zeros(3, 2, dtype=torch.int32, device=eng.device)
             self._eval_offs_host = (0,) * 6
@@ -249,13 +259,13 @@ class Deltar(_Store):
             if h is None:
                 if len(st["adopted"]) >= 2 * max(1, int(self.eval_out_ring)):
                     st["adopted"].clear()
-                eng.capture(input_data, return_prob=return_prob, pos_offsets=pos_offsets, adopt_inputs=True)
+                eng.capture(input_data, return_prob=return_prob, pos_offsets=pos_offsets, adopt_inputs=True, uncertainty=return_unc)
                 h = st["adopted"][(ptrs, slot)] = eng._graph
             eng._graph, eng._slots = h, None
             return eng.replay()
         h = st["owned"].get(slot)
         if h is None:
-            eng.capture(input_data, return_prob=return_prob, pos_offsets=pos_offsets)
+            eng.capture(input_data, return_prob=return_prob, pos_offsets=pos_offsets, uncertainty=return_unc)
             h = st["owned"][slot] = eng._graph
         eng._graph, eng._slots = h, None
         return eng.replay(input_data)

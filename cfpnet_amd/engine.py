@@ -771,7 +771,8 @@ class Engine:
 
     # ------------------------------------------------------------------------------ batch lanes
     @torch.no_grad()
-    def forward_lanes(self, input_data: dict, lanes: int, *, return_prob: bool = True, pos_offsets: Optional[dict] = None):
+    def forward_lanes(self, input_data: dict, lanes: int, *, return_prob: bool = True, pos_offsets: Optional[dict] = None,
+                      uncertainty: bool = False):
         """The same forward with the batch cut into `lanes` contiguous sub-batches that run CONCURRENTLY, each on its own
         HIP stream with its own scratch buffers, writing into slices of one set of outputs.  At batch 8 a forward is ~280
         dependent kernels that each leave most of the 256 CUs idle while they wait on their own loads (a batch-1 forward
@@ -781,13 +782,14 @@ class Engine:
         B = rgb.shape[0]
         lanes = max(1, min(lanes, B))
         if lanes == 1:
-            return self.forward(input_data, return_prob=return_prob, pos_offsets=pos_offsets)
+            return self.forward(input_data, return_prob=return_prob, pos_offsets=pos_offsets, uncertainty=uncertainty)
         dev = self.device
         add = input_data["additional"]
         H, W = rgb.shape[-2:]
         edges = torch.empty(B, self.n_bins + 1, dtype=torch.float32, device=dev)
         pred = torch.empty(B, 1, H // 2, W // 2, dtype=torch.float32, device=dev)
         prob = torch.empty(B, self.n_bins, H // 2, W // 2, dtype=self.dtype, device=dev) if return_prob else None
+        unc = torch.empty(B, 3, H // 2, W // 2, dtype=torch.float32, device=dev) if uncertainty else None
         main = torch.cuda.current_stream(dev)
         bounds = [B * i // lanes for i in range(lanes + 1)]
         for i in range(lanes):
@@ -801,23 +803,23 @@ class Engine:
             b0, b1 = bounds[i], bounds[i + 1]
             sub = {"rgb": rgb_d[b0:b1], "additional": {"hist_data": hist_d[b0:b1], "mask": mask_d[b0:b1],
                                                        "rect_data": add.get("rect_data"), "patch_info": add["patch_info"]}}
-            outs = (edges[b0:b1], pred[b0:b1], prob[b0:b1] if prob is not None else None)
+            outs = (edges[b0:b1], pred[b0:b1], prob[b0:b1] if prob is not None else None) + ((unc[b0:b1],) if uncertainty else ())
             if i == 0:
-                self.forward(sub, return_prob=return_prob, pos_offsets=pos_offsets, lane=0, out=outs)
+                self.forward(sub, return_prob=return_prob, pos_offsets=pos_offsets, lane=0, out=outs, uncertainty=uncertainty)
             else:
                 st = self._lane_streams[i][0]
                 st.wait_stream(main)
                 with torch.cuda.stream(st):
-                    self.forward(sub, return_prob=return_prob, pos_offsets=pos_offsets, lane=i, out=outs)
+                    self.forward(sub, return_prob=return_prob, pos_offsets=pos_offsets, lane=i, out=outs, uncertainty=uncertainty)
         for i in range(1, lanes):
             main.wait_stream(self._lane_streams[i][0])
         self._lane = 0
         self._lanes_active = 1
-        return edges, pred, prob
+        return (edges, pred, prob, unc) if uncertainty else (edges, pred, prob)
 
     # ------------------------------------------------------------------------------ HIP graph
     def capture(self, input_data: dict, *, return_prob: bool = True, pos_offsets: Optional[dict] = None, lanes: int = 1,
-                inflight: int = 1, adopt_inputs: bool = False):
+                inflight: int = 1, adopt_inputs: bool = False, uncertainty: bool = False):
         """Record the whole forward for this input shape into HIP graphs.  The launch list is static (all
         data-dependent geometry is host-side integers), so replaying costs one graph launch instead of ~280 kernel
         launches.  With `lanes` > 1 every batch lane gets its OWN graph, captured on and replayed from its own stream
@@ -830,7 +832,10 @@ class Engine:
 
         `adopt_inputs` (single graph only): the graph reads the CALLER'S device tensors in place instead of private copies (they must be
         float32 / uint8-or-bool, contiguous, on this device and must stay alive): `replay()` without arguments then sees whatever they
-        hold at that moment, with no copy in front of it (`Deltar.forward` uses this when it is called with the same tensors again)."""
+        hold at that moment, with no copy in front of it (`Deltar.forward` uses this when it is called with the same tensors again).
+
+        `uncertainty`: as in `forward` -- the captured forward also writes the uncertainty map, and this call, `replay` and
+        `replay_async` return (edges, pred, prob, unc) instead of the 3-tuple."""
         dev = self.device
         add = input_data["additional"]
         B = input_data["rgb"].shape[0]
@@ -839,7 +844,7 @@ class Engine:
         self._slots = None
         self._slot_next = 0
         if inflight > 1:
-            return self._capture_inflight(input_data, inflight, return_prob, pos_offsets)
+            return self._capture_inflight(input_data, inflight, return_prob, pos_offsets, uncertainty)
         if adopt_inputs:
             assert lanes == 1, "adopt_inputs: single-graph capture only"
             m = add["mask"]
@@ -855,6 +860,7 @@ class Engine:
         edges = torch.empty(B, self.n_bins + 1, dtype=torch.float32, device=dev)
         pred = torch.empty(B, 1, H // 2, W // 2, dtype=torch.float32, device=dev)
         prob = torch.empty(B, self.n_bins, H // 2, W // 2, dtype=self.dtype, device=dev) if return_prob else None
+        unc = torch.empty(B, 3, H // 2, W // 2, dtype=torch.float32, device=dev) if uncertainty else None
         bounds = [B * i // lanes for i in range(lanes + 1)]
         subs, outs = [], []
         for i in range(lanes):
@@ -862,7 +868,7 @@ class Engine:
             sa = static["additional"]
             subs.append({"rgb": static["rgb"][b0:b1], "additional": {"hist_data": sa["hist_data"][b0:b1], "mask": sa["mask"][b0:b1],
                                                                      "rect_data": sa["rect_data"], "patch_info": sa["patch_info"]}})
-            outs.append((edges[b0:b1], pred[b0:b1], prob[b0:b1] if prob is not None else None))
+            outs.append((edges[b0:b1], pred[b0:b1], prob[b0:b1] if prob is not None else None) + ((unc[b0:b1],) if uncertainty else ()))
             if i not in self._lane_streams:
                 self._lane_streams[i] = (_shared_stream(dev, ("lane", i)), _shared_stream(dev, ("lane-side", i)))
         graphs = []
@@ -874,21 +880,22 @@ class Engine:
             st.wait_stream(cur)
             with torch.cuda.stream(st):
                 for _ in range(2):      # warm-up: allocates every buffer of the lane's plan, sets kernel attributes
-                    self.forward(subs[i], return_prob=return_prob, pos_offsets=pos_offsets, lane=i, out=outs[i])
+                    self.forward(subs[i], return_prob=return_prob, pos_offsets=pos_offsets, lane=i, out=outs[i], uncertainty=uncertainty)
             torch.cuda.synchronize(dev)
             g = torch.cuda.CUDAGraph()
             self._capturing = True
             try:
                 with torch.cuda.graph(g, stream=st):
-                    self.forward(subs[i], return_prob=return_prob, pos_offsets=pos_offsets, lane=i, out=outs[i])
+                    self.forward(subs[i], return_prob=return_prob, pos_offsets=pos_offsets, lane=i, out=outs[i], uncertainty=uncertainty)
             finally:
                 self._capturing = False
             graphs.append(g)
         torch.cuda.synchronize(dev)
         self._lane = 0
         self._lanes_active = 1
-        self._graph = (graphs, static, (edges, pred, prob))
-        return edges, pred, prob
+        result = (edges, pred, prob, unc) if uncertainty else (edges, pred, prob)
+        self._graph = (graphs, static, result)
+        return result
 
     def plan_mode(self, throughput: bool):
         """Which of the two kernel plans the convolutions launched from now on follow: the default one, fitted on isolated timings, or the
@@ -898,14 +905,14 @@ class Engine:
         tile), i.e. another float32 summation order -- re-association noise, far below the storage rounding of the 16-bit modes."""
         ops.PLAN_IN_FLIGHT = bool(throughput) and os.environ.get("CFP_TPUT_PLAN", "1") != "0"
 
-    def _capture_inflight(self, input_data, inflight, return_prob, pos_offsets):
+    def _capture_inflight(self, input_data, inflight, return_prob, pos_offsets, uncertainty=False):
         self.plan_mode(True)
         try:
-            return self._capture_inflight_impl(input_data, inflight, return_prob, pos_offsets)
+            return self._capture_inflight_impl(input_data, inflight, return_prob, pos_offsets, uncertainty)
         finally:
             self.plan_mode(False)
 
-    def _capture_inflight_impl(self, input_data, inflight, return_prob, pos_offsets):
+    def _capture_inflight_impl(self, input_data, inflight, return_prob, pos_offsets, uncertainty=False):
         dev = self.device
         add = input_data["additional"]
         B = input_data["rgb"].shape[0]
@@ -923,16 +930,18 @@ class Engine:
             out = (torch.empty(B, self.n_bins + 1, dtype=torch.float32, device=dev),
                    torch.empty(B, 1, H // 2, W // 2, dtype=torch.float32, device=dev),
                    torch.empty(B, self.n_bins, H // 2, W // 2, dtype=self.dtype, device=dev) if return_prob else None)
+            if uncertainty:
+                out += (torch.empty(B, 3, H // 2, W // 2, dtype=torch.float32, device=dev),)
             st.wait_stream(cur)
             with torch.cuda.stream(st):
                 for _ in range(2):
-                    self.forward(static, return_prob=return_prob, pos_offsets=pos_offsets, lane=si, out=out)
+                    self.forward(static, return_prob=return_prob, pos_offsets=pos_offsets, lane=si, out=out, uncertainty=uncertainty)
             torch.cuda.synchronize(dev)
             g = torch.cuda.CUDAGraph()
             self._capturing = True
             try:
                 with torch.cuda.graph(g, stream=st):
-                    self.forward(static, return_prob=return_prob, pos_offsets=pos_offsets, lane=si, out=out)
+                    self.forward(static, return_prob=return_prob, pos_offsets=pos_offsets, lane=si, out=out, uncertainty=uncertainty)
             finally:
                 self._capturing = False
             slots.append({"graph": g, "static": static, "out": out, "stream": st, "event": torch.cuda.Event()})
@@ -944,7 +953,7 @@ class Engine:
 
     def replay_async(self, input_data: Optional[dict] = None):
         """Launch the captured forward on the next in-flight slot WITHOUT making the current stream wait for it.
-        Returns ((edges, pred, prob), event): the tensors belong to the slot and are valid from `event` until the slot
+        Returns ((edges, pred, prob), event) -- with `unc` as a fourth tensor when captured with `uncertainty=True`: the tensors belong to the slot and are valid from `event` until the slot
         comes round again (`inflight` calls later).  Inputs are read on the slot's stream after the current stream's
         pending work.  Falls back to `replay` (+ an event on the current stream) when captured without `inflight`."""
         dev = self.device
@@ -1060,10 +1069,15 @@ class Engine:
     @torch.no_grad()
     def forward(self, input_data: dict, *, return_prob: bool = True, pos_offsets: Optional[dict] = None,
                 taps: Optional[dict] = None, img_features: Optional[Sequence[torch.Tensor]] = None, lane: int = 0,
-                out: Optional[tuple] = None):
+                out: Optional[tuple] = None, uncertainty: bool = False):
         """Eval-mode forward.  Returns (bin_edges [B,n+1] f32, pred [B,1,H/2,W/2] f32, prob [B,n,H/2,W/2] | None).
         `lane` selects an independent set of scratch buffers / side stream (forward_lanes); `out` = preallocated
-        (edges, pred, prob) views to write into."""
+        (edges, pred, prob) views to write into.
+
+        `uncertainty=True` returns a fourth tensor (and takes it as out[3]): unc [B,3,H/2,W/2] float32 in every numerics mode, the planes
+        hip.UNC_STD (standard deviation of the bin distribution, metres), hip.UNC_ENTROPY (nats) and hip.UNC_PMAX (largest bin
+        probability), written by the head kernel from the values its softmax holds -- three output planes instead of the n of `prob`
+        (`return_prob=False` composes with it); edges, pred and prob are bit-identical to the call without it."""
         self._lane = lane
         side = self._lane_streams[lane][1] if lane in self._lane_streams else self._side
         if not self.use_side_stream or self._lanes_active > 1:
@@ -1215,18 +1229,22 @@ class Engine:
             prob = out[2] if return_prob else None
         else:
             prob = torch.empty(B, self.n_bins, hs[0], wsz[0], dtype=self.dtype, device=dev) if return_prob else None
+        unc = None
+        if uncertainty:
+            unc = out[3] if out is not None else torch.empty(B, 3, hs[0], wsz[0], dtype=torch.float32, device=dev)
         if fused_head:
             # conv3x3 + conv_out + softmax + expectation in one kernel: neither ram nor the logits reach HBM
             ops.depth_head_fused(unet, self.P[h + ".conv3x3.w"], self.P[h + ".conv3x3.s"], self.P[h + ".conv3x3.t"], self.P["conv_out.wp"],
-                                 self.P["conv_out.t"], centers, prob, pred, B, hs[0], wsz[0], ram_out=ram, ram_hilo=self.head_hilo[1])
+                                 self.P["conv_out.t"], centers, prob, pred, B, hs[0], wsz[0], ram_out=ram, ram_hilo=self.head_hilo[1],
+                                 stats=unc)
         elif (self.half or self.x3) and self.n_bins == 256 and HWh % 8 == 0 and os.environ.get("CFP_BIN_HEAD_FUSED", "1") != "0":
             # 1x1 conv + softmax + expectation in one kernel: the logits never reach HBM
-            ops.bin_head_fused(ram, self.P["conv_out.w"], self.P["conv_out.t"], centers, prob, pred, B, HWh)
+            ops.bin_head_fused(ram, self.P["conv_out.w"], self.P["conv_out.t"], centers, prob, pred, B, HWh, stats=unc)
         else:
             logits = self._act(plan, "logits", Mh, self.n_bins)
             self._lin("conv_out.w", ram, logits, Mh, hip.ACT_NONE, None, "conv_out")
-            ops.bin_softmax(logits, centers, prob, pred, B, HWh, self.n_bins)
+            ops.bin_softmax(logits, centers, prob, pred, B, HWh, self.n_bins, stats=unc)
         if taps is not None:
             taps["unet_out"] = self._nchw(unet, B, hs[0], wsz[0])
             taps["ram"] = self._nchw(ram, B, hs[0], wsz[0])
-        return edges, pred, prob
+        return (edges, pred, prob, unc) if uncertainty else (edges, pred, prob)

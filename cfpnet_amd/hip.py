@@ -18,6 +18,7 @@ F32X3 = 3      # float32 storage + f16x3 matrix math: a planning / packing dtype
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SILU, ACT_GELU, ACT_SIGMOID = range(6)
 TOF_SAMPLE_UNIFORM, TOF_SAMPLE_ICDF = 0, 1
 HEAD_WOUT_HILO, HEAD_RAM_HILO = 1, 2
+UNC_STD, UNC_ENTROPY, UNC_PMAX = 0, 1, 2     # planes of the heads' uncertainty output (CFP_UNC_*)
 CONV_PER_IMAGE, CONV_W2, CONV_IN_FLIGHT, CONV_X3, CONV_WS_TICKETS = 1, 2, 4, 8, 16
 CONV_TICKET_BYTES = 4096     # CFP_CONV_TICKET_BYTES
 
@@ -140,6 +141,7 @@ SIGNATURES = {
     "cfp_nyu_rotate": (_i, [_p, _p, _p, _p, _i, _i, _i, _p, _p]),
     "cfp_bin_regressor": (_i, [_p, _i, _f] + [_p] * 7 + [_f, _f, _i, _p, _p, _i, _i, _i, _i, _p]),
     "cfp_bin_softmax": (_i, [_p, _i, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "cfp_bin_softmax_stats": (_i, [_p, _i, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "cfp_conv3x3_mean": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "cfp_lkpm_tail": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _f, _i, _i, _i, _p]),
     "cfp_mbconv_plan": (_i, [_i, _i, _i, _i, _i, _p, _p]),
@@ -149,6 +151,8 @@ SIGNATURES = {
     "cfp_hist_encoder": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "cfp_depth_head_fused": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "cfp_bin_head_fused": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "cfp_depth_head_fused_stats": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "cfp_bin_head_fused_stats": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
 }
 
 class WgradJob(C.Structure):

@@ -478,18 +478,33 @@ def bin_regressor(partial, nsplit, inv_hw, w1x1, w0, b0, w1, b1, w2, b2, min_val
              edges.data_ptr(), centers.data_ptr(), B, C, hidden, nbins, _s())
 
 
-def bin_softmax(logits: Act, centers, prob, pred, B, HW, nbins):
-    hip.call("cfp_bin_softmax", logits.ptr, logits.ld, centers.data_ptr(), hip.ptr(prob), pred.data_ptr(), B, HW, nbins,
-             logits.dt, _s())
+def _check_stats(stats, B, HW):
+    assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() == B * 3 * HW, "stats: float32 [B, 3, HW]"
 
 
-def bin_head_fused(x: Act, w, bias, centers, prob, pred, B, HW):
+def bin_softmax(logits: Act, centers, prob, pred, B, HW, nbins, stats=None):
+    """`stats` (float32 [B, 3, HW], optional): the uncertainty planes hip.UNC_STD / UNC_ENTROPY / UNC_PMAX of the bin distribution."""
+    if stats is None:
+        hip.call("cfp_bin_softmax", logits.ptr, logits.ld, centers.data_ptr(), hip.ptr(prob), pred.data_ptr(), B, HW, nbins,
+                 logits.dt, _s())
+        return
+    _check_stats(stats, B, HW)
+    hip.call("cfp_bin_softmax_stats", logits.ptr, logits.ld, centers.data_ptr(), hip.ptr(prob), pred.data_ptr(), stats.data_ptr(), B, HW,
+             nbins, logits.dt, _s())
+
+
+def bin_head_fused(x: Act, w, bias, centers, prob, pred, B, HW, stats=None):
     """conv_out (1x1, -> 256 logits) + softmax + expectation in one launch.  16-bit tensors with 16-bit weights [256, C], or float32
-    tensors with the pre-split f16x3 operand of pack_w_x3 (float32 prob)."""
+    tensors with the pre-split f16x3 operand of pack_w_x3 (float32 prob).  `stats`: as in bin_softmax."""
     x3 = x.buf.dtype == torch.float32 and w.dtype == torch.float16
     assert not x3 or (tuple(w.shape) == (256, (x.C + 31) // 32 * 64) and (prob is None or prob.dtype == torch.float32))
-    hip.call("cfp_bin_head_fused", x.ptr, x.ld, w.data_ptr(), bias.data_ptr(), centers.data_ptr(), hip.ptr(prob),
-             pred.data_ptr(), B, HW, x.C, hip.F32X3 if x3 else x.dt, _s())
+    if stats is None:
+        hip.call("cfp_bin_head_fused", x.ptr, x.ld, w.data_ptr(), bias.data_ptr(), centers.data_ptr(), hip.ptr(prob),
+                 pred.data_ptr(), B, HW, x.C, hip.F32X3 if x3 else x.dt, _s())
+        return
+    _check_stats(stats, B, HW)
+    hip.call("cfp_bin_head_fused_stats", x.ptr, x.ld, w.data_ptr(), bias.data_ptr(), centers.data_ptr(), hip.ptr(prob),
+             pred.data_ptr(), stats.data_ptr(), B, HW, x.C, hip.F32X3 if x3 else x.dt, _s())
 
 
 def permute_wout(w: torch.Tensor, dtype, hilo: bool = True, diffuse: bool = False) -> torch.Tensor:
@@ -543,13 +558,19 @@ def conv3x3_pw_fused(x: Act, w1: torch.Tensor, s1, t1, act1, w2_pad: torch.Tenso
 
 
 def depth_head_fused(x: Act, w3, scale3, shift3, wout_perm: torch.Tensor, bias_out, centers, prob, pred, B, H, W, ram_out: Optional[Act] = None,
-                     ram_hilo: bool = True, probe: int = 0):
+                     ram_hilo: bool = True, probe: int = 0, stats=None):
     assert x.C == 128 and w3.shape == (128, 9 * 128) and wout_perm.shape[1:] == (256, 128) and wout_perm.dtype == x.buf.dtype
     flags = (hip.HEAD_WOUT_HILO if wout_perm.shape[0] == 2 else 0) | (hip.HEAD_RAM_HILO if ram_hilo else 0) | (probe << 8)
     if ram_out is not None:
         assert ram_out.ld == 128 and ram_out.C == 128
-    hip.call("cfp_depth_head_fused", x.ptr, x.ld, w3.data_ptr(), hip.ptr(scale3), hip.ptr(shift3), wout_perm.data_ptr(), bias_out.data_ptr(),
-             centers.data_ptr(), hip.ptr(prob), pred.data_ptr(), ram_out.ptr if ram_out is not None else 0, B, H, W, flags, x.dt, _s())
+    if stats is None:
+        hip.call("cfp_depth_head_fused", x.ptr, x.ld, w3.data_ptr(), hip.ptr(scale3), hip.ptr(shift3), wout_perm.data_ptr(), bias_out.data_ptr(),
+                 centers.data_ptr(), hip.ptr(prob), pred.data_ptr(), ram_out.ptr if ram_out is not None else 0, B, H, W, flags, x.dt, _s())
+        return
+    _check_stats(stats, B, H * W)
+    hip.call("cfp_depth_head_fused_stats", x.ptr, x.ld, w3.data_ptr(), hip.ptr(scale3), hip.ptr(shift3), wout_perm.data_ptr(), bias_out.data_ptr(),
+             centers.data_ptr(), hip.ptr(prob), pred.data_ptr(), stats.data_ptr(), ram_out.ptr if ram_out is not None else 0, B, H, W, flags,
+             x.dt, _s())
 
 
 def hist_encoder(hist: torch.Tensor, blob: torch.Tensor, layout, outs, R: int, pe=(None, None, None), n_pe: int = 0):

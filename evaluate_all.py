@@ -9,6 +9,10 @@ one device kernel (`cfp_eval_metrics`, mode 0); the per-image rows stay on the d
 formed once at the end -- the reference moves prediction and ground truth to the host for every image.
 Prints `Metrics: {...}` rounded to 3 decimals and the comma-joined line, like `evaluate_all.py:88-90`.
 
+`--save_entropy` (with `--save_dir D`, default `tmp`) also asks the model for its per-pixel uncertainty map and writes, per evaluated
+batch, `D/unc_<index of the batch's first image>.npy`: float32 `[B,3,h,w]`, planes std of the bin distribution (m), entropy (nats), largest
+bin probability.  The metrics and everything printed are the same with and without it.
+
 Differences on purpose: the xlsx report (openpyxl) is not written; `--synthetic N` evaluates N seeded synthetic samples
 when the dataset is not on the box (without it a missing `filenames_file_eval` is an error); weights are the
 deterministic key-addressed set unless `weights/<name>/<selected_epoch>.pt` (the reference's location) exists or
@@ -60,11 +64,19 @@ def main(argv=None):
     model = model.to(device).eval()
     build = data.EvalInputBuilder(args, device)
     avg = metrics.RunningAverageDict()
+    save_unc = bool(getattr(args, "save_entropy", False))
+    if save_unc:
+        import numpy as np
+        os.makedirs(args.save_dir, exist_ok=True)
     n_img, t0 = 0, time.perf_counter()
     with torch.no_grad():
         for img, dep, names in data.batches(samples, bs):
             inp, gt = build(img, dep)
-            _, pred, _, _ = model(inp)
+            if save_unc:
+                _, pred, _, unc = model(inp, return_uncertainty=True)
+                np.save(os.path.join(args.save_dir, f"unc_{n_img}.npy"), unc.cpu().numpy())
+            else:
+                _, pred, _, _ = model(inp)
             avg.update(metrics.eval_metrics(pred, gt, float(args.min_depth), float(args.max_depth), mode=metrics.EVALUATE_ALL))
             n_img += img.shape[0]
     torch.cuda.synchronize()

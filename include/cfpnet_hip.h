@@ -397,10 +397,23 @@ int cfp_conv3x3_mean(const float* partial, int nsplit, const void* in, int in_ld
 
 /* Per-pixel softmax over nbins logits + expectation over bin centres:
  *   prob[b, n, hw] = softmax_n(logits[b*HW + hw, n]);  pred[b, hw] = sum_n prob * centers[b, n]
- * prob (NCHW, `dtype`) may be NULL.  pred is f32.  Replaces nn.Softmax(dim=1) of deltar.py:19
+ * nbins is 64, 128 or 256.  prob (NCHW, `dtype`) may be NULL.  pred is f32.  Replaces nn.Softmax(dim=1) of deltar.py:19
  * and deltar.py:61. */
 int cfp_bin_softmax(const void* logits, int ld, const float* centers, void* prob, float* pred,
                     int B, int HW, int nbins, int dtype, cfp_stream_t stream);
+
+/* Per-pixel uncertainty of the bin distribution, an optional third output of the three head entry points (the `_stats` twins below:
+ * the same argument lists with `float* stats` after `pred`).  With p_n the softmax over the bins (deltar.py:51), c_n the image's bin
+ * centres and mu = pred = sum_n p_n c_n (deltar.py:61), stats is float32 [B][3][HW] in every dtype:
+ *   plane CFP_UNC_STD      sqrt(sum_n p_n (c_n - mu)^2)   metres, >= 0 (centred two-pass form: no cancellation on a confident pixel)
+ *   plane CFP_UNC_ENTROPY  -sum_n p_n ln p_n              nats, 0 .. ln nbins; from the shifted logits d_n = l_n - max as
+ *                                                         ln s - (sum_n e^d_n d_n) / s with s = sum_n e^d_n: no log of a probability
+ *   plane CFP_UNC_PMAX     max_n p_n = 1 / s              1 / nbins .. 1
+ * computed from the float32 values the kernel holds before `prob` is rounded to its storage type.  stats == NULL is exactly the call
+ * without the suffix (the same kernel instantiation); with stats given, prob and pred are bit-identical to that call. */
+enum { CFP_UNC_STD = 0, CFP_UNC_ENTROPY = 1, CFP_UNC_PMAX = 2 };
+int cfp_bin_softmax_stats(const void* logits, int ld, const float* centers, void* prob, float* pred, float* stats,
+                          int B, int HW, int nbins, int dtype, cfp_stream_t stream);
 
 /* The whole adaptive-bins head in one kernel (csrc/head_fused.hip):
  *   ram = conv3x3(x) (128 -> 128, decoder.py:22-27 `self.conv3x3`), logits = conv_out(ram) (1x1, 128 -> 256,
@@ -416,6 +429,10 @@ enum { CFP_HEAD_WOUT_HILO = 1, CFP_HEAD_RAM_HILO = 2 };
 int cfp_depth_head_fused(const void* x, int x_ld, const void* w3, const float* scale3, const float* shift3,
                          const void* wout_perm, const float* bias_out, const float* centers, void* prob, float* pred,
                          void* ram_out, int B, int H, int W, int flags, int dtype, cfp_stream_t stream);
+/* The same with the uncertainty planes (see cfp_bin_softmax_stats): stats [B][3][H*W] f32, may be NULL. */
+int cfp_depth_head_fused_stats(const void* x, int x_ld, const void* w3, const float* scale3, const float* shift3,
+                               const void* wout_perm, const float* bias_out, const float* centers, void* prob, float* pred,
+                               float* stats, void* ram_out, int B, int H, int W, int flags, int dtype, cfp_stream_t stream);
 
 /* Fused bin head: logits = x @ w^T + bias never leave the chip:
  *   1x1 conv (Cin -> 256) on the matrix cores, row softmax, expectation, optional prob write.
@@ -424,6 +441,9 @@ int cfp_depth_head_fused(const void* x, int x_ld, const void* w3, const float* s
  * -- the reference's own output type -- written by the kernel; HW % 4 == 0. */
 int cfp_bin_head_fused(const void* x, int x_ld, const void* w, const float* bias, const float* centers,
                        void* prob, float* pred, int B, int HW, int Cin, int dtype, cfp_stream_t stream);
+/* The same with the uncertainty planes (see cfp_bin_softmax_stats): stats [B][3][HW] f32, may be NULL. */
+int cfp_bin_head_fused_stats(const void* x, int x_ld, const void* w, const float* bias, const float* centers,
+                             void* prob, float* pred, float* stats, int B, int HW, int Cin, int dtype, cfp_stream_t stream);
 
 /* ---- training step pieces -------------------------------------------------- */
 

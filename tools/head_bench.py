@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """The adaptive-bins head at the bench shape (batch 8, 240x320 half-resolution map): separate kernels (3x3 conv -> ram -> fused
 conv_out + softmax) against the one-kernel head (csrc/head_fused.hip) with its exactness islands on / off; back-to-back inside a
-replayed HIP graph, alone and with 4 copies side by side (the throughput mode of bench.py)."""
+replayed HIP graph, alone and with 4 copies side by side (the throughput mode of bench.py).  Every head also with the per-pixel
+uncertainty planes (`stats`: std, entropy, pmax -- 3 float32 planes) on, with and without `prob`; a block for the default numerics
+(f32x3: conv_out + softmax in bin_head_x3_kernel) and, for context, the torch post-processing of a float32 `prob` that the planes replace."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -39,8 +41,36 @@ for dt in (torch.bfloat16, torch.float16):
                         (5, "probe: GEMM1 + GEMM2, no fetch")):
         rows.append((what, lambda probe=probe: ops.depth_head_fused(x, w3, sc, sh, wp0, bo, cen, prob, pred, B, H, W, ram_hilo=False, probe=probe)))
     rows.append(("no prob output", lambda: ops.depth_head_fused(x, w3, sc, sh, wp0, bo, cen, None, pred, B, H, W, ram_hilo=False)))
+    unc = torch.empty(B, 3, H * W, device=DEV)
+    rows.append(("one kernel, prob + stats", lambda: ops.depth_head_fused(x, w3, sc, sh, wp0, bo, cen, prob, pred, B, H, W, ram_hilo=False, stats=unc)))
+    rows.append(("one kernel, stats, no prob output", lambda: ops.depth_head_fused(x, w3, sc, sh, wp0, bo, cen, None, pred, B, H, W, ram_hilo=False, stats=unc)))
     streams = concurrent_streams(DEV, 4)
     for name, fn in rows:
         t = graph_time_us(fn, calls=6, replays=5)
         t4 = graph_time_us_concurrent(fn, streams, calls=6, replays=5)
         print(f"{str(dt):16s} {name:52s} alone {t:7.1f} us ({FL / t / 1e6:5.0f} TFLOP/s)   4 side by side {t4:7.1f} us per call")
+
+# the default numerics: float32 tensors, conv_out (f16x3 matrix math) + softmax + expectation in bin_head_x3_kernel, float32 prob
+x32 = ops.Act(torch.randn(M, 128, device=DEV), 0, 128)
+wx = ops.pack_w_x3((torch.randn(256, 128, device=DEV) * 0.3).contiguous())
+bo = torch.zeros(256, device=DEV)
+cen = torch.sort(torch.rand(B, 256, device=DEV) * 10, dim=1)[0].contiguous()
+prob32 = torch.empty(B, 256, H * W, device=DEV)
+pred = torch.empty(M, device=DEV)
+unc = torch.empty(B, 3, H * W, device=DEV)
+FL3 = 2.0 * M * 128 * 256
+for name, pr, st in (("prob", prob32, None), ("prob + stats", prob32, unc), ("no prob output", None, None), ("stats, no prob output", None, unc)):
+    fn = lambda pr=pr, st=st: ops.bin_head_fused(x32, wx, bo, cen, pr, pred, B, H * W, stats=st)
+    t = graph_time_us(fn, calls=6, replays=5)
+    t4 = graph_time_us_concurrent(fn, streams, calls=6, replays=5)
+    print(f"{'f32x3':16s} {'conv_out + softmax, ' + name:52s} alone {t:7.1f} us ({FL3 / t / 1e6:5.0f} TFLOP/s)   4 side by side {t4:7.1f} us per call")
+
+
+def torch_post():      # what a caller needs today for the same three maps: entropy, centred variance, max over a float32 prob
+    c = cen[:, :, None]
+    mu = (prob32 * c).sum(1, keepdim=True)
+    return torch.stack([(prob32 * (c - mu) ** 2).sum(1).sqrt(), -torch.xlogy(prob32, prob32).sum(1), prob32.max(1)[0]], 1)
+
+
+ops.bin_head_fused(x32, wx, bo, cen, prob32, pred, B, H * W)
+print(f"{'float32':16s} {'torch post-processing of prob (std, entropy, max)':52s} alone {graph_time_us(torch_post, calls=3, replays=3):7.1f} us")
