@@ -3,6 +3,9 @@
 Reference interface: `compute_errors(gt, pred)` (`src/utils/metrics.py:4-24`), `RunningAverageDict`
 (`src/utils/utils.py:14-41`) and the protocol around them in `evaluate_all.py:38-41,80-84` / `train.py:187-199`.
 The arithmetic is the HIP kernel behind `cfp_eval_metrics` (`csrc/metrics.hip`); nothing here computes on the CPU.
+
+`sparsification` / `RunningSparsification` have no counterpart in the reference: they rate the per-pixel uncertainty planes of the
+model (sparsification curves, AUSE, AURG; `cfp_unc_sparsification`, `csrc/unc_metrics.hip`), again without leaving the device.
 """
 from __future__ import annotations
 
@@ -74,3 +77,74 @@ class RunningAverageDict:
             avg = [(v + count * a) / (count + 1) for v, a in zip(r[:9], avg)]
             count += 1
         return dict(zip(KEYS, avg)) if count else {}
+
+
+RANKINGS = ("std", "entropy", "pmax", "oracle_rmse", "oracle_absrel")   # CFP_SPARS_* order; the first three are the planes of `unc`
+SPARS_METRICS = ("rmse", "absrel")
+
+
+def sparsification(pred: torch.Tensor, unc: torch.Tensor, gt: torch.Tensor, lo: float, hi: float, steps: int = 20,
+                   mode: int = EVALUATE_ALL, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """Sparsification curves of the three uncertainty planes against the two oracles (`cfp_unc_sparsification`, definition in
+    include/cfpnet_hip.h).  pred and gt as in `eval_metrics`, unc [B,3,Hp,Wp] f32 at the prediction's resolution ->
+    {"curves": [B,5,2,K] f64 (ranking in `RANKINGS` order, metric rmse / absrel, point k removes floor(k*N/K) pixels),
+     "ause": [B,3,2], "aurg": [B,3,2], "n_valid": [B]} on the device.  `out` is a dict of a previous call to write into.
+    No host synchronisation."""
+    if pred.dim() == 4:
+        pred = pred[:, 0]
+    if gt.dim() == 4:
+        gt = gt[:, 0]
+    if pred.dtype != torch.float32 or gt.dtype != torch.float32 or not pred.is_cuda or not gt.is_cuda:
+        raise ValueError("pred and gt must be float32 device tensors")
+    if unc.dtype != torch.float32 or not unc.is_cuda:
+        raise ValueError("unc must be a float32 device tensor")
+    pred, gt, unc = pred.contiguous(), gt.contiguous(), unc.contiguous()
+    B, Hp, Wp = pred.shape
+    if gt.shape[0] != B:
+        raise ValueError("batch sizes differ")
+    if tuple(unc.shape) != (B, 3, Hp, Wp):
+        raise ValueError(f"unc must be [B,3,Hp,Wp] = {(B, 3, Hp, Wp)}, got {tuple(unc.shape)}")
+    H, W = gt.shape[1:]
+    K = int(steps)
+    interp = int((Hp, Wp) != (H, W) or mode == VALIDATE)     # the rule of eval_metrics
+    nbytes = hip.load().cfp_unc_sparsification_ws_bytes(B, H, W, K)
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=pred.device)
+    if out is None:
+        out = {"curves": torch.empty(B, 5, 2, max(K, 0), dtype=torch.float64, device=pred.device),
+               "summary": torch.empty(B, 3, 2, 2, dtype=torch.float64, device=pred.device),
+               "n_valid": torch.empty(B, dtype=torch.float64, device=pred.device)}
+    hip.call("cfp_unc_sparsification", pred.data_ptr(), unc.data_ptr(), Hp, Wp, gt.data_ptr(), H, W, B, interp, mode, lo, hi, K,
+             ws.data_ptr(), nbytes, out["curves"].data_ptr(), out["summary"].data_ptr(), out["n_valid"].data_ptr(),
+             hip.current_stream())
+    out["ause"], out["aurg"] = out["summary"][..., 0], out["summary"][..., 1]
+    return out
+
+
+class RunningSparsification:
+    """Per-image means of the sparsification curves, AUSE and AURG over a data set: `update` takes the dict of `sparsification`
+    and keeps the rows on the device; `get_value` synchronises once, skips images without valid pixels or with NaN rows and returns
+    {"ause_rmse_std": ..., "ause_absrel_std": ..., ..., "aurg_absrel_pmax": ..., "curves": [5][2][K] nested lists}."""
+
+    def __init__(self):
+        self._rows = []
+
+    def update(self, res: Dict[str, torch.Tensor]) -> None:
+        B = res["n_valid"].shape[0]
+        self._rows.append(torch.cat([res["n_valid"].reshape(B, 1), res["summary"].reshape(B, 12), res["curves"].reshape(B, -1)], 1))
+
+    def get_value(self) -> Dict[str, object]:
+        if not self._rows:
+            return {}
+        rows = torch.cat(self._rows, 0).cpu()                    # the only host synchronisation
+        keep = (rows[:, 0] > 0) & ~torch.isnan(rows).any(1)
+        if not bool(keep.any()):
+            return {}
+        mean = rows[keep].mean(0).tolist()
+        res: Dict[str, object] = {}
+        for a, name in enumerate(("ause", "aurg")):
+            for m, metric in enumerate(SPARS_METRICS):
+                for u, plane in enumerate(RANKINGS[:3]):
+                    res[f"{name}_{metric}_{plane}"] = mean[1 + (u * 2 + m) * 2 + a]
+        K = (len(mean) - 13) // 10
+        res["curves"] = [[mean[13 + (r * 2 + m) * K: 13 + (r * 2 + m + 1) * K] for m in range(2)] for r in range(5)]
+        return res

@@ -13,6 +13,11 @@ Prints `Metrics: {...}` rounded to 3 decimals and the comma-joined line, like `e
 batch, `D/unc_<index of the batch's first image>.npy`: float32 `[B,3,h,w]`, planes std of the bin distribution (m), entropy (nats), largest
 bin probability.  The metrics and everything printed are the same with and without it.
 
+`--unc_metrics [--unc_steps K]` (K = 20 by default, 1..100) rates that uncertainty map against the ground truth on the device
+(`cfp_unc_sparsification`): sparsification curves of the three planes and of the two oracles at K removal fractions, AUSE and AURG per
+image, averaged over the images with valid pixels.  It prints a third line `Uncertainty: {...}` with the twelve means rounded to 4 decimals
+and, with `--save_dir D` given, writes `D/sparsification.json` with the mean curves.  The first two lines do not change.
+
 Differences on purpose: the xlsx report (openpyxl) is not written; `--synthetic N` evaluates N seeded synthetic samples
 when the dataset is not on the box (without it a missing `filenames_file_eval` is an error); weights are the
 deterministic key-addressed set unless `weights/<name>/<selected_epoch>.pt` (the reference's location) exists or
@@ -27,8 +32,12 @@ import torch
 
 
 def _pop(argv, flag, default=None, cast=str):
+    """Take `flag VALUE` out of argv (`cast=None`: a switch without a value -> True)."""
     if flag in argv:
         i = argv.index(flag)
+        if cast is None:
+            del argv[i]
+            return True
         v = cast(argv[i + 1])
         del argv[i:i + 2]
         return v
@@ -44,6 +53,9 @@ def main(argv=None):
     n_syn = _pop(argv, "--synthetic", 0, int)
     dtype = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32, "f32x3": "f32x3"}[_pop(argv, "--dtype", "f32x3")]
     bs = _pop(argv, "--batch", 8, int)
+    unc_metrics = _pop(argv, "--unc_metrics", False, None)
+    unc_steps = _pop(argv, "--unc_steps", 20, int)
+    save_spars = "--save_dir" in argv
     args = config.parse_args(argv) if argv else config.defaults()
     device = torch.device("cuda:0")
     if n_syn > 0:
@@ -68,15 +80,22 @@ def main(argv=None):
     if save_unc:
         import numpy as np
         os.makedirs(args.save_dir, exist_ok=True)
+    spars = metrics.RunningSparsification() if unc_metrics else None
     n_img, t0 = 0, time.perf_counter()
     with torch.no_grad():
         for img, dep, names in data.batches(samples, bs):
             inp, gt = build(img, dep)
-            if save_unc:
+            if unc_metrics:
+                _, pred, _, unc = model(inp, return_uncertainty=True, return_prob=False)
+            elif save_unc:
                 _, pred, _, unc = model(inp, return_uncertainty=True)
-                np.save(os.path.join(args.save_dir, f"unc_{n_img}.npy"), unc.cpu().numpy())
             else:
                 _, pred, _, _ = model(inp)
+            if save_unc:
+                np.save(os.path.join(args.save_dir, f"unc_{n_img}.npy"), unc.cpu().numpy())
+            if unc_metrics:
+                spars.update(metrics.sparsification(pred, unc, gt, float(args.min_depth), float(args.max_depth), steps=unc_steps,
+                                                    mode=metrics.EVALUATE_ALL))
             avg.update(metrics.eval_metrics(pred, gt, float(args.min_depth), float(args.max_depth), mode=metrics.EVALUATE_ALL))
             n_img += img.shape[0]
     torch.cuda.synchronize()
@@ -84,6 +103,15 @@ def main(argv=None):
     res = {k: round(v, 3) for k, v in avg.get_value().items()}
     print(f"Metrics: {res}")
     print(",".join(str(v) for v in res.values()))
+    if unc_metrics:
+        sp = spars.get_value()
+        print(f"Uncertainty: { {k: round(v, 4) for k, v in sp.items() if k != 'curves'} }")
+        if save_spars:
+            import json
+            os.makedirs(args.save_dir, exist_ok=True)
+            with open(os.path.join(args.save_dir, "sparsification.json"), "w") as f:
+                json.dump({"steps": unc_steps, "rankings": list(metrics.RANKINGS), "metrics": list(metrics.SPARS_METRICS),
+                           "curves": sp.get("curves", [])}, f)
     print(f"{n_img} images in {dt:.2f} s ({n_img / dt:.1f} images/s incl. host-side sample generation/decoding)", file=sys.stderr)
     return res
 

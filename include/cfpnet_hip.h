@@ -517,6 +517,35 @@ size_t cfp_eval_metrics_ws_bytes(int B);
 int cfp_eval_metrics(const float* pred, int Hp, int Wp, const float* gt, int H, int W, int B, int interpolate, int mode,
                      float lo, float hi, void* ws, size_t ws_bytes, double* out, cfp_stream_t stream);
 
+/* Sparsification curves, AUSE and AURG of the uncertainty planes (CFP_UNC_*) per image without leaving the device.
+ *   Inputs  pred [B,Hp,Wp] f32, unc [B,3,Hp,Wp] f32 (planes CFP_UNC_STD / ENTROPY / PMAX), gt [B,H,W] f32, bounds lo < hi,
+ *           mode 0 or 1 exactly as cfp_eval_metrics (clip / bilinear order, nan -> lo in mode 1, valid pixels lo < gt < hi),
+ *           steps = K with 1 <= K <= 100.
+ *   Protocol  the prediction v at a valid pixel is what cfp_eval_metrics evaluates there; each uncertainty plane is brought to
+ *           H x W with the same align-corners bilinear taps, without a clip (interpolate = 0: read directly, equal sizes required).
+ *   Terms   float32: d = g - v, t0 = d*d, t1 = fabsf(d)/g.
+ *   Scores  float32, a larger score is removed first: s0 = std, s1 = entropy, s2 = 1 - pmax, s3 = t0 (the RMSE oracle),
+ *           s4 = t1 (the abs-rel oracle); rankings are numbered CFP_SPARS_*.  Float ordering with -0 == +0 and NaN above +inf
+ *           (all NaNs tie).
+ *   Curves  for ranking r, point k = 0..K-1 and N valid pixels the kept count is n_k = N - floor(k*N/K) (integers, n_k >= 1 when
+ *           N >= 1) and the kept set is the n_k pixels with the smallest s_r.  A group of exactly equal scores that straddles the
+ *           boundary with t of its c members kept contributes t/c of the group's sums, so no value depends on a tie-break or on
+ *           pixel order.  With S_m the float64 sum of t_m over the kept set:
+ *             curves[b][r][0][k] = sqrt(S_0 / n_k)  (RMSE)      curves[b][r][1][k] = S_1 / n_k  (abs-rel)
+ *   Summary for the uncertainty rankings u = 0..2 and metric m, with e0 = curve[.][m][0] (the same for every ranking) and
+ *           o = 3 + m:  AUSE = summary[b][u][m][0] = mean_k (curve[u][m][k] - curve[o][m][k]) / e0
+ *                       AURG = summary[b][u][m][1] = mean_k (e0 - curve[u][m][k]) / e0
+ *   n_valid[b] = N.  If N == 0 or e0 == 0 every curve and summary value of that image is NaN.
+ * The ranking is exact on the full float32 score (radix select, no quantised keys); the sums are exact integer accumulations
+ * rounded to float64 once, so two calls on the same tensors give identical bits.  No host synchronisation, no global atomics;
+ * everything runs on `stream` in the caller's workspace (cfp_unc_sparsification_ws_bytes bytes, 8-byte aligned). */
+enum { CFP_SPARS_STD = 0, CFP_SPARS_ENTROPY, CFP_SPARS_PMAX, CFP_SPARS_ORACLE_RMSE, CFP_SPARS_ORACLE_ABSREL };
+size_t cfp_unc_sparsification_ws_bytes(int B, int H, int W, int steps);
+int cfp_unc_sparsification(const float* pred, const float* unc, int Hp, int Wp, const float* gt, int H, int W, int B,
+                           int interpolate, int mode, float lo, float hi, int steps, void* ws, size_t ws_bytes,
+                           double* curves /* [B][5][2][steps] */, double* summary /* [B][3][2][2]: AUSE, AURG */,
+                           double* n_valid /* [B] */, cfp_stream_t stream);
+
 /* ---- training-step kernels: backward of the dense convolution, batch-statistics BatchNorm --------------------------
  * (the training row of SURVEY.md section 8: cfpnet_amd/autograd_hip.py chains them into the backward of the whole network) */
 
