@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import synthetic
-from .geometry import centered_zone_rects, collate_patch_info, patch_info_from_rect_data
+from .geometry import central_zone_block, centered_zone_rects, collate_patch_info, patch_info_from_rect_data
 from .tof import TofSimulator, zone_layout
 
 IMAGENET_MEAN = np.array([0.485, 0.456, 0.406], dtype=np.float32)
@@ -153,11 +153,19 @@ def batches(samples, batch_size: int) -> Iterator[tuple]:
 
 
 class EvalInputBuilder:
-    """image/depth batch -> the `input_data` dict of `Deltar.forward` (`evaluate_all.py:55-65`), ToF branch on the GPU."""
+    """image/depth batch -> the `input_data` dict of `Deltar.forward` (`evaluate_all.py:55-65`), ToF branch on the GPU.
+
+    `args.zone_type` (8x8 by default) = 6x6 / 4x4 / 2x2 keeps the central block of the simulated 8x8 grid, row-major, in `hist_data`,
+    `rect_data` and `mask` (zjuL5.py:107-132); `patch_info` then comes from the kept rectangles.  The block is gathered on the
+    device from the full simulation, so it equals that simulation's entries bit for bit."""
 
     def __init__(self, args, device="cuda:0"):
         self.args = args
         self.device = torch.device(device)
+        self.zone_type = str(getattr(args, "zone_type", "8x8") or "8x8")
+        keep = central_zone_block(self.zone_type)                # raises on an unknown value
+        self._keep_np = None if self.zone_type == "8x8" else keep
+        self._keep = None if self.zone_type == "8x8" else torch.from_numpy(keep).to(self.device)
         cfg = _as_mode(args, "online_eval")
         self.sim = TofSimulator(cfg, self.device)
         self.cfg = cfg
@@ -168,6 +176,8 @@ class EvalInputBuilder:
         if key not in self._pinfo:
             zn, zp, sy0, sx0 = zone_layout(self.cfg, H, W)
             rects = centered_zone_rects(H, W, zn, zp)
+            if self._keep_np is not None:
+                rects = rects[self._keep_np]
             pi = collate_patch_info([patch_info_from_rect_data(rects, (H, W))] * B)
             info = {s: {k: torch.from_numpy(v) for k, v in pi[s].items()} for s in (4, 8, 16)}
             info["zone_num"] = torch.from_numpy(pi["zone_num"])
@@ -180,6 +190,8 @@ class EvalInputBuilder:
         dep = depth.to(dev, dtype=torch.float32, non_blocking=True)
         B, _, H, W = img.shape
         sim = self.sim.simulate(dep)
+        if self._keep is not None:
+            sim = {k: sim[k].index_select(1, self._keep) for k in ("hist_data", "rect_data", "mask")}
         return {"rgb": img, "additional": {"hist_data": sim["hist_data"], "rect_data": sim["rect_data"], "mask": sim["mask"],
                                            "patch_info": self.patch_info(B, H, W)}}, dep
 

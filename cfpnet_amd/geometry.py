@@ -102,6 +102,21 @@ def centered_zone_rects(height: int, width: int, zone_num: int, zone_px: int, of
     return rects
 
 
+# `--zone_type`: the central block of the sensor's 8x8 grid that an evaluation keeps (zjuL5.py:107-132, nyu.py:166-177)
+ZONE_TYPES = {"8x8": (0, 8), "6x6": (1, 7), "4x4": (2, 6), "2x2": (3, 5)}
+
+
+def central_zone_block(zone_type: str, zone_num: int = 8) -> np.ndarray:
+    """Row-major indices into the zone_num x zone_num grid of the zones `--zone_type` keeps (`valid_mask[a:b, a:b]` of
+    zjuL5.py:112-132 flattened), int64.  Any value other than 8x8 / 6x6 / 4x4 / 2x2 is an error."""
+    if zone_type not in ZONE_TYPES:
+        raise ValueError(f"zone_type must be one of {', '.join(ZONE_TYPES)}, got {zone_type!r}")
+    if zone_num != 8:
+        raise ValueError("zone_type subsets the 8x8 grid of the sensor")
+    a, b = ZONE_TYPES[zone_type]
+    return np.arange(zone_num * zone_num, dtype=np.int64).reshape(zone_num, zone_num)[a:b, a:b].reshape(-1)
+
+
 def _get(info, key):
     """patch_info is keyed by int 4/8/16; the reference indexes it with the float 640/W
     (fusion.py:41,71), which works because hash(4.0) == hash(4)."""

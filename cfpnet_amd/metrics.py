@@ -6,10 +6,15 @@ The arithmetic is the HIP kernel behind `cfp_eval_metrics` (`csrc/metrics.hip`);
 
 `sparsification` / `RunningSparsification` have no counterpart in the reference: they rate the per-pixel uncertainty planes of the
 model (sparsification curves, AUSE, AURG; `cfp_unc_sparsification`, `csrc/unc_metrics.hip`), again without leaving the device.
+
+`region_metrics` / `RunningRegionAverage` split the nine metrics by where a pixel lies relative to the ToF zones (the reference's
+`my_mask`, `src/dataloader/nyu.py:182-187`, and its `--zone_area_only` / `--outside_zone_area_only` flags) and by depth range
+(`cfp_eval_metrics_regions`, `csrc/region_metrics.hip`).
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+import ctypes
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
@@ -147,4 +152,99 @@ class RunningSparsification:
                     res[f"{name}_{metric}_{plane}"] = mean[1 + (u * 2 + m) * 2 + a]
         K = (len(mean) - 13) // 10
         res["curves"] = [[mean[13 + (r * 2 + m) * K: 13 + (r * 2 + m + 1) * K] for m in range(2)] for r in range(5)]
+        return res
+
+
+REGIONS = ("all", "fov_in", "fov_out", "zone_valid", "zone_invalid")     # CFP_REGION_* order
+MAX_RANGE_EDGES = 7
+
+
+def range_labels(range_edges: Sequence[float] = ()) -> Tuple[str, ...]:
+    """Labels of the range axis of `region_metrics`: () -> ("all",); (2, 4) -> ("all", "<2", "2-4", ">=4")."""
+    e = [f"{float(v):g}" for v in range_edges]
+    if not e:
+        return ("all",)
+    return ("all", f"<{e[0]}") + tuple(f"{a}-{b}" for a, b in zip(e[:-1], e[1:])) + (f">={e[-1]}",)
+
+
+def region_metrics(pred: torch.Tensor, gt: torch.Tensor, lo: float, hi: float, rect_data: torch.Tensor, mask: torch.Tensor,
+                   range_edges: Sequence[float] = (), mode: int = EVALUATE_ALL, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The metrics of `eval_metrics` per region and depth range (`cfp_eval_metrics_regions`, definition in include/cfpnet_hip.h).
+    pred and gt as in `eval_metrics`; rect_data [B,Z,4] f32 (sy, sx, ey, ex) and mask [B,Z] bool / uint8 on the device, as the model
+    receives them; range_edges: up to 7 finite, strictly increasing depths in metres -> [B,5,Q,10] f64 on the device, regions in
+    `REGIONS` order, ranges in `range_labels(range_edges)` order (Q = 1 without edges), then the nine metrics in `KEYS` order and
+    the pixel count; a segment without a valid pixel holds NaN metrics and count 0.  No host synchronisation."""
+    if pred.dim() == 4:
+        pred = pred[:, 0]
+    if gt.dim() == 4:
+        gt = gt[:, 0]
+    if pred.dtype != torch.float32 or gt.dtype != torch.float32 or not pred.is_cuda or not gt.is_cuda:
+        raise ValueError("pred and gt must be float32 device tensors")
+    if rect_data.dtype != torch.float32 or not rect_data.is_cuda or mask.dtype not in (torch.bool, torch.uint8) or not mask.is_cuda:
+        raise ValueError("rect_data must be a float32 and mask a bool / uint8 device tensor")
+    if pred.dim() != 3 or gt.dim() != 3:
+        raise ValueError("pred and gt must be [B,H,W] or [B,1,H,W]")
+    pred, gt, rect_data, mask = pred.contiguous(), gt.contiguous(), rect_data.contiguous(), mask.contiguous()
+    B, Hp, Wp = pred.shape
+    if gt.shape[0] != B:
+        raise ValueError("batch sizes differ")
+    if rect_data.dim() != 3 or rect_data.shape[0] != B or rect_data.shape[2] != 4 or rect_data.shape[1] < 1:
+        raise ValueError(f"rect_data must be [B,Z,4] with B = {B}, got {tuple(rect_data.shape)}")
+    Z = rect_data.shape[1]
+    if tuple(mask.shape) != (B, Z):
+        raise ValueError(f"mask must be [B,Z] = {(B, Z)}, got {tuple(mask.shape)}")
+    edges = [float(v) for v in range_edges]
+    E = len(edges)
+    if E > MAX_RANGE_EDGES:
+        raise ValueError(f"at most {MAX_RANGE_EDGES} range edges, got {E}")
+    Q = 1 if E == 0 else E + 2
+    H, W = gt.shape[1:]
+    interp = int((Hp, Wp) != (H, W) or mode == VALIDATE)     # the rule of eval_metrics
+    nbytes = hip.load().cfp_eval_metrics_regions_ws_bytes(B)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=pred.device)
+    if out is None:
+        out = torch.empty(B, 5, Q, 10, dtype=torch.float64, device=pred.device)
+    elif tuple(out.shape) != (B, 5, Q, 10) or out.dtype != torch.float64 or not out.is_cuda or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float64 device tensor {(B, 5, Q, 10)}")
+    host_edges = (ctypes.c_float * max(E, 1))(*edges)      # the one host pointer of the call: copied into the kernel arguments
+    hip.call("cfp_eval_metrics_regions", pred.data_ptr(), Hp, Wp, gt.data_ptr(), H, W, B, interp, mode, lo, hi, rect_data.data_ptr(),
+             mask.data_ptr(), Z, host_edges, E, ws.data_ptr(), nbytes, out.data_ptr(), hip.current_stream())
+    return out
+
+
+class RunningRegionAverage:
+    """`RunningAverageDict` per (region, range): `update` takes the [B,5,Q,10] tensor of `region_metrics` and keeps it on the device;
+    `get_value` synchronises once and applies the reference's recurrence avg <- (v + count*avg)/(count+1) image by image, skipping
+    -- for that segment only -- the images whose count there is 0 (evaluate_all.py:83).  It returns
+    {region: {range label: {metric: mean}}} with an empty dict for a segment no image contributed to; `image_counts` then holds
+    {region: {range label: number of images averaged}}."""
+
+    def __init__(self, range_edges: Sequence[float] = ()):
+        self.labels = range_labels(range_edges)
+        self.image_counts: Dict[str, Dict[str, int]] = {}
+        self._rows = []
+
+    def update(self, rows: torch.Tensor) -> None:
+        if rows.dim() != 4 or tuple(rows.shape[1:]) != (5, len(self.labels), 10):
+            raise ValueError(f"rows must be [B,5,{len(self.labels)},10], got {tuple(rows.shape)}")
+        self._rows.append(rows)
+
+    def get_value(self) -> Dict[str, Dict[str, Dict[str, float]]]:
+        if not self._rows:
+            return {}
+        rows = torch.cat(self._rows, 0).cpu().tolist()            # the only host synchronisation
+        res: Dict[str, Dict[str, Dict[str, float]]] = {}
+        self.image_counts = {}
+        for ri, region in enumerate(REGIONS):
+            res[region], self.image_counts[region] = {}, {}
+            for qi, label in enumerate(self.labels):
+                avg, count = [0.0] * 9, 0
+                for img in rows:
+                    r = img[ri][qi]
+                    if not r[9] > 0:
+                        continue
+                    avg = [(v + count * a) / (count + 1) for v, a in zip(r[:9], avg)]
+                    count += 1
+                res[region][label] = dict(zip(KEYS, avg)) if count else {}
+                self.image_counts[region][label] = count
         return res

@@ -18,6 +18,14 @@ bin probability.  The metrics and everything printed are the same with and witho
 image, averaged over the images with valid pixels.  It prints a third line `Uncertainty: {...}` with the twelve means rounded to 4 decimals
 and, with `--save_dir D` given, writes `D/sparsification.json` with the mean curves.  The first two lines do not change.
 
+`--zone_type 6x6|4x4|2x2` feeds the model the central block of the 8x8 zone grid only (the reference's zjuL5 loader).  `--zone_area_only` /
+`--outside_zone_area_only` compute the two metric lines over the pixels inside / outside the field of view of the kept zones (the reference's
+`my_mask`: the rectangle spanned by the first and the last zone); images without a valid pixel there are skipped; giving both is an error.
+`--region_metrics [--range_edges 2,4]` splits the metrics by region (all, fov_in, fov_out, zone_valid, zone_invalid) and by ground-truth depth
+range on the device (`cfp_eval_metrics_regions`); it prints one more line `Regions: {...}` (after `Uncertainty:` when that is present) and, with
+`--save_dir D` given, writes `D/regions.json` with the labels, the table and the image counts.  With none of these flags the code path and the
+output are what they were.
+
 Differences on purpose: the xlsx report (openpyxl) is not written; `--synthetic N` evaluates N seeded synthetic samples
 when the dataset is not on the box (without it a missing `filenames_file_eval` is an error); weights are the
 deterministic key-addressed set unless `weights/<name>/<selected_epoch>.pt` (the reference's location) exists or
@@ -45,7 +53,7 @@ def _pop(argv, flag, default=None, cast=str):
 
 
 def main(argv=None):
-    from cfpnet_amd import config, data, metrics
+    from cfpnet_amd import config, data, geometry, metrics
     from cfpnet_amd.deltar import make_model
     from cfpnet_amd.model_io import load_weights
 
@@ -55,8 +63,17 @@ def main(argv=None):
     bs = _pop(argv, "--batch", 8, int)
     unc_metrics = _pop(argv, "--unc_metrics", False, None)
     unc_steps = _pop(argv, "--unc_steps", 20, int)
+    want_regions = _pop(argv, "--region_metrics", False, None)
+    range_edges = _pop(argv, "--range_edges", (), lambda v: tuple(float(x) for x in v.split(",") if x.strip()))
     save_spars = "--save_dir" in argv
     args = config.parse_args(argv) if argv else config.defaults()
+    area_in, area_out = bool(getattr(args, "zone_area_only", False)), bool(getattr(args, "outside_zone_area_only", False))
+    if area_in and area_out:
+        raise ValueError("--zone_area_only and --outside_zone_area_only exclude each other")
+    area = metrics.REGIONS.index("fov_in") if area_in else metrics.REGIONS.index("fov_out") if area_out else None
+    if range_edges and not want_regions:
+        raise ValueError("--range_edges needs --region_metrics")
+    geometry.central_zone_block(str(getattr(args, "zone_type", "8x8")))      # an unknown --zone_type is an error before anything is built
     device = torch.device("cuda:0")
     if n_syn > 0:
         samples = data.SyntheticEvalSamples(n_syn, 480, 640)
@@ -81,6 +98,7 @@ def main(argv=None):
         import numpy as np
         os.makedirs(args.save_dir, exist_ok=True)
     spars = metrics.RunningSparsification() if unc_metrics else None
+    regions = metrics.RunningRegionAverage(range_edges) if want_regions else None
     n_img, t0 = 0, time.perf_counter()
     with torch.no_grad():
         for img, dep, names in data.batches(samples, bs):
@@ -96,7 +114,16 @@ def main(argv=None):
             if unc_metrics:
                 spars.update(metrics.sparsification(pred, unc, gt, float(args.min_depth), float(args.max_depth), steps=unc_steps,
                                                     mode=metrics.EVALUATE_ALL))
-            avg.update(metrics.eval_metrics(pred, gt, float(args.min_depth), float(args.max_depth), mode=metrics.EVALUATE_ALL))
+            if want_regions or area is not None:
+                add = inp["additional"]
+                rows = metrics.region_metrics(pred, gt, float(args.min_depth), float(args.max_depth), add["rect_data"], add["mask"],
+                                              range_edges, mode=metrics.EVALUATE_ALL)
+                if want_regions:
+                    regions.update(rows)
+            if area is not None:
+                avg.update(rows[:, area, 0])             # the region's "all depths" row; images without a valid pixel there are skipped
+            else:
+                avg.update(metrics.eval_metrics(pred, gt, float(args.min_depth), float(args.max_depth), mode=metrics.EVALUATE_ALL))
             n_img += img.shape[0]
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -112,6 +139,17 @@ def main(argv=None):
             with open(os.path.join(args.save_dir, "sparsification.json"), "w") as f:
                 json.dump({"steps": unc_steps, "rankings": list(metrics.RANKINGS), "metrics": list(metrics.SPARS_METRICS),
                            "curves": sp.get("curves", [])}, f)
+    if want_regions:
+        rv = regions.get_value()
+        print(f"Regions: { {r: {q: {k: round(v, 3) for k, v in m.items()} for q, m in t.items()} for r, t in rv.items()} }")
+        if save_spars:
+            import json
+            os.makedirs(args.save_dir, exist_ok=True)
+            with open(os.path.join(args.save_dir, "regions.json"), "w") as f:
+                json.dump({"regions": list(metrics.REGIONS), "ranges": list(regions.labels), "range_edges": list(range_edges),
+                           "metrics": list(metrics.KEYS), "zone_type": str(getattr(args, "zone_type", "8x8")),
+                           "table": [[[rv[r][q].get(k) for k in metrics.KEYS] for q in regions.labels] for r in metrics.REGIONS],
+                           "images": [[regions.image_counts[r][q] for q in regions.labels] for r in metrics.REGIONS]}, f)
     print(f"{n_img} images in {dt:.2f} s ({n_img / dt:.1f} images/s incl. host-side sample generation/decoding)", file=sys.stderr)
     return res
 

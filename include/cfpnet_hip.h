@@ -546,6 +546,34 @@ int cfp_unc_sparsification(const float* pred, const float* unc, int Hp, int Wp, 
                            double* curves /* [B][5][2][steps] */, double* summary /* [B][3][2][2]: AUSE, AURG */,
                            double* n_valid /* [B] */, cfp_stream_t stream);
 
+/* The metrics of cfp_eval_metrics split by region and by depth range, per image, in one pass, without leaving the device.
+ *   Inputs  pred, gt, interpolate, mode, lo < hi exactly as cfp_eval_metrics: the float32 prediction evaluated at a pixel and the
+ *           validity rule lo < gt < hi are the same, bit for bit.  rect [B,Z,4] f32 (sy, sx, ey, ex) and mask [B,Z] u8 on the
+ *           device, read per image (the model's rect_data / mask inputs).
+ *   Regions the FoV rectangle is the reference's `my_mask` (src/dataloader/nyu.py:182-187): aa = max(0, trunc(rect[b][0][0])),
+ *           bb = max(0, trunc(rect[b][0][1])), cc = min(H, trunc(rect[b][Z-1][2])), dd = min(W, trunc(rect[b][Z-1][3])); pixel
+ *           (y, x) is inside iff aa <= y < cc && bb <= x < dd (empty if cc <= aa or dd <= bb; no negative-slice wrap-around).
+ *             CFP_REGION_ALL           every valid pixel
+ *             CFP_REGION_FOV_IN        inside the FoV rectangle            CFP_REGION_FOV_OUT  not inside it
+ *             CFP_REGION_ZONE_VALID    inside the FoV rectangle and inside the rectangle of some zone z with mask[b][z] != 0
+ *                                      (sy <= y < ey && sx <= x < ex, compared in float)
+ *             CFP_REGION_ZONE_INVALID  inside the FoV rectangle and not ZONE_VALID (a dropped zone, or a gap between zones)
+ *   Ranges  n_edges = E, 0 <= E <= 7; `edges` is a HOST array of E finite, strictly increasing floats -- the one host pointer of the
+ *           call, copied into the kernel arguments (may be NULL when E == 0).  A pixel's range index is the number of edges e with
+ *           gt >= e in float32: E + 1 ranges.
+ *   out [B][5][Q][10] f64 (device), Q = 1 if E == 0 else E + 2: region CFP_REGION_*, then q = 0 "all depths" and q = 1 + r range r,
+ *           then the ten values of cfp_eval_metrics (nine metrics, pixel count).  A segment without a valid pixel has NaN metrics
+ *           and count 0.
+ * Every valid pixel is accumulated into exactly one cell (zone class x range); every entry of `out` is finalised from sums of cell
+ * sums.  Per-pixel terms f32, sums f64, no floating-point atomics, fixed summation order: two calls on the same tensors give identical
+ * bits.  No host synchronisation; workspace of cfp_eval_metrics_regions_ws_bytes(B) bytes, 8-byte aligned. */
+enum { CFP_REGION_ALL = 0, CFP_REGION_FOV_IN, CFP_REGION_FOV_OUT, CFP_REGION_ZONE_VALID, CFP_REGION_ZONE_INVALID };
+size_t cfp_eval_metrics_regions_ws_bytes(int B);
+int cfp_eval_metrics_regions(const float* pred, int Hp, int Wp, const float* gt, int H, int W, int B, int interpolate, int mode,
+                             float lo, float hi, const float* rect /* [B][Z][4] */, const unsigned char* mask /* [B][Z] */, int Z,
+                             const float* edges /* host, [n_edges] */, int n_edges, void* ws, size_t ws_bytes,
+                             double* out /* [B][5][Q][10] */, cfp_stream_t stream);
+
 /* ---- training-step kernels: backward of the dense convolution, batch-statistics BatchNorm --------------------------
  * (the training row of SURVEY.md section 8: cfpnet_amd/autograd_hip.py chains them into the backward of the whole network) */
 
