@@ -83,6 +83,9 @@ SIGNATURES = {
     "cfp_unc_sparsification": (_i, [_p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _f, _f, _i, _p, _sz, _p, _p, _p, _p]),
     "cfp_eval_metrics_regions_ws_bytes": (_sz, [_i]),
     "cfp_eval_metrics_regions": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _i, _f, _f, _p, _p, _i, C.POINTER(C.c_float), _i, _p, _sz, _p, _p]),
+    "cfp_depth_unproject": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p]),
+    "cfp_points_compact_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "cfp_points_compact": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _p, _i, _i, _ll, _f, _f, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "cfp_conv2d_wgrad_ws_bytes": (_sz, [_i, _i, _i]),
     "cfp_grad_absmax": (_i, [_p, _i, _ll, _i, _p, _p]),
     "cfp_grad_scale": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p]),

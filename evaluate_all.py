@@ -26,6 +26,14 @@ range on the device (`cfp_eval_metrics_regions`); it prints one more line `Regio
 `--save_dir D` given, writes `D/regions.json` with the labels, the table and the image counts.  With none of these flags the code path and the
 output are what they were.
 
+`--save_points` back-projects every prediction to 3-D points in the camera frame on the device (`cfp_depth_unproject`, the depth being the
+clipped, bilinearly enlarged prediction the metrics evaluate), keeps the pixels of every `--points_stride N`-th row and column (N = 2 by
+default) whose depth lies strictly inside (min_depth, max_depth) and -- with `--points_max_std S` -- whose predicted standard deviation (plane
+0 of the uncertainty map, metres) is at most S (`cfp_points_compact`), and writes `D/points_<image index>.ply` per image into `--save_dir D`
+(default `tmp`): binary PLY with x y z, the surface normal with `--points_normals`, and the de-normalised RGB.  `--intrinsics fx,fy,cx,cy`
+(pixels of the full-resolution image) defaults to the ZJU-L5 sensor's.  One more stderr line reports the mean number of points kept; the
+`Metrics:` lines do not change.  The `--points_*` switches and `--intrinsics` without `--save_points` are an error.
+
 Differences on purpose: the xlsx report (openpyxl) is not written; `--synthetic N` evaluates N seeded synthetic samples
 when the dataset is not on the box (without it a missing `filenames_file_eval` is an error); weights are the
 deterministic key-addressed set unless `weights/<name>/<selected_epoch>.pt` (the reference's location) exists or
@@ -52,6 +60,13 @@ def _pop(argv, flag, default=None, cast=str):
     return default
 
 
+def _intrinsics(v):
+    k = tuple(float(x) for x in v.split(","))
+    if len(k) != 4:
+        raise ValueError(f"--intrinsics takes fx,fy,cx,cy, got '{v}'")
+    return k
+
+
 def main(argv=None):
     from cfpnet_amd import config, data, geometry, metrics
     from cfpnet_amd.deltar import make_model
@@ -65,6 +80,13 @@ def main(argv=None):
     unc_steps = _pop(argv, "--unc_steps", 20, int)
     want_regions = _pop(argv, "--region_metrics", False, None)
     range_edges = _pop(argv, "--range_edges", (), lambda v: tuple(float(x) for x in v.split(",") if x.strip()))
+    save_points = _pop(argv, "--save_points", False, None)
+    points_stride = _pop(argv, "--points_stride", None, int)
+    points_max_std = _pop(argv, "--points_max_std", None, float)
+    points_normals = _pop(argv, "--points_normals", False, None)
+    intrinsics = _pop(argv, "--intrinsics", None, _intrinsics)
+    if not save_points and (points_stride is not None or points_max_std is not None or points_normals or intrinsics is not None):
+        raise ValueError("--points_stride, --points_max_std, --points_normals and --intrinsics need --save_points")
     save_spars = "--save_dir" in argv
     args = config.parse_args(argv) if argv else config.defaults()
     area_in, area_out = bool(getattr(args, "zone_area_only", False)), bool(getattr(args, "outside_zone_area_only", False))
@@ -99,13 +121,20 @@ def main(argv=None):
         os.makedirs(args.save_dir, exist_ok=True)
     spars = metrics.RunningSparsification() if unc_metrics else None
     regions = metrics.RunningRegionAverage(range_edges) if want_regions else None
+    if save_points:
+        from cfpnet_amd import pointcloud
+        os.makedirs(args.save_dir, exist_ok=True)
+        rgb_mean = torch.from_numpy(data.IMAGENET_MEAN).to(device)[None, :, None, None]
+        rgb_std = torch.from_numpy(data.IMAGENET_STD).to(device)[None, :, None, None]
+        n_points = 0
+    want_std = save_points and points_max_std is not None
     n_img, t0 = 0, time.perf_counter()
     with torch.no_grad():
         for img, dep, names in data.batches(samples, bs):
             inp, gt = build(img, dep)
             if unc_metrics:
                 _, pred, _, unc = model(inp, return_uncertainty=True, return_prob=False)
-            elif save_unc:
+            elif save_unc or want_std:
                 _, pred, _, unc = model(inp, return_uncertainty=True)
             else:
                 _, pred, _, _ = model(inp)
@@ -124,6 +153,15 @@ def main(argv=None):
                 avg.update(rows[:, area, 0])             # the region's "all depths" row; images without a valid pixel there are skipped
             else:
                 avg.update(metrics.eval_metrics(pred, gt, float(args.min_depth), float(args.max_depth), mode=metrics.EVALUATE_ALL))
+            if save_points:
+                pc = pointcloud.point_cloud(pred, intrinsics or pointcloud.ZJUL5_INTRINSICS, size=gt.shape[-2:], lo=float(args.min_depth),
+                                            hi=float(args.max_depth), depth_range=(float(args.min_depth), float(args.max_depth)),
+                                            unc=unc if want_std else None, unc_range=(float("-inf"), points_max_std if want_std else float("inf")),
+                                            stride=2 if points_stride is None else points_stride, normals=points_normals,
+                                            colors=inp["rgb"] * rgb_std + rgb_mean)
+                for b, one in enumerate(pc.split()):
+                    n_points += pointcloud.write_ply(os.path.join(args.save_dir, f"points_{n_img + b}.ply"), one["points"], one["normals"],
+                                                     one["colors"])
             n_img += img.shape[0]
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -150,6 +188,8 @@ def main(argv=None):
                            "metrics": list(metrics.KEYS), "zone_type": str(getattr(args, "zone_type", "8x8")),
                            "table": [[[rv[r][q].get(k) for k in metrics.KEYS] for q in regions.labels] for r in metrics.REGIONS],
                            "images": [[regions.image_counts[r][q] for q in regions.labels] for r in metrics.REGIONS]}, f)
+    if save_points:
+        print(f"points: {n_points / max(n_img, 1):.1f} kept per image on average, written to {args.save_dir}/points_<index>.ply", file=sys.stderr)
     print(f"{n_img} images in {dt:.2f} s ({n_img / dt:.1f} images/s incl. host-side sample generation/decoding)", file=sys.stderr)
     return res
 

@@ -574,6 +574,52 @@ int cfp_eval_metrics_regions(const float* pred, int Hp, int Wp, const float* gt,
                              const float* edges /* host, [n_edges] */, int n_edges, void* ws, size_t ws_bytes,
                              double* out /* [B][5][Q][10] */, cfp_stream_t stream);
 
+/* Back-projection of the prediction to 3-D points in the camera frame, with surface normals, without leaving the device: the step
+ * after the depth map for whoever consumes ToF depth completion (robotics, AR, reconstruction).
+ *   Inputs  pred [B,Hp,Wp] f32 (device); H, W, interpolate, lo < hi as cfp_eval_metrics in mode 0; K [B][4] f32 ON THE DEVICE: the
+ *           pinhole intrinsics (fx, fy, cx, cy) in pixels of the H x W grid, per image -- the numbers the reference's ZJU-L5 loader
+ *           carries as K_list and never uses (src/dataloader/zjuL5.py:66-71).  fx and fy cannot be checked without a
+ *           synchronisation: the caller guarantees that all four are finite and that fx, fy are not 0.
+ *   Depth   d(x, y) is the float32 value cfp_eval_metrics evaluates at that pixel in mode 0 (evaluate_all.py:40-41): clip to [lo, hi] at
+ *           model resolution, then the align-corners bilinear blend, a dimension of unchanged size read twice with weights (1, 0); with
+ *           interpolate = 0 the sizes must be equal and d is the clipped value.  One implementation (csrc/metrics_pred.h): bit for bit.
+ *   Point   float32, in this order of operations (no fused multiply-add):
+ *             rx = ((float)x - cx) / fx     ry = ((float)y - cy) / fy     P(x, y) = (rx * d, ry * d, d)
+ *           Plain arithmetic: a NaN depth gives a NaN point.
+ *   Normal  from the clamped neighbours x0 = max(x - 1, 0), x1 = min(x + 1, W - 1), k = x1 - x0, xm = 0.5f * (x0 + x1), with
+ *           d0 = d(x0, y), d1 = d(x1, y), in a form without the cancellation of a point difference:
+ *             T_x = (d1 - d0) * r_m + (d1 + d0) * (0.5f * k / fx) * e_1      r_m = ((xm - cx) / fx, ry, 1),  e_1 = (1, 0, 0)
+ *           and T_y likewise in y (y0, y1, ym, second unit vector, r_m = (rx, (ym - cy) / fy, 1)).  In exact arithmetic
+ *           T_x = P(x1, y) - P(x0, y).  n = normalize(T_y x T_x): for fx, fy > 0 it faces the camera (n . P < 0), a fronto-parallel
+ *           wall gives (0, 0, -1).  If one of the five depths involved (the pixel's own and its four neighbours') is not finite, or the
+ *           length of the cross product is 0 or not finite, the normal is (0, 0, 0); so every normal is 0 when H == 1 or W == 1.
+ *   Outputs points [B,H,W,3] f32; normals [B,H,W,3] f32 or NULL (not computed).
+ * One launch, no host synchronisation, no allocation, no workspace. */
+int cfp_depth_unproject(const float* pred, int Hp, int Wp, int H, int W, int B, int interpolate, float lo, float hi,
+                        const float* K /* device, [B][4]: fx fy cx cy */, float* points /* [B][H][W][3] */,
+                        float* normals /* [B][H][W][3] or NULL */, cfp_stream_t stream);
+
+/* Order-preserving selection of the points of such a map (stream compaction) by grid stride, range and uncertainty, per image, without
+ * a host synchronisation.
+ *   Inputs  points [B,H,W,3] f32, normals [B,H,W,3] f32 or NULL; stride >= 1; z_near < z_far; an optional uncertainty plane: unc
+ *           (NULL: none) points to image 0's plane of Hu x Wu f32, image b's lies unc_stride ELEMENTS further per image (a plane of the
+ *           model's [B,3,h,w] uncertainty tensor: stride 3 * h * w), with the closed interval unc_lo <= unc_hi.  When Hu x Wu differs
+ *           from H x W the plane is brought to the H x W grid with the align-corners bilinear taps of the prediction, without a clip
+ *           (as cfp_unc_sparsification does); otherwise it is read directly.
+ *   Kept    pixel (x, y) of image b iff  x % stride == 0 && y % stride == 0,  Z = points[b][y][x][2] is finite and
+ *           z_near < Z < z_far,  and -- with a plane -- unc_lo <= u(x, y) <= unc_hi (a NaN u fails).
+ *   Outputs the kept pixels of image b in row-major pixel order (a stable compaction) in rows 0 .. min(count, cap) - 1 of
+ *           out_points [B,cap,3] f32, out_normals [B,cap,3] f32 (given exactly when normals is) and out_index [B,cap] i32 = y * W + x.
+ *           counts [B] i32 is the TRUE number kept, also when it exceeds cap (the caller detects the overflow when it reads the counts
+ *           anyway).  Rows at or beyond min(count, cap) are not touched.
+ * Three launches -- per-chunk counts, one exclusive scan per image, scatter -- and no atomics: two calls on the same tensors give
+ * identical bits.  Workspace of cfp_points_compact_ws_bytes(B, H, W, stride) bytes, 8-byte aligned; 0 for arguments that make no sense. */
+size_t cfp_points_compact_ws_bytes(int B, int H, int W, int stride);
+int cfp_points_compact(const float* points, const float* normals, int H, int W, int B, int stride, float z_near, float z_far,
+                       const float* unc, int Hu, int Wu, long long unc_stride, float unc_lo, float unc_hi, int cap,
+                       float* out_points /* [B][cap][3] */, float* out_normals /* [B][cap][3] or NULL */,
+                       int* out_index /* [B][cap] */, int* counts /* [B] */, void* ws, size_t ws_bytes, cfp_stream_t stream);
+
 /* ---- training-step kernels: backward of the dense convolution, batch-statistics BatchNorm --------------------------
  * (the training row of SURVEY.md section 8: cfpnet_amd/autograd_hip.py chains them into the backward of the whole network) */
 
