@@ -18,16 +18,9 @@
 //   * MFMA v_mfma_f32_16x16x32_bf16; an M-tile is 16 consecutive output pixels of one row.
 //   * epilogue as in conv_igemm2.hip: scale/shift, activation, residual, 16-byte channel vectors.
 #include "igemm_core.h"
+#include "lds_dma.h"
 
 namespace {
-
-__device__ __attribute__((aligned(16))) unsigned int g_zero16b[4] = {0u, 0u, 0u, 0u};
-
-using gptr_t = const __attribute__((address_space(1))) void*;
-using lptr_t = __attribute__((address_space(3))) void*;
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
-}
 
 // UP = true (cfp_upsample_cat_conv3x3, decoder.py:51-58 UpSampleBN: interpolate(x, size=skip, bilinear, align_corners=True) -> cat -> conv3x3):
 // the 64-channel chunks below p.up_C are not fetched but COMPUTED into the halo tile -- four 16-byte taps of the low-resolution map,
@@ -74,7 +67,7 @@ __global__ __launch_bounds__(256) void conv3x3_direct_kernel(ConvP p) {
 
   const H* __restrict__ in = reinterpret_cast<const H*>(p.in) + (long long)b * p.H * p.W * p.in_ld;
   const H* __restrict__ wt = reinterpret_cast<const H*>(p.w);
-  const H* zsrc = reinterpret_cast<const H*>(g_zero16b);
+  const H* zsrc = reinterpret_cast<const H*>(g_zero16);
 
   // ---- per-lane DMA bookkeeping ---------------------------------------------------------------
   int a_off[NAH];       // element offset of the halo pixel inside the image, or -1

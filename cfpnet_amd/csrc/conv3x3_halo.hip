@@ -25,16 +25,10 @@
 #include <algorithm>
 
 #include "igemm_core.h"
+#include "lds_dma.h"
 
 namespace {
 
-__device__ __attribute__((aligned(16))) unsigned int g_zero16h[4] = {0u, 0u, 0u, 0u};
-
-using gptr_t = const __attribute__((address_space(1))) void*;
-using lptr_t = __attribute__((address_space(3))) void*;
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
-}
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 struct HaloP {
@@ -108,7 +102,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
 
   const H* __restrict__ in = reinterpret_cast<const H*>(p.in) + (long long)b * p.H * p.W * p.in_ld;
   const H* __restrict__ wt = reinterpret_cast<const H*>(p.w);
-  const H* zsrc = reinterpret_cast<const H*>(g_zero16h);
+  const H* zsrc = reinterpret_cast<const H*>(g_zero16);
   const int nk = (p.K + 63) >> 6;
 
   // ---- weight stages: lane (row rsub of an 8-row group, logical chunk lc) -------------------------------------------------------

@@ -26,16 +26,10 @@
 // L2 -> LDS bytes per workgroup: halo + all weights of its channel block, e.g. conv0 (32 -> 128 channels at 240 x 320 x 8): 0.45 GB per
 // launch against the implicit GEMM's 1.42 GB; up4's first conv (80 -> 32): 0.47 against 2.26.
 #include "igemm_core.h"
+#include "lds_dma.h"
 
 namespace {
 
-__device__ __attribute__((aligned(16))) unsigned int g_zero16hx[4] = {0u, 0u, 0u, 0u};
-
-using gptr_t = const __attribute__((address_space(1))) void*;
-using lptr_t = __attribute__((address_space(3))) void*;
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
-}
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 struct HaloX3P {
@@ -82,7 +76,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_x3_kernel(ConvP p, HaloX3P h
 
   const float* __restrict__ in = reinterpret_cast<const float*>(p.in) + (long long)b * p.H * p.W * p.in_ld;
   const f16_t* __restrict__ wt = reinterpret_cast<const f16_t*>(p.w);
-  const void* zsrc = reinterpret_cast<const void*>(g_zero16hx);
+  const void* zsrc = reinterpret_cast<const void*>(g_zero16);
   const int nk = (p.K + 31) >> 5;
   const int wrow = nk * 64;
 
@@ -312,7 +306,7 @@ __global__ __launch_bounds__(256) void conv3x3_chunk_x3_kernel(ConvP p, HaloX3P 
 
   const float* __restrict__ in = reinterpret_cast<const float*>(p.in) + (long long)b * p.H * p.W * p.in_ld;
   const f16_t* __restrict__ wt = reinterpret_cast<const f16_t*>(p.w);
-  const void* zsrc = reinterpret_cast<const void*>(g_zero16hx);
+  const void* zsrc = reinterpret_cast<const void*>(g_zero16);
   const int NC0 = UP ? (p.up_C >> 5) : 0;                  // blended chunks (UP)
   const int c_skip = UP ? p.Cin - p.up_C : p.Cin;          // channels of `in` (UP: the skip tensor; any multiple of 4, zero-padded to chunks)
   const int NC = NC0 + ((c_skip + 31) >> 5);               // 32-channel chunks

@@ -30,17 +30,9 @@
 //     w + b * w_bstride (squeeze-excite gates folded into per-image project weights).
 //   * split-K as in conv_igemm.hip: f32 slabs + the shared reduce kernel.
 #include "igemm_core.h"
+#include "lds_dma.h"
 
 namespace {
-
-__device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
-
-using gptr_t = const __attribute__((address_space(1))) void*;
-using lptr_t = __attribute__((address_space(3))) void*;
-
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
-}
 
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 

@@ -22,17 +22,10 @@
 //   * the epilogue stores float32 straight from the accumulators (a lane owns 4 consecutive output channels of one pixel: 16 bytes).
 #include "igemm_core.h"
 #include "head_stats.h"
+#include "lds_dma.h"
 
 namespace {
 
-__device__ __attribute__((aligned(16))) unsigned int g_zero16_x3[4] = {0u, 0u, 0u, 0u};
-
-using gptr_t = const __attribute__((address_space(1))) void*;
-using lptr_t = __attribute__((address_space(3))) void*;
-
-__device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
-}
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // The K loop: accumulates C[m0.., n0..] over K-steps [k0, k1) into acc.  smem: KG * STAGES * (BM + BN) * 128 bytes.  All 256 * KG threads call it.
@@ -95,7 +88,7 @@ __device__ __forceinline__ void x3_mainloop(const ConvP& p, const f16_t* __restr
     if (ok) b_okmask |= 1u << j;
     b_ptr[j] = wt + (long long)(ok ? n : 0) * wrow;
   }
-  const void* zsrc = reinterpret_cast<const void*>(g_zero16_x3);
+  const void* zsrc = reinterpret_cast<const void*>(g_zero16);
   // im2col position of this lane's chunk in the next K-step to be issued, advanced by 32 channels per K-step without divisions
   int i_cc = 0, i_kh = 0, i_kw = 0;
   if (!p.pointwise) {
@@ -329,7 +322,7 @@ __device__ __forceinline__ void x3_mainloop_ad(const ConvP& p, const f16_t* __re
   const int lc = (lane & 7) ^ rsub;
   const int wrow = ((p.K + 31) >> 5) * 64;
   const float* __restrict__ in = reinterpret_cast<const float*>(p.in);
-  const void* zsrc = reinterpret_cast<const void*>(g_zero16_x3);
+  const void* zsrc = reinterpret_cast<const void*>(g_zero16);
 
   const float* a_ptr[TM];
   int a_hi0[TM], a_wi0[TM];

@@ -1567,6 +1567,45 @@ def test_fused_tails_are_bit_stable_at_d32(dtype):
                 assert torch.equal(refs[i], o), (it, i, int((refs[i] != o).any(1).sum()))
 
 
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("D", [32, 64, 128])
+def test_fused_tails_tile_copies_respect_rows_and_pitches(D, dtype):
+    """The 16-row tile copies of the fused tails (global -> LDS with zero fill past the last row, LDS -> global) are one template over the
+    storage type.  70 rows = four full tiles and a ragged one of 6; the LoFTR tail (own-q path) and the LKPM tail run with tight pitches
+    and again with x / t / out at pitch D + 8: the D columns must agree bit for bit, and the 8 columns of `out` behind them keep their
+    sentinel in every row, as does a spare row behind the last one."""
+    heads, NB, Hq, Wq, qt = 8, 2, 5, 7, 3
+    rows, d = NB * Hq * Wq, D // heads
+    G = NB * (-(-Hq // qt)) * (-(-Wq // qt))
+    x3 = dtype == torch.float32
+    x, t = rnd(rows, D, seed=1), rnd(rows, D, seed=2) * 1.5 + 0.2
+    kv, ks = (rnd(G * heads, d, d, seed=3) * 0.3).to(DEV), (rnd(G * heads, d, seed=4).abs() + 0.5).to(DEV)
+    P = (lambda w: ops.pack_w_x3(w.contiguous().to(DEV))) if x3 else (lambda w: w.to(dtype).to(DEV))
+    wq, wm = P(rnd(D, D, seed=5, scale=1 / math.sqrt(D))), P(rnd(D, D, seed=6, scale=1 / math.sqrt(D)))
+    w0, w2 = P(rnd(2 * D, 2 * D, seed=7, scale=1 / math.sqrt(2 * D))), P(rnd(D, 2 * D, seed=8, scale=1 / math.sqrt(2 * D)))
+    w1l, w2l = P(rnd(4 * D, D, seed=9, scale=1 / math.sqrt(D))), P(rnd(D, 4 * D, seed=10, scale=1 / math.sqrt(4 * D)))
+    b1l, b2l = rnd(4 * D, seed=11, scale=0.2).to(DEV), rnd(D, seed=12, scale=0.2).to(DEV)
+    ln1, ln2 = (rnd(D, seed=13).abs().to(DEV) + 0.5, rnd(D, seed=14).to(DEV)), (rnd(D, seed=15).abs().to(DEV) + 0.5, rnd(D, seed=16).to(DEV))
+    SENTINEL = 123.0
+    got = []
+    for ld in (D, D + 8):
+        outs = []
+        for tail in ("loftr", "lkpm"):
+            out = ops.Act(torch.full((rows + 1, ld), SENTINEL, dtype=dtype, device=DEV), 0, D)      # one spare row behind the ragged tile
+            if tail == "loftr":
+                ops.loftr_tail(None, kv, ks, to_act(x, dtype, ld=ld), out, wq, wm, w0, w2, ln1, ln2, NB, Hq, Wq, qt, qt, float(qt * qt), heads)
+            else:
+                ops.lkpm_tail(to_act(t, dtype, ld=ld), to_act(x, dtype, ld=ld), out, w1l, b1l, w2l, b2l, ln1[0], ln1[1], rows)
+            outs.append(out.buf)
+        torch.cuda.synchronize()
+        got.append(outs)
+    for tight, wide in zip(*got):
+        assert bool(torch.isfinite(tight.float()).all()) and not bool((tight[:rows] == SENTINEL).all(1).any())      # every row was written
+        assert torch.equal(tight[:rows], wide[:rows, :D]), (D, dtype, int((tight[:rows] != wide[:rows, :D]).any(1).sum()))
+        assert bool((wide[:, D:] == SENTINEL).all()), (D, dtype)
+        assert bool((tight[rows] == SENTINEL).all()) and bool((wide[rows] == SENTINEL).all()), (D, dtype)      # nothing stored past the last row
+
+
 @pytest.mark.parametrize("D,rows", [(32, 5000), (64, 777), (128, 300), (32, 64), (128, 4097)])
 def test_lkpm_tail_x3(D, rows):
     """LKPM's LayerNorm -> pwconv1 -> GELU -> pwconv2 -> + input in one kernel, default numerics (float32 tensors, f16x3 GEMMs, the hidden
