@@ -22,21 +22,14 @@
 //
 // Same products, float32 accumulation in a different order than the implicit GEMM: results agree to float32 re-association
 // (tests: <= 1 ulp of the storage type against cfp_conv2d_nhwc's other kernels, bit-exact on small integers).
-#include <algorithm>
-
-#include "igemm_core.h"
-#include "lds_dma.h"
+//
+// The tile constants, the workgroup decode, the bilinear taps of the UP loader and the host side
+// (variant table, pitch rule, LDS sizes, launch) are shared with the float32 kernels of conv3x3_halo_x3.hip: halo_core.h.
+#include "halo_core.h"
 
 namespace {
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-struct HaloP {
-  int PP;          // halo pixel pitch in bytes (Cin * 2 rounded up to an odd number of 16-byte slots)
-  int CPT;         // 16-byte chunks per pixel = Cin / 8
-  int tiles_x, tiles_y;
-  int n_blocks;    // workgroups per pixel tile: each owns NT * WN * 16 output channels (they re-read the halo from L2)
-  FastDiv dcpt;    // piece -> (pixel, chunk)
+struct HaloP : HaloGeo {      // PP: Cin * 2 rounded up by halo16_pitch; PPX = 16-byte pieces of a pixel the loader fetches = Cin / 8 (8-channel chunks)
   // --- PW = true only (cfp_conv3x3_pw_fused): the 1x1 convolution that consumes this one's output in the same launch ---
   const void* w2;          // [16 ceil(Cout2 / 16)][Kp] 16-bit, zero padded (ops.pad_pw_w)
   const float* scale2;     // folded BatchNorm / bias of the 1x1 convolution [Cout2] (null = 1 / 0)
@@ -69,15 +62,11 @@ struct HaloP {
 // identical arithmetic.
 template <typename H, int NT, int WN, int STAGES, bool UP = false, int STRIDE = 1, bool PW = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp) {
-  constexpr int WM = 4 / WN;
-  constexpr int TH = 4 * WM;                 // output rows per workgroup (a wave owns 4)
+  using T = HaloTile<NT, WN>;
+  constexpr int TH = T::TH, NPAD = T::NPAD, NB = T::NB, WSTAGE = T::WSTAGE;
   constexpr int HC = 15 * STRIDE + 3;        // halo columns
   constexpr int HPIX = ((TH - 1) * STRIDE + 3) * HC;
   static_assert(!(UP && STRIDE != 1), "the upsampling loader is stride 1");
-  constexpr int NPAD = NT * WN * 16;         // weight rows staged per K-step
-  constexpr int NBG = NPAD / 8;              // 8-row DMA groups
-  constexpr int NB = (NBG + 3) / 4;          // DMA instructions per wave per stage
-  constexpr int WSTAGE = NPAD * 128;
   constexpr int LB = UP ? 4 : 6;             // halo pieces per thread and loader pass (UP: four taps each)
   static_assert((STAGES - 2) * NB <= 63, "vmcnt field");
   static_assert(!PW || (STAGES == 2 && !UP && WN <= 2), "the fused 1x1 takes stage 0 of two weight stages");
@@ -90,27 +79,23 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
   const int fr = lane & 15, fq = lane >> 4;
-  const int rsub = lane >> 3;
-  const int lc = (lane & 7) ^ rsub;
 
-  int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int n_base = (bid % hp.n_blocks) * NPAD; bid /= hp.n_blocks;      // channel blocks of one tile are neighbours: they share the halo in L2
-  const int tx_ = bid % hp.tiles_x; bid /= hp.tiles_x;
-  const int ty_ = bid % hp.tiles_y;
-  const int b = bid / hp.tiles_y;
-  const int x0 = tx_ * 16, y0 = ty_ * TH;
+  const HaloWg wg = halo_wg<NT, WN>(hp);
+  const int n_base = wg.n_base, x0 = wg.x0, y0 = wg.y0, b = wg.b;
 
   const H* __restrict__ in = reinterpret_cast<const H*>(p.in) + (long long)b * p.H * p.W * p.in_ld;
-  const H* __restrict__ wt = reinterpret_cast<const H*>(p.w);
-  const H* zsrc = reinterpret_cast<const H*>(g_zero16);
   const int nk = (p.K + 63) >> 6;
 
-  // ---- weight stages: lane (row rsub of an 8-row group, logical chunk lc) -------------------------------------------------------
+  // ---- weight stages: lane (row rsub of an 8-row group, logical chunk lc); 64-deep K-steps of the [Cout][K] rows, the K tail masked ------------------------------------------------------
+  const int rsub = lane >> 3;
+  const int lc = (lane & 7) ^ rsub;
+  const H* __restrict__ wt = reinterpret_cast<const H*>(p.w);
+  const void* zsrc = reinterpret_cast<const void*>(g_zero16);
   const H* b_ptr[NB];
   unsigned b_okmask = 0;
 #pragma unroll
   for (int j = 0; j < NB; ++j) {
-    const int n = n_base + ((j * 4 + wave) % NBG) * 8 + rsub;
+    const int n = n_base + ((j * 4 + wave) % T::NBG) * 8 + rsub;
     const bool ok = n < p.Cout;
     if (ok) b_okmask |= 1u << j;
     b_ptr[j] = wt + (long long)(ok ? n : 0) * p.K;
@@ -122,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
       const bool ok = kok && ((b_okmask >> j) & 1u);
-      glds16(ok ? b_ptr[j] + kk : zsrc, s + ((j * 4 + wave) % NBG) * 1024);
+      glds16(ok ? (const void*)(b_ptr[j] + kk) : zsrc, s + ((j * 4 + wave) % T::NBG) * 1024);
     }
   };
   const int sb = PW ? (nk & 1) : 0;      // PW: the stages rotate so that the LAST K-step reads stage 1 and W2 lands in stage 0
@@ -150,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
   // ---- the halo: all pieces of the thread in flight, then the LDS stores (the compiler drains the DMA queue before them; both are
   //      needed before the first MFMA anyway) ---------------------------------------------------------------------------------------
   {
-    const int nitems = HPIX * hp.CPT;
+    const int nitems = HPIX * hp.PPX;
     const H* __restrict__ low = nullptr;
     int upc = 0;
     if constexpr (UP) { low = reinterpret_cast<const H*>(p.up_src) + (long long)b * p.up_H * p.up_W * p.up_ld; upc = p.up_C >> 3; }
@@ -163,7 +148,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
       for (int n = 0; n < LB; ++n) {
         const int i = base + tid + n * 256;
         unsigned upx, uch;
-        fd_rowcol((unsigned)i, hp.dcpt, upx, uch);
+        fd_rowcol((unsigned)i, hp.dpx, upx, uch);
         const int px = (int)upx, ch = (int)uch;
         const int hy = px / HC, hx = px - hy * HC;
         const int y = y0 * STRIDE - p.pad_t + hy, x = x0 * STRIDE - p.pad_l + hx;
@@ -175,14 +160,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
         if constexpr (UP) {
           if (ch < upc) {
             blend[n] = ok;
-            const float fy = p.up_sy * (float)y, fx = p.up_sx * (float)x;      // torch: src = scale * dst_index (align_corners=True)
-            const int ys = (int)fy, xs = (int)fx;
-            lyx[n][0] = fy - (float)ys; lyx[n][1] = fx - (float)xs;
+            const BilinTap bt = bilin_tap(p, y, x);
+            lyx[n][0] = bt.ly; lyx[n][1] = bt.lx;
             if (ok) {
-              const int dyo = (ys < p.up_H - 1 ? 1 : 0) * p.up_W * p.up_ld, dxo = (xs < p.up_W - 1 ? 1 : 0) * p.up_ld;
-              const H* s00 = low + (ys * p.up_W + xs) * p.up_ld + ch * 8;
-              v[n][0] = *reinterpret_cast<const u32x4*>(s00); v[n][1] = *reinterpret_cast<const u32x4*>(s00 + dxo);
-              v[n][2] = *reinterpret_cast<const u32x4*>(s00 + dyo); v[n][3] = *reinterpret_cast<const u32x4*>(s00 + dyo + dxo);
+              const H* s00 = low + bt.off + ch * 8;
+              v[n][0] = *reinterpret_cast<const u32x4*>(s00); v[n][1] = *reinterpret_cast<const u32x4*>(s00 + bt.dxo);
+              v[n][2] = *reinterpret_cast<const u32x4*>(s00 + bt.dyo); v[n][3] = *reinterpret_cast<const u32x4*>(s00 + bt.dyo + bt.dxo);
             }
             continue;
           }
@@ -197,9 +180,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
             float t[4][8], o[8];
 #pragma unroll
             for (int q = 0; q < 4; ++q) Vec<H>::load(reinterpret_cast<const H*>(&v[n][q]), t[q]);
-            const float ly1 = lyx[n][0], lx1 = lyx[n][1], ly0 = 1.f - ly1, lx0 = 1.f - lx1;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = ly0 * (lx0 * t[0][e] + lx1 * t[1][e]) + ly1 * (lx0 * t[2][e] + lx1 * t[3][e]);
+            for (int e = 0; e < 8; ++e) o[e] = bilin_blend(lyx[n][0], lyx[n][1], t[0][e], t[1][e], t[2][e], t[3][e]);
             Vec<H>::store(reinterpret_cast<H*>(sX + dst[n]), o);
             continue;
           }
@@ -221,12 +203,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
     for (int j = 0; j < NT; ++j) acc[g][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
   // im2col position of this lane's k-chunk (c = 4 * step + fq): tap offset inside the halo and chunk inside the pixel
-  const int ntap_chunks = 9 * hp.CPT;
+  const int ntap_chunks = 9 * hp.PPX;
   int c_cc, c_dx = 0, c_off = 0, c_idx = fq;
   {
-    const int tap = fq / hp.CPT;
-    c_cc = fq - tap * hp.CPT;
-    c_dx = tap;                                  // fq <= 3 and CPT >= 1: tap <= 3; normalised below
+    const int tap = fq / hp.PPX;
+    c_cc = fq - tap * hp.PPX;
+    c_dx = tap;                                  // fq <= 3 and PPX >= 1: tap <= 3; normalised below
     while (c_dx >= 3) { c_dx -= 3; c_off += HC * hp.PP; }
     c_off += c_dx * hp.PP;
   }
@@ -264,8 +246,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
       // next 32-deep step: four chunks further
       c_idx += 4;
       c_cc += 4;
-      while (c_cc >= hp.CPT) {
-        c_cc -= hp.CPT;
+      while (c_cc >= hp.PPX) {
+        c_cc -= hp.PPX;
         c_off += hp.PP;
         if (++c_dx == 3) { c_dx = 0; c_off += (HC - 3) * hp.PP; }
       }
@@ -441,83 +423,33 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
 int g_halo_odd_pitch = 0;    // cfp_debug_set key 27: 1 = the round-3 odd pixel pitch
 int g_halo_stages = 0;      // cfp_debug_set key 13: force the number of weight stages (2-4), 0 = automatic
 
-struct HCfg { int nt, wn; };
-constexpr HCfg kHCfg[] = {
-    {1, 1},  // 0: Cout <= 16, 16 x 16 pixels
-    {2, 1},  // 1: <= 32
-    {4, 1},  // 2: <= 64
-    {2, 2},  // 3: <= 64, 8 x 16 pixels
-    {4, 2},  // 4: <= 128
-    {5, 2},  // 5: <= 160
-    {7, 2},  // 6: <= 224
-    {1, 2},  // 7: <= 32, 8 x 16 pixels
-};
-constexpr int kNumHCfg = sizeof(kHCfg) / sizeof(kHCfg[0]);
-
-// LDS bytes of a fused 3x3 -> 1x1 (PW) workgroup before its epilogue constants: the K loop's two weight stages + halo, or W2 (in stage 0) + the
-// `mid` tile of the tail, whichever is larger
-static size_t pw_lds_body(int npad, int th, size_t halo, int mid, int cout2) {
-  const size_t kp = (size_t)cdiv(mid, 32) * 32;
-  const size_t tail = (size_t)cdiv(cout2, 16) * 16 * kp * 2 + (size_t)th * 16 * (kp * 2 + 16);
-  return std::max((size_t)2 * npad * 128 + halo, tail);
-}
-static size_t pw_const_bytes(int npad) { return (size_t)(2 * npad + 128) * 4; }      // scale | shift of the 3x3, scale2 | shift2 [64] of the 1x1
-
 template <typename H, int NT, int WN, bool UP = false, int STRIDE = 1, bool PW = false>
 int launch_h(const ConvP& p, hipStream_t s, const ConvPwP* pw = nullptr) {
-  constexpr int TH = 4 * (4 / WN);
-  constexpr int NPAD = NT * WN * 16;
+  constexpr HaloTileV t = halo_tile(NT, WN);
   HaloP hp{};
-  hp.n_blocks = cdiv(p.Cout, NPAD);
-  hp.CPT = p.Cin / 8;
-  hp.dcpt = make_fastdiv((unsigned)hp.CPT);
-  if ((long long)p.H * p.W * p.in_ld >= (1ll << 31)) return -1;
-  // Pixel pitch in 16-byte slots.  `ds_read_b128` is served in four 16-lane groups that pair the lanes (fr in {0-3, 12-15}, fq) with (fr in
-  // {4-11}, fq ^ 1) (MI355X_MICROARCH.md, LDS table): the first set reads slots fr * S * P + o, the second fr * S * P + o + 1 (the next chunk of the
-  // same pixel), and the 16 of them must differ mod 16.  Stride 1: P = 2 (mod 4) -- the first set then covers the even slots, the second the
-  // odd ones (an ODD pitch, the classic padding and this kernel's rule until round 4, puts 43-50 % conflict cycles on these reads:
-  // tools/halo_bank_model.py, measured 25-41 % of all LDS cycles, profiles/r3m_pmc_sq_inference.json).  One chunk per pixel (the sets then
-  // read neighbouring PIXELS) and stride 2 (pixel step 2 P) want P odd.  Odd chunk counts keep 11-20 % on the steps where the two sets
-  // straddle a tap (the shift between them is then even); no linear pitch removes both cases.
-  int slots = hp.CPT;
-  if (STRIDE == 1 && hp.CPT > 1) { while ((slots & 3) != 2) ++slots; }
-  else if ((slots & 1) == 0) ++slots;
-  if (g_halo_odd_pitch) { slots = hp.CPT; if ((slots & 1) == 0) ++slots; }      // cfp_debug_set key 27: the round-3 rule (A/B, PMC comparison)
-  hp.PP = slots * 16;
-  hp.tiles_x = cdiv(p.Wo, 16); hp.tiles_y = cdiv(p.Ho, TH);
-  const int hpix = ((TH - 1) * STRIDE + 3) * (15 * STRIDE + 3);
-  size_t halo = (size_t)hpix * hp.PP;
+  if (!halo_geo<NT, WN>(hp, p, p.Cin / 8, halo16_pitch(p.Cin, STRIDE, g_halo_odd_pitch != 0))) return -1;
+  // weight stages: two.  More would hide more of the DMA latency behind MFMAs, but measured (tools/conv_bench.py --halo, us with
+  // 2 / 3 / 4 stages: 614400 px x 128 ch 82 / 93 / 96, 153600 x 160 36 / 38 / 52, 614400 x 16 23 / 25 / 25, 38400 x 224 19 / 24 / 32)
+  // the LDS they take costs more in resident workgroups than it gains -- the same finding as for the implicit GEMM's tiles
+  const int stages = g_halo_stages && !PW ? g_halo_stages : 2;
+  size_t lds = halo16_lds(t, stages, STRIDE, hp.PP);
   if constexpr (PW) {
     if (!pw || hp.n_blocks != 1 || pw->Cout2 > 64 || pw->Cout2 % 8 != 0) return -1;
     hp.w2 = pw->w2; hp.scale2 = pw->scale2; hp.shift2 = pw->shift2; hp.Cout2 = pw->Cout2; hp.slope2 = pw->act2 == CFP_ACT_LRELU ? 0.01f : 1.f;
     hp.Kp = cdiv(p.Cout, 32) * 32;
-    hp.w2_kb = cdiv(pw->Cout2, 16) * 16 * hp.Kp * 2 / 1024;
-    if ((size_t)hp.w2_kb * 1024 > (size_t)NPAD * 128) return -1;      // W2 must fit one weight stage
-    hp.koff = (int)pw_lds_body(NPAD, TH, halo, p.Cout, pw->Cout2);
-    halo = (size_t)hp.koff - (size_t)2 * NPAD * 128 + pw_const_bytes(NPAD);
+    hp.w2_kb = (int)(halo16_pw_w2_bytes(p.Cout, pw->Cout2) / 1024);
+    if (halo16_pw_w2_bytes(p.Cout, pw->Cout2) > (size_t)t.wstage) return -1;      // W2 must fit one weight stage
+    hp.koff = (int)halo16_pw_body(t, STRIDE, hp.PP, p.Cout, pw->Cout2);
+    lds = halo16_pw_lds(t, STRIDE, hp.PP, p.Cout, pw->Cout2);
   }
-  const long long tiles = (long long)p.B * hp.tiles_x * hp.tiles_y * hp.n_blocks;
-  // weight stages: two.  More would hide more of the DMA latency behind MFMAs, but measured (tools/conv_bench.py --halo, us with
-  // 2 / 3 / 4 stages: 614400 px x 128 ch 82 / 93 / 96, 153600 x 160 36 / 38 / 52, 614400 x 16 23 / 25 / 25, 38400 x 224 19 / 24 / 32)
-  // the LDS they take costs more in resident workgroups than it gains -- the same finding as for the implicit GEMM's tiles
-  int stages = g_halo_stages && !PW ? g_halo_stages : 2;
-  const size_t lds = (size_t)stages * NPAD * 128 + halo;
-  if (lds > 160 * 1024 || tiles >= (1ll << 31)) return -1;
-#define HL(ST)                                                                                                                      \
-  do {                                                                                                                              \
-    auto k = conv3x3_halo_kernel<H, NT, WN, ST, UP, STRIDE, PW>;                                                                      \
-    static bool attr = false;                                                                                                       \
-    if (!attr) { if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -2; attr = true; } \
-    hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(256), lds, s, p, hp);                                                         \
-  } while (0)
-  if constexpr (UP || STRIDE != 1 || PW) { HL(2); } else { if (stages == 4) HL(4); else if (stages == 3) HL(3); else HL(2); }
-#undef HL
-  return 0;
+  if constexpr (UP || STRIDE != 1 || PW) return halo_launch<conv3x3_halo_kernel<H, NT, WN, 2, UP, STRIDE, PW>>(p, hp, lds, s);
+  else return stages == 4 ? halo_launch<conv3x3_halo_kernel<H, NT, WN, 4>>(p, hp, lds, s)
+            : stages == 3 ? halo_launch<conv3x3_halo_kernel<H, NT, WN, 3>>(p, hp, lds, s) : halo_launch<conv3x3_halo_kernel<H, NT, WN, 2>>(p, hp, lds, s);
 }
 
 }  // namespace
 
-int conv3x3_halo_num_variants() { return kNumHCfg; }
+int conv3x3_halo_num_variants() { return kNumHCfg16; }
 void conv3x3_halo_debug_stages(int v) { g_halo_stages = v; }
 void conv3x3_halo_debug_odd_pitch(int v) { g_halo_odd_pitch = v; }
 
@@ -542,7 +474,7 @@ int conv3x3_halo_launch(int v, const ConvP& p, hipStream_t s) {
     else if (p.Cout <= 160) v = 5;
     else v = 4;                      // two or more 128-channel blocks
   }
-  if (v >= kNumHCfg) return -3;
+  if (v >= kNumHCfg16) return -3;
   if (p.up_src != nullptr) {      // upsample + concatenation in the loader: the thin-output tiles only (the decoder's first conv of a stage)
 #define HU(NT, WN) (p.f16 ? launch_h<f16_t, NT, WN, true>(p, s) : launch_h<bf16_t, NT, WN, true>(p, s))
     switch (v) {
@@ -591,13 +523,9 @@ int conv3x3_pw_variant(int Cin, int mid, int Cout2, int stride) {
   if (Cin < 8 || Cin > 128 || Cin % 8 != 0 || mid < 8 || mid % 8 != 0 || Cout2 < 8 || Cout2 > 64 || Cout2 % 8 != 0 || (stride != 1 && stride != 2)) return -1;
   const int v = mid <= 64 ? 2 : mid <= 160 ? 5 : mid <= 224 ? 6 : -1;
   if (v < 0 || (stride == 2 && v == 6)) return -1;
-  const int wn = kHCfg[v].wn, npad = kHCfg[v].nt * wn * 16, th = 4 * (4 / wn);
-  if ((size_t)cdiv(Cout2, 16) * 16 * (cdiv(mid, 32) * 32) * 2 > (size_t)npad * 128) return -1;
-  int slots = Cin / 8;
-  if (stride == 1 && slots > 1) { while ((slots & 3) != 2) ++slots; }
-  else if ((slots & 1) == 0) ++slots;
-  const size_t halo = (size_t)((th - 1) * stride + 3) * (15 * stride + 3) * slots * 16;
-  return pw_lds_body(npad, th, halo, mid, Cout2) + pw_const_bytes(npad) <= 160 * 1024 ? v : -1;
+  const HaloTileV t = halo_tile(kHCfg[v].nt, kHCfg[v].wn);
+  if (halo16_pw_w2_bytes(mid, Cout2) > (size_t)t.wstage) return -1;
+  return halo16_pw_lds(t, stride, halo16_pitch(Cin, stride, false), mid, Cout2) <= kHaloLdsMax ? v : -1;
 }
 
 int conv3x3_pw_launch(const ConvP& p, const ConvPwP& pw, hipStream_t s) {

@@ -25,34 +25,26 @@
 //     folded BatchNorm / bias, activation, optional skip, 16-byte float32 stores.
 // L2 -> LDS bytes per workgroup: halo + all weights of its channel block, e.g. conv0 (32 -> 128 channels at 240 x 320 x 8): 0.45 GB per
 // launch against the implicit GEMM's 1.42 GB; up4's first conv (80 -> 32): 0.47 against 2.26.
-#include "igemm_core.h"
-#include "lds_dma.h"
+//
+// The tile constants, the workgroup decode, the bilinear taps of the UP loader and
+// the host side (variant table, pitch rule, LDS sizes, launch) are shared between the two kernels of this file and with conv3x3_halo.hip:
+// halo_core.h.
+#include "halo_core.h"
 
 namespace {
 
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-
-struct HaloX3P {
-  int PP;          // halo pixel pitch in bytes PER PLANE: Cin * 2 rounded up to an odd number of 16-byte slots
-  int LO;          // byte offset of the lo plane = halo pixels * PP
-  int QPP;         // channel quads per pixel = Cin / 4 (even: Cin % 8 == 0)
-  int tiles_x, tiles_y;
-  int n_blocks;    // workgroups per pixel tile (each owns NT * WN * 16 output channels and re-reads the halo from L2)
-  FastDiv dq;      // piece -> (pixel, quad)
-};
-
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+
+struct HaloX3P : HaloGeo {      // PP per PLANE (halo_x3_pitch); PPX = 16-byte pieces of a pixel the loader fetches = Cin / 4 (float32 channel quads; even: Cin % 8 == 0)
+  int LO;                       // byte offset of the lo plane = halo pixels * PP
+};
 
 template <int NT, int WN, int STAGES>
 __global__ __launch_bounds__(256) void conv3x3_halo_x3_kernel(ConvP p, HaloX3P hp) {
-  constexpr int WM = 4 / WN;
-  constexpr int TH = 4 * WM;                 // output rows per workgroup (a wave owns 4)
+  using T = HaloTile<NT, WN>;
+  constexpr int TH = T::TH, NB = T::NB, WSTAGE = T::WSTAGE;
   constexpr int HC = 18;                     // halo columns
   constexpr int HPIX = (TH + 2) * HC;
-  constexpr int NPAD = NT * WN * 16;         // weight rows staged per K-step
-  constexpr int NBG = NPAD / 8;
-  constexpr int NB = (NBG + 3) / 4;
-  constexpr int WSTAGE = NPAD * 128;
   constexpr int LB = 6;                      // halo pieces per thread and loader pass
   static_assert((STAGES - 2) * NB <= 63, "vmcnt field");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -64,28 +56,24 @@ __global__ __launch_bounds__(256) void conv3x3_halo_x3_kernel(ConvP p, HaloX3P h
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
   const int fr = lane & 15, fq = lane >> 4;
-  const int rsub = lane >> 3;
-  const int lc = (lane & 7) ^ rsub;
 
-  int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int n_base = (bid % hp.n_blocks) * NPAD; bid /= hp.n_blocks;      // channel blocks of one tile are neighbours: they share the halo in L2
-  const int tx_ = bid % hp.tiles_x; bid /= hp.tiles_x;
-  const int ty_ = bid % hp.tiles_y;
-  const int b = bid / hp.tiles_y;
-  const int x0 = tx_ * 16, y0 = ty_ * TH;
+  const HaloWg wg = halo_wg<NT, WN>(hp);
+  const int n_base = wg.n_base, x0 = wg.x0, y0 = wg.y0, b = wg.b;
 
   const float* __restrict__ in = reinterpret_cast<const float*>(p.in) + (long long)b * p.H * p.W * p.in_ld;
+  const int nk = (p.K + 31) >> 5;
+
+  // ---- weight stages: 32-deep K-steps [hi(32) | lo(32)] of rows zero-padded to whole K-steps ---------------------------------------
+  const int wrow = nk * 64;
+  const int rsub = lane >> 3;
+  const int lc = (lane & 7) ^ rsub;
   const f16_t* __restrict__ wt = reinterpret_cast<const f16_t*>(p.w);
   const void* zsrc = reinterpret_cast<const void*>(g_zero16);
-  const int nk = (p.K + 31) >> 5;
-  const int wrow = nk * 64;
-
-  // ---- weight stages: lane (row rsub of an 8-row group, logical 16-byte chunk lc of the 128-byte K-step row) -----------------------
   const f16_t* b_ptr[NB];
   unsigned b_okmask = 0;
 #pragma unroll
   for (int j = 0; j < NB; ++j) {
-    const int n = n_base + ((j * 4 + wave) % NBG) * 8 + rsub;
+    const int n = n_base + ((j * 4 + wave) % T::NBG) * 8 + rsub;
     const bool ok = n < p.Cout;
     if (ok) b_okmask |= 1u << j;
     b_ptr[j] = wt + (long long)(ok ? n : 0) * wrow;
@@ -96,7 +84,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_x3_kernel(ConvP p, HaloX3P h
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
       const bool ok = (b_okmask >> j) & 1u;
-      glds16(ok ? (const void*)(b_ptr[j] + kk) : zsrc, s + ((j * 4 + wave) % NBG) * 1024);
+      glds16(ok ? (const void*)(b_ptr[j] + kk) : zsrc, s + ((j * 4 + wave) % T::NBG) * 1024);
     }
   };
 #pragma unroll
@@ -106,7 +94,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_x3_kernel(ConvP p, HaloX3P h
   // ---- the halo: 16-byte float32 pieces (one channel quad of one pixel), all of the thread's loads of a pass in flight, then split and
   //      stored as [hi4 | .. | lo4 | ..] of the quad's 8-channel group ----------------------------------------------------------------
   {
-    const int nitems = HPIX * hp.QPP;
+    const int nitems = HPIX * hp.PPX;
     for (int base = 0; base < nitems; base += 256 * LB) {
       f32x4 v[LB];
       int dst[LB];
@@ -114,7 +102,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_x3_kernel(ConvP p, HaloX3P h
       for (int n = 0; n < LB; ++n) {
         const int i = base + tid + n * 256;
         unsigned upx, uq;
-        fd_rowcol((unsigned)i, hp.dq, upx, uq);
+        fd_rowcol((unsigned)i, hp.dpx, upx, uq);
         const int px = (int)upx, q = (int)uq;
         const int hy = px / HC, hx = px - hy * HC;
         const int y = y0 - p.pad_t + hy, x = x0 - p.pad_l + hx;
@@ -145,13 +133,13 @@ __global__ __launch_bounds__(256) void conv3x3_halo_x3_kernel(ConvP p, HaloX3P h
 
   // positions of this lane's two channel quads (k4 = 8 ks + fq and 8 ks + 4 + fq) in the flattened (tap, quad) axis: quad inside the pixel,
   // byte offset of the tap inside the halo
-  const int nq_all = 9 * hp.QPP;
+  const int nq_all = 9 * hp.PPX;
   int cq[2], dx[2], off[2], k4[2];
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     k4[h] = fq + 4 * h;
-    int tap = k4[h] / hp.QPP;
-    cq[h] = k4[h] - tap * hp.QPP;
+    int tap = k4[h] / hp.PPX;
+    cq[h] = k4[h] - tap * hp.PPX;
     const int ty = tap / 3;
     dx[h] = tap - ty * 3;
     off[h] = (ty * HC + dx[h]) * hp.PP;
@@ -201,15 +189,16 @@ __global__ __launch_bounds__(256) void conv3x3_halo_x3_kernel(ConvP p, HaloX3P h
     for (int h = 0; h < 2; ++h) {
       k4[h] += 8;
       cq[h] += 8;
-      while (cq[h] >= hp.QPP) {
-        cq[h] -= hp.QPP;
+      while (cq[h] >= hp.PPX) {
+        cq[h] -= hp.PPX;
         off[h] += hp.PP;
         if (++dx[h] == 3) { dx[h] = 0; off[h] += (HC - 3) * hp.PP; }
       }
     }
   }
 
-  // ---- epilogue: folded BatchNorm / bias, activation, optional skip; 16-byte float32 stores from the accumulators ----------------------
+  // ---- epilogue: folded BatchNorm / bias, activation, optional skip; 16-byte float32 stores from the accumulators (the same text in both
+  //      kernels of this file: as a function of halo_core.h it compiled to more registers, profiles/halo_shared_core_ab.txt section 2) ----
   float* __restrict__ out = reinterpret_cast<float*>(p.out) + (long long)b * p.Ho * p.Wo * p.out_ld;
   const float* __restrict__ res = p.res ? reinterpret_cast<const float*>(p.res) + (long long)b * p.Ho * p.Wo * p.res_ld : nullptr;
   const int x = x0 + fr;
@@ -271,14 +260,10 @@ __global__ __launch_bounds__(256) void conv3x3_halo_x3_kernel(ConvP p, HaloX3P h
 // the current one) -- which the other workgroup covers.
 template <int NT, int WN, bool UP = false, int NSTW = 2, bool SB = false>
 __global__ __launch_bounds__(256) void conv3x3_chunk_x3_kernel(ConvP p, HaloX3P hp) {
-  constexpr int WM = 4 / WN;
-  constexpr int TH = 4 * WM;
+  using T = HaloTile<NT, WN>;
+  constexpr int TH = T::TH, NB = T::NB, WSTAGE = T::WSTAGE;
   constexpr int HC = 18;
   constexpr int HPIX = (TH + 2) * HC;
-  constexpr int NPAD = NT * WN * 16;
-  constexpr int NBG = NPAD / 8;
-  constexpr int NB = (NBG + 3) / 4;
-  constexpr int WSTAGE = NPAD * 128;
   constexpr int PPC = 80;                                  // bytes per pixel and plane of a chunk: 32 halves + 16 bytes (5 slots: odd)
   constexpr int LO = HPIX * PPC;                           // lo plane behind the hi plane
   constexpr int CBUF = 2 * LO;                             // one chunk buffer
@@ -294,31 +279,27 @@ __global__ __launch_bounds__(256) void conv3x3_chunk_x3_kernel(ConvP p, HaloX3P 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave / WN, wn = wave % WN;
   const int fr = lane & 15, fq = lane >> 4;
-  const int rsub = lane >> 3;
-  const int lc = (lane & 7) ^ rsub;
 
-  int bid = xcd_remap(blockIdx.x, gridDim.x);
-  const int n_base = (bid % hp.n_blocks) * NPAD; bid /= hp.n_blocks;
-  const int tx_ = bid % hp.tiles_x; bid /= hp.tiles_x;
-  const int ty_ = bid % hp.tiles_y;
-  const int b = bid / hp.tiles_y;
-  const int x0 = tx_ * 16, y0 = ty_ * TH;
+  const HaloWg wg = halo_wg<NT, WN>(hp);
+  const int n_base = wg.n_base, x0 = wg.x0, y0 = wg.y0, b = wg.b;
 
   const float* __restrict__ in = reinterpret_cast<const float*>(p.in) + (long long)b * p.H * p.W * p.in_ld;
-  const f16_t* __restrict__ wt = reinterpret_cast<const f16_t*>(p.w);
-  const void* zsrc = reinterpret_cast<const void*>(g_zero16);
   const int NC0 = UP ? (p.up_C >> 5) : 0;                  // blended chunks (UP)
   const int c_skip = UP ? p.Cin - p.up_C : p.Cin;          // channels of `in` (UP: the skip tensor; any multiple of 4, zero-padded to chunks)
   const int NC = NC0 + ((c_skip + 31) >> 5);               // 32-channel chunks
   const float* __restrict__ low = UP ? reinterpret_cast<const float*>(p.up_src) + (long long)b * p.up_H * p.up_W * p.up_ld : nullptr;
   const int nit = 9 * NC;
-  const int wrow = nit * 64;
 
+  const int rsub = lane >> 3;
+  const int lc = (lane & 7) ^ rsub;
+  const f16_t* __restrict__ wt = reinterpret_cast<const f16_t*>(p.w);
+  const void* zsrc = reinterpret_cast<const void*>(g_zero16);
+  const int wrow = nit * 64;
   const f16_t* b_ptr[NB];
   unsigned b_okmask = 0;
 #pragma unroll
   for (int j = 0; j < NB; ++j) {
-    const int n = n_base + ((j * 4 + wave) % NBG) * 8 + rsub;
+    const int n = n_base + ((j * 4 + wave) % T::NBG) * 8 + rsub;
     const bool ok = n < p.Cout;
     if (ok) b_okmask |= 1u << j;
     b_ptr[j] = wt + (long long)(ok ? n : 0) * wrow;
@@ -329,7 +310,7 @@ __global__ __launch_bounds__(256) void conv3x3_chunk_x3_kernel(ConvP p, HaloX3P 
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
       const bool ok = (b_okmask >> j) & 1u;
-      glds16(ok ? (const void*)(b_ptr[j] + kk) : zsrc, s + ((j * 4 + wave) % NBG) * 1024);
+      glds16(ok ? (const void*)(b_ptr[j] + kk) : zsrc, s + ((j * 4 + wave) % T::NBG) * 1024);
     }
   };
   // this thread's pieces of a chunk's halo: (pixel, quad) -> image offset / LDS offset (the same for every chunk)
@@ -357,12 +338,9 @@ __global__ __launch_bounds__(256) void conv3x3_chunk_x3_kernel(ConvP p, HaloX3P 
       const int px = i >> 3, q = i & 7;
       const int hy = px / HC, hx = px - hy * HC;
       const int y = min(max(y0 - p.pad_t + hy, 0), p.H - 1), x = min(max(x0 - p.pad_l + hx, 0), p.W - 1);      // (pieces outside the image are zeroed by src_okmask)
-      const float fy = p.up_sy * (float)y, fx = p.up_sx * (float)x;
-      const int ys = (int)fy, xs = (int)fx;
-      up_ly[n] = fy - (float)ys; up_lx[n] = fx - (float)xs;
-      up_dyo[n] = (ys < p.up_H - 1 ? 1 : 0) * p.up_W * p.up_ld;
-      up_dxo[n] = (xs < p.up_W - 1 ? 1 : 0) * p.up_ld;
-      up_off[n] = (ys * p.up_W + xs) * p.up_ld + q * 4;
+      const BilinTap bt = bilin_tap(p, y, x);
+      up_ly[n] = bt.ly; up_lx[n] = bt.lx; up_dyo[n] = bt.dyo; up_dxo[n] = bt.dxo;
+      up_off[n] = bt.off + q * 4;
     }
   }
   f32x4 hv[NLD][UP ? 4 : 1];
@@ -401,9 +379,8 @@ __global__ __launch_bounds__(256) void conv3x3_chunk_x3_kernel(ConvP p, HaloX3P 
       f32x4 v = hv[n][0];
       if constexpr (UP) {
         if (blended) {
-          const float ly1 = up_ly[n], lx1 = up_lx[n], ly0 = 1.f - ly1, lx0 = 1.f - lx1;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = ly0 * (lx0 * hv[n][0][e] + lx1 * hv[n][1][e]) + ly1 * (lx0 * hv[n][2][e] + lx1 * hv[n][3][e]);
+          for (int e = 0; e < 4; ++e) v[e] = bilin_blend(up_ly[n], up_lx[n], hv[n][0][e], hv[n][1][e], hv[n][2][e], hv[n][3][e]);
         } else {
           okn = okn && (c - NC0) * 32 + ((tid + n * 256) & 7) * 4 < c_skip;
         }
@@ -495,6 +472,8 @@ __global__ __launch_bounds__(256) void conv3x3_chunk_x3_kernel(ConvP p, HaloX3P 
     }
   }
 
+  // ---- epilogue: folded BatchNorm / bias, activation, optional skip; 16-byte float32 stores from the accumulators (the same text in both
+  //      kernels of this file: as a function of halo_core.h it compiled to more registers, profiles/halo_shared_core_ab.txt section 2) ----
   float* __restrict__ out = reinterpret_cast<float*>(p.out) + (long long)b * p.Ho * p.Wo * p.out_ld;
   const float* __restrict__ res = p.res ? reinterpret_cast<const float*>(p.res) + (long long)b * p.Ho * p.Wo * p.res_ld : nullptr;
   const int x = x0 + fr;
@@ -526,70 +505,28 @@ __global__ __launch_bounds__(256) void conv3x3_chunk_x3_kernel(ConvP p, HaloX3P 
 
 template <int NT, int WN, bool UP = false, int NSTW = 2, bool SB = false>
 int launch_cx(const ConvP& p, hipStream_t s) {
-  constexpr int TH = 4 * (4 / WN);
-  constexpr int NPAD = NT * WN * 16;
+  constexpr HaloTileV t = halo_tile(NT, WN);
   HaloX3P hp;
-  hp.n_blocks = cdiv(p.Cout, NPAD);
-  hp.QPP = p.Cin / 4; hp.dq = make_fastdiv((unsigned)hp.QPP); hp.PP = 80; hp.LO = (TH + 2) * 18 * 80;
-  if ((long long)p.H * p.W * p.in_ld >= (1ll << 31)) return -1;
+  if (!halo_geo<NT, WN>(hp, p, p.Cin / 4, 80)) return -1;
+  hp.LO = (int)halo_x3_plane(t, 80);
   if (!UP && p.Cin % 32 != 0) return -1;
   if (UP && (p.up_src == nullptr || p.up_C % 32 != 0 || p.up_C <= 0 || (p.Cin - p.up_C) % 4 != 0 || p.Cin - p.up_C < 4 ||
              (long long)p.up_H * p.up_W * p.up_ld >= (1ll << 31) || p.H < 2 || p.W < 2)) return -1;
-  hp.tiles_x = cdiv(p.Wo, 16); hp.tiles_y = cdiv(p.Ho, TH);
-  const long long tiles = (long long)p.B * hp.tiles_x * hp.tiles_y * hp.n_blocks;
-  const size_t lds = (size_t)NSTW * NPAD * 128 + (size_t)(SB ? 1 : 2) * 2 * hp.LO;
-  if (lds > 160 * 1024 || tiles >= (1ll << 31)) return -1;
-  auto k = conv3x3_chunk_x3_kernel<NT, WN, UP, NSTW, SB>;
-  static bool attr = false;
-  if (!attr) { if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -2; attr = true; }
-  hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(256), lds, s, p, hp);
-  return 0;
+  return halo_launch<conv3x3_chunk_x3_kernel<NT, WN, UP, NSTW, SB>>(p, hp, chunk_x3_lds(t, NSTW, SB), s);
 }
-
-struct HCfg { int nt, wn; };
-constexpr HCfg kHCfg[] = {
-    {1, 1},  // 0: Cout <= 16, 16 x 16 pixels
-    {2, 1},  // 1: <= 32
-    {4, 1},  // 2: <= 64
-    {2, 2},  // 3: <= 64, 8 x 16 pixels
-    {4, 2},  // 4: <= 128
-    {5, 2},  // 5: <= 160
-    {7, 2},  // 6: <= 224
-    {1, 2},  // 7: <= 32, 8 x 16 pixels
-    {8, 1},  // 8: <= 128, 16 x 16 pixels
-    {5, 1},  // 9: <= 80
-};
-constexpr int kNumHCfg = sizeof(kHCfg) / sizeof(kHCfg[0]);
 
 template <int NT, int WN>
 int launch_hx(const ConvP& p, hipStream_t s) {
-  constexpr int TH = 4 * (4 / WN);
-  constexpr int NPAD = NT * WN * 16;
-  constexpr int STAGES = 2;
+  constexpr HaloTileV t = halo_tile(NT, WN);
   HaloX3P hp;
-  hp.n_blocks = cdiv(p.Cout, NPAD);
-  hp.QPP = p.Cin / 4;
-  hp.dq = make_fastdiv((unsigned)hp.QPP);
-  if ((long long)p.H * p.W * p.in_ld >= (1ll << 31)) return -1;
-  int slots = hp.QPP / 2;          // 16-byte slots of one plane's pixel (QPP is even)
-  if ((slots & 1) == 0) ++slots;
-  hp.PP = slots * 16;
-  hp.LO = (TH + 2) * 18 * hp.PP;
-  hp.tiles_x = cdiv(p.Wo, 16); hp.tiles_y = cdiv(p.Ho, TH);
-  const size_t halo = (size_t)2 * hp.LO;
-  const long long tiles = (long long)p.B * hp.tiles_x * hp.tiles_y * hp.n_blocks;
-  const size_t lds = (size_t)STAGES * NPAD * 128 + halo;
-  if (lds > 160 * 1024 || tiles >= (1ll << 31)) return -1;
-  auto k = conv3x3_halo_x3_kernel<NT, WN, STAGES>;
-  static bool attr = false;
-  if (!attr) { if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -2; attr = true; }
-  hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(256), lds, s, p, hp);
-  return 0;
+  if (!halo_geo<NT, WN>(hp, p, p.Cin / 4, halo_x3_pitch(p.Cin))) return -1;
+  hp.LO = (int)halo_x3_plane(t, hp.PP);
+  return halo_launch<conv3x3_halo_x3_kernel<NT, WN, 2>>(p, hp, halo_x3_lds(t, hp.PP), s);
 }
 
 }  // namespace
 
-int conv3x3_halo_x3_num_variants() { return kNumHCfg; }
+int conv3x3_halo_x3_num_variants() { return kNumHCfgX3; }
 
 // The problems this kernel takes: 3x3, stride 1, undilated, float32 tensors with pre-split weights, Cin a multiple of 8, shared weights.
 bool conv3x3_halo_x3_takes(const ConvP& p) {
@@ -599,12 +536,9 @@ bool conv3x3_halo_x3_takes(const ConvP& p) {
 
 // Smallest LDS footprint (bytes) of variant v for this problem, or 0 if it cannot hold the halo.
 size_t conv3x3_halo_x3_lds(int v, const ConvP& p) {
-  if (v < 0 || v >= kNumHCfg) return 0;
-  const int th = 4 * (4 / kHCfg[v].wn), npad = kHCfg[v].nt * kHCfg[v].wn * 16;
-  int slots = p.Cin / 8;
-  if ((slots & 1) == 0) ++slots;
-  const size_t lds = (size_t)2 * npad * 128 + (size_t)2 * (th + 2) * 18 * slots * 16;
-  return lds <= 160 * 1024 ? lds : 0;
+  if (v < 0 || v >= kNumHCfgX3) return 0;
+  const size_t lds = halo_x3_lds(halo_tile(kHCfg[v].nt, kHCfg[v].wn), halo_x3_pitch(p.Cin));
+  return lds <= kHaloLdsMax ? lds : 0;
 }
 
 // v < 0: automatic tile (widest channel block that fits, 16 x 16 pixels while two workgroups still share a CU).

@@ -12,3 +12,6 @@ using lptr_t = __attribute__((address_space(3))) void*;
 __device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)lds_wave_base, 16, 0, 0);
 }
+
+// counted wait: all but this wave's N youngest vector-memory operations (they complete in order) have landed
+template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }

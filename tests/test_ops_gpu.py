@@ -1,5 +1,6 @@
 """Kernel-level numerics: every HIP entry point against a plain PyTorch fp32 reference of the
 same op (CPU), in f32 (tight) and bf16 (storage-rounding) tolerances.  Runs on the GPU box."""
+import functools
 import math
 import os
 
@@ -609,6 +610,64 @@ def test_conv3x3_halo_x3_every_variant(variant):
     finally:
         lib.cfp_debug_set(0, -1)
     assert ran >= (len(X3_HALO_CASES) if variant == 99 else 5)
+
+
+X3_DGRAD_FORM_CASES = [
+    (1, 9, 18, 32, 40),       # one chunk, Cout fills no tile, more columns than one tile, fewer rows than one
+    (2, 17, 16, 64, 32),      # two chunks, ragged rows
+]
+
+
+@functools.lru_cache(maxsize=None)
+def _x3_dgrad_form_problem(case):
+    """Operands and the float64 convolution (no epilogue) of a 3x3 stride-1 pad-1 case, and the implicit GEMM's outputs (variant 413) for the
+    four call forms (scale?, residual?): computed once, shared by every forced variant."""
+    B, H, W, Cin, Cout = case
+    x, w = rnd(B, Cin, H, W, seed=31), rnd(Cout, Cin, 3, 3, seed=32, scale=1.0 / math.sqrt(9 * Cin))
+    scale, res = rnd(Cout, seed=33).abs() + 0.5, rnd(B, Cout, H, W, seed=34)
+    conv = F.conv2d(x.double(), w.double(), None, 1, 1)
+    xa = to_act(nhwc(x), torch.float32, ld=Cin + 16, c0=8)
+    wx = ops.pack_w_x3(w.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin).contiguous().to(DEV))
+    ra, sc = to_act(nhwc(res), torch.float32), scale.to(DEV)
+    lib = hip.load()
+    igemm = {}
+    try:
+        lib.cfp_debug_set(0, 413)
+        for use_scale in (False, True):
+            for use_res in (False, True):
+                o = ops.new_act(B * H * W, Cout, torch.float32, DEV)
+                ops.conv2d(xa, wx, sc if use_scale else None, None, o, B, H, W, 3, 3, 1, 1, 1, H, W, hip.ACT_NONE, ra if use_res else None, None)
+                igemm[use_scale, use_res] = o.torch().clone()
+        torch.cuda.synchronize()
+    finally:
+        lib.cfp_debug_set(0, -1)
+    return conv, scale.double()[None, :, None, None], res.double(), xa, wx, sc, ra, igemm
+
+
+@pytest.mark.parametrize("variant", [3, 7, 9, 24, 36, 45])
+def test_conv3x3_x3_kernels_in_the_data_gradient_call_form(variant):
+    """cfp_conv2d_dgrad in f32x3 reaches the whole-depth (3, 7, 9) and chunk-pipelined (24, 36, 45) kernels with the scale set or null, the
+    shift null, no activation and the skip as accumulation -- the null branches of their epilogues, which the variant tests above
+    (scale, shift, SiLU and a residual, always) never take.  Against float64 and the f16x3 implicit GEMM; the guard columns stay zero."""
+    lib = hip.load()
+    try:
+        for case in X3_DGRAD_FORM_CASES:
+            B, H, W, Cin, Cout = case
+            conv, scale64, res64, xa, wx, sc, ra, igemm = _x3_dgrad_form_problem(case)
+            lib.cfp_debug_set(0, 500 + variant)
+            for use_scale in (False, True):
+                for use_res in (False, True):
+                    ref = (conv * scale64 if use_scale else conv) + (res64 if use_res else 0.0)
+                    out = ops.new_act(B * H * W, Cout, torch.float32, DEV, ld=Cout + 24, zero=True)
+                    out = ops.Act(out.buf, 16, Cout)
+                    ops.conv2d(xa, wx, sc if use_scale else None, None, out, B, H, W, 3, 3, 1, 1, 1, H, W, hip.ACT_NONE, ra if use_res else None, None)
+                    torch.cuda.synchronize()
+                    what = f"x3 v{variant} scale {use_scale} residual {use_res} conv {case}"
+                    _x3_close(from_nhwc(out.torch(), B, H, W), ref, what)
+                    assert float(out.buf[:, :16].abs().max()) == 0 and float(out.buf[:, 16 + Cout:].abs().max()) == 0, what
+                    assert float((igemm[use_scale, use_res] - out.torch()).abs().max()) <= 2e-6 * float(ref.abs().max()), what
+    finally:
+        lib.cfp_debug_set(0, -1)
 
 
 def test_conv3x3_halo_x3_is_what_the_plan_picks_for_many_pixel_layers():
