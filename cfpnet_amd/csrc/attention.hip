@@ -17,6 +17,7 @@ struct KvP {
   int cy0, cy1, cx0, cx1;
   int count_pad, heads, d, nsplit;
   float inv_len;
+  const int* rec;      // DEV only (last: the scalar instantiation's argument offsets stay): the zone record, see cfp_attn_kv_reduce_dev
 };
 
 // IC rows of the d x d accumulator per lane; TPK = d / IC lanes per key; KL = 64 / TPK key lanes.
@@ -29,7 +30,9 @@ template <> struct KvCfg<8>  { static constexpr int IC = 2; };
 template <> struct KvCfg<16> { static constexpr int IC = 2; };
 template <> struct KvCfg<32> { static constexpr int IC = 2; };
 
-template <typename T, int D>
+// DEV: the clip rectangle and v_length come from the int32[9] zone record in device memory (y0, y1, x0, x1, n_inside: uniform loads)
+// instead of the host's integers; everything after that is the scalar instantiation's own code.
+template <typename T, int D, bool DEV>
 __global__ __launch_bounds__(64) void kv_reduce_kernel(KvP p) {
   constexpr int IC = KvCfg<D>::IC;
   constexpr int TPK = D / IC;
@@ -43,9 +46,16 @@ __global__ __launch_bounds__(64) void kv_reduce_kernel(KvP p) {
   const int gpb = p.gy * p.gx;
   const int b = g / gpb, gi = g % gpb;
   const int ty = gi / p.gx, tx = gi % p.gx;
+  int cy0 = p.cy0, cy1 = p.cy1, cx0 = p.cx0, cx1 = p.cx1;
+  float inv_len = p.inv_len;
+  if constexpr (DEV) {
+    const int* __restrict__ rec = p.rec;
+    cy0 = rec[4]; cy1 = rec[5]; cx0 = rec[6]; cx1 = rec[7];
+    inv_len = 1.0f / (float)max(rec[8], 1);      // the host's expression: 1 / v_length, v_length = max(n_inside, 1)
+  }
   // key rectangle of this group: tile, clipped to the grid and to the clip rectangle
-  const int y0 = max(max(ty * p.th, p.cy0), 0), y1 = min(min((ty + 1) * p.th, p.cy1), p.Hk);
-  const int x0 = max(max(tx * p.tw, p.cx0), 0), x1 = min(min((tx + 1) * p.tw, p.cx1), p.Wk);
+  const int y0 = max(max(ty * p.th, cy0), 0), y1 = min(min((ty + 1) * p.th, cy1), p.Hk);
+  const int x0 = max(max(tx * p.tw, cx0), 0), x1 = min(min((tx + 1) * p.tw, cx1), p.Wk);
   const int rh = max(y1 - y0, 0), rw = max(x1 - x0, 0);
   const int S = rh * rw;
   const int per = (S + p.nsplit - 1) / p.nsplit;
@@ -89,7 +99,7 @@ __global__ __launch_bounds__(64) void kv_reduce_kernel(KvP p) {
     for (int u = 0; u < KU; ++u) {
       if (s0 + u * KL >= s_end) continue;              // same order of accumulation per lane as the one-key loop
 #pragma unroll
-      for (int j = 0; j < D; ++j) vf[u][j] *= p.inv_len;
+      for (int j = 0; j < D; ++j) vf[u][j] *= inv_len;
 #pragma unroll
       for (int i = 0; i < IC; ++i) {
         const float kk = elu1(kf[u][i]);
@@ -159,16 +169,25 @@ struct ApP {
   int ey0, ey1, ex0, ex1, heads;
   float v_length, eps;
   FastDiv fheads, fwq, fhq, fqth, fqtw;      // (token, head) index arithmetic without 64-bit divisions (five per element in the first version)
+  const int* rec;      // DEV only (last, as in KvP): the zone record, see cfp_attn_apply_dev
 };
 
 // JS lanes share one (token, head): lane js computes the D / JS outputs js * D / JS ... (and the normaliser, redundantly).  With one lane per
 // (token, head) a d = 32 head is a chain of 1 024 dependent-latency FMAs fed by 256 sixteen-byte loads, and a single image has 4 800 such lanes --
 // 19 workgroups, 24 us; eight lanes each shorten the chain eightfold and fill eight times the CUs.  Every output is the same sum in the same order.
-template <typename T, int D, int JS>
+// DEV: exclusion rectangle and v_length from the zone record, as in kv_reduce_kernel.
+template <typename T, int D, int JS, bool DEV>
 __global__ __launch_bounds__(256) void attn_apply_kernel(ApP p) {
   constexpr int DJ = D / JS;
   const T* __restrict__ Q = reinterpret_cast<const T*>(p.q);
   T* __restrict__ O = reinterpret_cast<T*>(p.out);
+  int ey0 = p.ey0, ey1 = p.ey1, ex0 = p.ex0, ex1 = p.ex1;
+  float v_length = p.v_length;
+  if constexpr (DEV) {
+    const int* __restrict__ rec = p.rec;
+    ey0 = rec[4]; ey1 = rec[5]; ex0 = rec[6]; ex1 = rec[7];
+    v_length = (float)max(rec[8], 1);
+  }
   const unsigned total = (unsigned)p.NB * p.Hq * p.Wq * p.heads * JS;      // < 2^31: host check
   for (unsigned i0 = blockIdx.x * 256u + threadIdx.x; i0 < total; i0 += gridDim.x * 256u) {
     const unsigned i = i0 / JS;
@@ -181,7 +200,7 @@ __global__ __launch_bounds__(256) void attn_apply_kernel(ApP p) {
     const long long tok = toku;
     T* op = O + tok * p.out_ld + h * D + js * DJ;
     float o[DJ];
-    if (y >= p.ey0 && y < p.ey1 && x >= p.ex0 && x < p.ex1) {
+    if (y >= ey0 && y < ey1 && x >= ex0 && x < ex1) {
 #pragma unroll
       for (int j = 0; j < DJ; ++j) o[j] = 0.f;
     } else {
@@ -201,7 +220,7 @@ __global__ __launch_bounds__(256) void attn_apply_kernel(ApP p) {
       }
       const float zi = 1.f / (z + p.eps);
 #pragma unroll
-      for (int j = 0; j < DJ; ++j) o[j] = o[j] * zi * p.v_length;
+      for (int j = 0; j < DJ; ++j) o[j] = o[j] * zi * v_length;
     }
 #pragma unroll
     for (int j = 0; j < DJ; ++j) op[j] = from_f32<T>(o[j]);
@@ -233,15 +252,17 @@ extern "C" size_t cfp_attn_kv_ws_floats(int NB, int Hk, int Wk, int th, int tw, 
   return (size_t)(groups * heads * ns * (d * d + d));
 }
 
-extern "C" int cfp_attn_kv_reduce(const void* k, int k_ld, const void* v, int v_ld, float* kv, float* ksum, float* ws,
-                                  int NB, int Hk, int Wk, int th, int tw, int cy0, int cy1, int cx0, int cx1,
-                                  int count_pad, float v_length, int heads, int d, int dtype, cfp_stream_t stream) {
-  CFP_REQUIRE(dtype_ok(dtype), CFP_EINVAL, "cfp_attn_kv_reduce: bad dtype");
-  CFP_REQUIRE(k && v && kv && ksum, CFP_EINVAL, "cfp_attn_kv_reduce: null pointer");
+// `rec` == nullptr: the scalar entry point (clip rectangle and v_length from the arguments); otherwise the record-reading one
+static int kv_reduce_impl(const void* k, int k_ld, const void* v, int v_ld, float* kv, float* ksum, float* ws,
+                          int NB, int Hk, int Wk, int th, int tw, int cy0, int cy1, int cx0, int cx1,
+                          int count_pad, float v_length, const int* rec, int heads, int d, int dtype, cfp_stream_t stream, const char* who) {
+  CFP_REQUIRE(dtype_ok(dtype), CFP_EINVAL, std::string(who) + ": bad dtype");
+  CFP_REQUIRE(k && v && kv && ksum, CFP_EINVAL, std::string(who) + ": null pointer");
   CFP_REQUIRE(NB > 0 && Hk > 0 && Wk > 0 && th > 0 && tw > 0 && heads > 0 && (d == 4 || d == 8 || d == 16 || d == 32) &&
                   k_ld >= heads * d && v_ld >= heads * d && v_length > 0.f,
-              CFP_ESHAPE, "cfp_attn_kv_reduce: bad shape (head dim must be 4, 8, 16 or 32)");
+              CFP_ESHAPE, std::string(who) + ": bad shape (head dim must be 4, 8, 16 or 32)");
   KvP p;
+  p.rec = rec;
   p.k = k; p.v = v; p.kv = kv; p.ksum = ksum; p.ws = ws; p.k_ld = k_ld; p.v_ld = v_ld;
   p.NB = NB; p.Hk = Hk; p.Wk = Wk; p.th = th; p.tw = tw; p.gy = cdiv(Hk, th); p.gx = cdiv(Wk, tw);
   p.cy0 = cy0; p.cy1 = cy1; p.cx0 = cx0; p.cx1 = cx1; p.count_pad = count_pad; p.heads = heads; p.d = d;
@@ -249,11 +270,12 @@ extern "C" int cfp_attn_kv_reduce(const void* k, int k_ld, const void* v, int v_
   long long groups = (long long)NB * p.gy * p.gx;
   int S = (th < Hk ? th : Hk) * (tw < Wk ? tw : Wk);
   p.nsplit = pick_nsplit(S, groups * heads);
-  CFP_REQUIRE(p.nsplit == 1 || ws, CFP_EINVAL, "cfp_attn_kv_reduce: workspace required");
-  CFP_REQUIRE(groups < (1ll << 31) && heads <= 65535, CFP_ESHAPE, "cfp_attn_kv_reduce: grid too large");
+  CFP_REQUIRE(p.nsplit == 1 || ws, CFP_EINVAL, std::string(who) + ": workspace required");
+  CFP_REQUIRE(groups < (1ll << 31) && heads <= 65535, CFP_ESHAPE, std::string(who) + ": grid too large");
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   dim3 grid((unsigned)groups, heads, p.nsplit);
-#define KV_LAUNCH(T, D) hipLaunchKernelGGL((kv_reduce_kernel<T, D>), grid, dim3(64), 0, s, p)
+#define KV_LAUNCH(T, D) do { if (rec) hipLaunchKernelGGL((kv_reduce_kernel<T, D, true>), grid, dim3(64), 0, s, p); \
+                             else hipLaunchKernelGGL((kv_reduce_kernel<T, D, false>), grid, dim3(64), 0, s, p); } while (0)
 #define KV_SWITCH(T) switch (d) { case 4: KV_LAUNCH(T, 4); break; case 8: KV_LAUNCH(T, 8); break; \
                                   case 16: KV_LAUNCH(T, 16); break; default: KV_LAUNCH(T, 32); break; }
   if (dtype == CFP_BF16) { KV_SWITCH(bf16_t) } else if (dtype == CFP_F16) { KV_SWITCH(f16_t) } else { KV_SWITCH(float) }
@@ -265,30 +287,47 @@ extern "C" int cfp_attn_kv_reduce(const void* k, int k_ld, const void* v, int v_
     int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
     hipLaunchKernelGGL(kv_finalize_kernel, dim3(blocks), dim3(256), 0, s, ws, kv, ksum, p.nsplit, d, items);
   }
-  return cfp_check_launch("cfp_attn_kv_reduce");
+  return cfp_check_launch(who);
 }
 
-extern "C" int cfp_attn_apply(const void* q, int q_ld, const float* kv, const float* ksum, void* out, int out_ld,
-                              int NB, int Hq, int Wq, int qth, int qtw, int ey0, int ey1, int ex0, int ex1,
-                              float v_length, float eps, int heads, int d, int dtype, cfp_stream_t stream) {
-  CFP_REQUIRE(dtype_ok(dtype), CFP_EINVAL, "cfp_attn_apply: bad dtype");
-  CFP_REQUIRE(q && kv && ksum && out, CFP_EINVAL, "cfp_attn_apply: null pointer");
+extern "C" int cfp_attn_kv_reduce(const void* k, int k_ld, const void* v, int v_ld, float* kv, float* ksum, float* ws,
+                                  int NB, int Hk, int Wk, int th, int tw, int cy0, int cy1, int cx0, int cx1,
+                                  int count_pad, float v_length, int heads, int d, int dtype, cfp_stream_t stream) {
+  return kv_reduce_impl(k, k_ld, v, v_ld, kv, ksum, ws, NB, Hk, Wk, th, tw, cy0, cy1, cx0, cx1, count_pad, v_length, nullptr, heads, d, dtype,
+                        stream, "cfp_attn_kv_reduce");
+}
+
+extern "C" int cfp_attn_kv_reduce_dev(const void* k, int k_ld, const void* v, int v_ld, float* kv, float* ksum, float* ws,
+                                      int NB, int Hk, int Wk, int th, int tw, const int* rec, int count_pad, int heads, int d, int dtype,
+                                      cfp_stream_t stream) {
+  CFP_REQUIRE(rec && (reinterpret_cast<uintptr_t>(rec) & 3) == 0, CFP_EINVAL, "cfp_attn_kv_reduce_dev: bad record pointer");
+  return kv_reduce_impl(k, k_ld, v, v_ld, kv, ksum, ws, NB, Hk, Wk, th, tw, 0, 0, 0, 0, count_pad, 1.f, rec, heads, d, dtype, stream,
+                        "cfp_attn_kv_reduce_dev");
+}
+
+static int attn_apply_impl(const void* q, int q_ld, const float* kv, const float* ksum, void* out, int out_ld,
+                           int NB, int Hq, int Wq, int qth, int qtw, int ey0, int ey1, int ex0, int ex1,
+                           float v_length, const int* rec, float eps, int heads, int d, int dtype, cfp_stream_t stream, const char* who) {
+  CFP_REQUIRE(dtype_ok(dtype), CFP_EINVAL, std::string(who) + ": bad dtype");
+  CFP_REQUIRE(q && kv && ksum && out, CFP_EINVAL, std::string(who) + ": null pointer");
   CFP_REQUIRE(NB > 0 && Hq > 0 && Wq > 0 && qth > 0 && qtw > 0 && heads > 0 && (d == 4 || d == 8 || d == 16 || d == 32) &&
-                  q_ld >= heads * d && out_ld >= heads * d, CFP_ESHAPE, "cfp_attn_apply: bad shape");
+                  q_ld >= heads * d && out_ld >= heads * d, CFP_ESHAPE, std::string(who) + ": bad shape");
   ApP p;
+  p.rec = rec;
   p.q = q; p.kv = kv; p.ksum = ksum; p.out = out; p.q_ld = q_ld; p.out_ld = out_ld;
   p.NB = NB; p.Hq = Hq; p.Wq = Wq; p.qth = qth; p.qtw = qtw; p.ggy = cdiv(Hq, qth); p.ggx = cdiv(Wq, qtw);
   p.ey0 = ey0; p.ey1 = ey1; p.ex0 = ex0; p.ex1 = ex1; p.heads = heads; p.v_length = v_length; p.eps = eps;
   long long total = (long long)NB * Hq * Wq * heads;
-  CFP_REQUIRE(total < (1ll << 31), CFP_ESHAPE, "cfp_attn_apply: too many (token, head) pairs");
+  CFP_REQUIRE(total < (1ll << 31), CFP_ESHAPE, std::string(who) + ": too many (token, head) pairs");
   p.fheads = make_fastdiv((unsigned)heads); p.fwq = make_fastdiv((unsigned)Wq); p.fhq = make_fastdiv((unsigned)Hq);
   p.fqth = make_fastdiv((unsigned)qth); p.fqtw = make_fastdiv((unsigned)qtw);
   const int js = total < g_ap_split_below ? (d >= 32 ? 8 : d >= 16 ? 4 : d >= 8 ? 2 : 1) : 1;
-  CFP_REQUIRE(total * js < (1ll << 31), CFP_ESHAPE, "cfp_attn_apply: too many lanes");
+  CFP_REQUIRE(total * js < (1ll << 31), CFP_ESHAPE, std::string(who) + ": too many lanes");
   const long long lanes = total * js;
   int blocks = (int)((lanes + 255) / 256 > 8192 ? 8192 : (lanes + 255) / 256);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-#define AP_LAUNCH(T, D, JS) hipLaunchKernelGGL((attn_apply_kernel<T, D, JS>), dim3(blocks), dim3(256), 0, s, p)
+#define AP_LAUNCH(T, D, JS) do { if (rec) hipLaunchKernelGGL((attn_apply_kernel<T, D, JS, true>), dim3(blocks), dim3(256), 0, s, p); \
+                                 else hipLaunchKernelGGL((attn_apply_kernel<T, D, JS, false>), dim3(blocks), dim3(256), 0, s, p); } while (0)
 #define AP_SWITCH(T) switch (d) { case 4: AP_LAUNCH(T, 4, 1); break; \
                                   case 8: if (js > 1) AP_LAUNCH(T, 8, 2); else AP_LAUNCH(T, 8, 1); break; \
                                   case 16: if (js > 1) AP_LAUNCH(T, 16, 4); else AP_LAUNCH(T, 16, 1); break; \
@@ -296,5 +335,20 @@ extern "C" int cfp_attn_apply(const void* q, int q_ld, const float* kv, const fl
   if (dtype == CFP_BF16) { AP_SWITCH(bf16_t) } else if (dtype == CFP_F16) { AP_SWITCH(f16_t) } else { AP_SWITCH(float) }
 #undef AP_SWITCH
 #undef AP_LAUNCH
-  return cfp_check_launch("cfp_attn_apply");
+  return cfp_check_launch(who);
+}
+
+extern "C" int cfp_attn_apply(const void* q, int q_ld, const float* kv, const float* ksum, void* out, int out_ld,
+                              int NB, int Hq, int Wq, int qth, int qtw, int ey0, int ey1, int ex0, int ex1,
+                              float v_length, float eps, int heads, int d, int dtype, cfp_stream_t stream) {
+  return attn_apply_impl(q, q_ld, kv, ksum, out, out_ld, NB, Hq, Wq, qth, qtw, ey0, ey1, ex0, ex1, v_length, nullptr, eps, heads, d, dtype,
+                         stream, "cfp_attn_apply");
+}
+
+extern "C" int cfp_attn_apply_dev(const void* q, int q_ld, const float* kv, const float* ksum, void* out, int out_ld,
+                                  int NB, int Hq, int Wq, int qth, int qtw, const int* rec, float eps, int heads, int d, int dtype,
+                                  cfp_stream_t stream) {
+  CFP_REQUIRE(rec && (reinterpret_cast<uintptr_t>(rec) & 3) == 0, CFP_EINVAL, "cfp_attn_apply_dev: bad record pointer");
+  return attn_apply_impl(q, q_ld, kv, ksum, out, out_ld, NB, Hq, Wq, qth, qtw, 0, 0, 0, 0, 1.f, rec, eps, heads, d, dtype, stream,
+                         "cfp_attn_apply_dev");
 }

@@ -508,26 +508,55 @@ struct ResizeP {
   int zn, p1, p2, accumulate, B, C;
   float scale_y, scale_x;
   FastDiv fcv, fdw, fdh;      // element index -> (b, dy, dx, channel vector) without 64-bit divisions (the first version's four cost more than the taps)
+  const int* rec;             // DEV only (last: the scalar instantiation's argument offsets stay): the zone record, see cfp_resize_bilinear_dev
+  int rec_side;
 };
 
-template <typename T>
+// DEV: the moving rectangle comes from the int32[9] zone record in device memory (uniform loads) instead of the host's integers; p.dh x p.dw
+// is then the extent the launch ITERATES over -- the whole destination map, which no record changes -- and the element code below is the
+// scalar instantiation's own, fed the record's rectangle and the scales computed here with the host's float32 expression.
+template <typename T, bool DEV>
 __global__ __launch_bounds__(256) void resize_kernel(ResizeP p) {
   constexpr int VE = Vec<T>::N;
   const T* __restrict__ src = reinterpret_cast<const T*>(p.src);
   T* __restrict__ dst = reinterpret_cast<T*>(p.dst);
+  int sy0 = p.sy0, sx0 = p.sx0, sh = p.sh, sw = p.sw, dy0 = p.dy0, dx0 = p.dx0, dh = p.dh, dw = p.dw;
+  float scale_y = p.scale_y, scale_x = p.scale_x;
+  if constexpr (DEV) {
+    const int* __restrict__ rec = p.rec;
+    if (p.rec_side == 0) { sy0 = rec[0]; sx0 = rec[1]; sh = rec[2]; sw = rec[3]; }      // crop: rectangle of the source map -> whole destination
+    else { dy0 = rec[0]; dx0 = rec[1]; dh = rec[2]; dw = rec[3]; }                        // paste: whole source -> rectangle of the destination
+    scale_y = dh > 1 ? (float)(sh - 1) / (float)(dh - 1) : 0.f;
+    scale_x = dw > 1 ? (float)(sw - 1) / (float)(dw - 1) : 0.f;
+  }
   const unsigned total = (unsigned)p.B * p.dh * p.dw * p.fcv.d;      // < 2^31: host check
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
     unsigned t, cvu, q, dxu, bu, dyu;
     fd_rowcol(i, p.fcv, t, cvu);
     fd_rowcol(t, p.fdw, q, dxu);
     fd_rowcol(q, p.fdh, bu, dyu);
-    const int cv = (int)cvu, dx = (int)dxu, dy = (int)dyu, b = (int)bu;
-    const int oy = p.dy0 + dy, ox = p.dx0 + dx;
+    const int cv = (int)cvu, b = (int)bu;
+    int dx = (int)dxu, dy = (int)dyu;
+    if constexpr (DEV) {
+      if (p.rec_side != 0) {      // the launch walks the destination map: keep the rectangle's pixels
+        dy -= dy0; dx -= dx0;
+        if (dy < 0 || dy >= dh || dx < 0 || dx >= dw) continue;
+      } else if (sh <= 0 || sw <= 0) {      // empty source rectangle: the crop is all zeros
+        if (!p.accumulate) {
+          float z[VE];
+#pragma unroll
+          for (int e = 0; e < VE; ++e) z[e] = 0.f;
+          Vec<T>::store(dst + ((long long)(b * p.Hd + dy) * p.Wd + dx) * p.dst_ld + cv * VE, z);
+        }
+        continue;
+      }
+    }
+    const int oy = dy0 + dy, ox = dx0 + dx;
     if (oy < 0 || oy >= p.Hd || ox < 0 || ox >= p.Wd) continue;
     // source coordinate inside the source rectangle (torch: src = scale * dst_index)
-    const float fy = p.scale_y * (float)dy, fx = p.scale_x * (float)dx;
+    const float fy = scale_y * (float)dy, fx = scale_x * (float)dx;
     const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < p.sh - 1 ? 1 : 0), x1 = x0 + (x0 < p.sw - 1 ? 1 : 0);
+    const int y1 = y0 + (y0 < sh - 1 ? 1 : 0), x1 = x0 + (x0 < sw - 1 ? 1 : 0);
     const float ly1 = fy - (float)y0, lx1 = fx - (float)x0;
     const float ly0 = 1.f - ly1, lx0 = 1.f - lx1;
     float tap[4][VE];
@@ -540,7 +569,7 @@ __global__ __launch_bounds__(256) void resize_kernel(ResizeP p) {
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
         const int ry = ys[a], rx = xs[c];              // rectangle coordinates
-        const int gy = p.sy0 + ry, gx = p.sx0 + rx;    // source-map coordinates
+        const int gy = sy0 + ry, gx = sx0 + rx;        // source-map coordinates
         ok[a * 2 + c] = gy >= 0 && gy < p.Hs && gx >= 0 && gx < p.Ws;
         const int gyc = min(max(gy, 0), p.Hs - 1), gxc = min(max(gx, 0), p.Ws - 1);
         sp[a * 2 + c] = src + ((long long)(b * p.Hs + gyc) * p.Ws + gxc) * p.src_ld + cv * VE;
@@ -887,11 +916,43 @@ extern "C" int cfp_resize_bilinear(const void* src, int src_ld, int Hs, int Ws, 
   long long total = (long long)B * dh * dw * (C / ve);
   CFP_REQUIRE(total < (1ll << 31), CFP_ESHAPE, "cfp_resize_bilinear: too many elements");
   p.fcv = make_fastdiv((unsigned)(C / ve)); p.fdw = make_fastdiv((unsigned)dw); p.fdh = make_fastdiv((unsigned)dh);
+  p.rec = nullptr; p.rec_side = 0;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == CFP_BF16) hipLaunchKernelGGL(resize_kernel<bf16_t>, dim3(ew_blocks(total)), dim3(256), 0, s, p);
-  else if (dtype == CFP_F16) hipLaunchKernelGGL(resize_kernel<f16_t>, dim3(ew_blocks(total)), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL(resize_kernel<float>, dim3(ew_blocks(total)), dim3(256), 0, s, p);
+  if (dtype == CFP_BF16) hipLaunchKernelGGL((resize_kernel<bf16_t, false>), dim3(ew_blocks(total)), dim3(256), 0, s, p);
+  else if (dtype == CFP_F16) hipLaunchKernelGGL((resize_kernel<f16_t, false>), dim3(ew_blocks(total)), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((resize_kernel<float, false>), dim3(ew_blocks(total)), dim3(256), 0, s, p);
   return cfp_check_launch("cfp_resize_bilinear");
+}
+
+extern "C" int cfp_resize_bilinear_dev(const void* src, int src_ld, int Hs, int Ws, void* dst, int dst_ld, int Hd, int Wd, const int* rec,
+                                       int rec_side, const uint8_t* zone_valid, int zn, int p1, int p2, int accumulate, int B, int C,
+                                       int dtype, cfp_stream_t stream) {
+  CHECK_DTYPE("cfp_resize_bilinear_dev");
+  const int ve = vec_elems(dtype);
+  CFP_REQUIRE(src && dst && rec && aligned16(src) && aligned16(dst) && (reinterpret_cast<uintptr_t>(rec) & 3) == 0, CFP_EINVAL,
+              "cfp_resize_bilinear_dev: bad pointer");
+  CFP_REQUIRE(B > 0 && C > 0 && C % 8 == 0 && Hs > 0 && Ws > 0 && Hd > 0 && Wd > 0 && (rec_side == 0 || rec_side == 1) &&
+                  src_ld % ve == 0 && dst_ld % ve == 0 && src_ld >= C && dst_ld >= C,
+              CFP_ESHAPE, "cfp_resize_bilinear_dev: bad shape");
+  // the zone flags are indexed by the SOURCE rectangle's coordinates: the whole source map with the record on the destination side (checked
+  // here); the record's own extent on the source side, which the caller checks on the host (the kernel clamps the zone index either way)
+  CFP_REQUIRE(!zone_valid || (zn > 0 && p1 > 0 && p2 > 0 && (rec_side == 0 || (Hs <= zn * p1 && Ws <= zn * p2))), CFP_ESHAPE,
+              "cfp_resize_bilinear_dev: zone grid smaller than the source rectangle");
+  ResizeP p;
+  p.src = src; p.dst = dst; p.zone_valid = zone_valid;
+  p.src_ld = src_ld; p.Hs = Hs; p.Ws = Ws; p.sy0 = 0; p.sx0 = 0; p.sh = Hs; p.sw = Ws;
+  p.dst_ld = dst_ld; p.Hd = Hd; p.Wd = Wd; p.dy0 = 0; p.dx0 = 0; p.dh = Hd; p.dw = Wd;      // the walked extent: the whole destination map
+  p.zn = zn; p.p1 = p1; p.p2 = p2; p.accumulate = accumulate; p.B = B; p.C = C;
+  p.scale_y = 0.f; p.scale_x = 0.f;                                                          // computed on the device from the record
+  long long total = (long long)B * Hd * Wd * (C / ve);
+  CFP_REQUIRE(total < (1ll << 31), CFP_ESHAPE, "cfp_resize_bilinear_dev: too many elements");
+  p.fcv = make_fastdiv((unsigned)(C / ve)); p.fdw = make_fastdiv((unsigned)Wd); p.fdh = make_fastdiv((unsigned)Hd);
+  p.rec = rec; p.rec_side = rec_side;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (dtype == CFP_BF16) hipLaunchKernelGGL((resize_kernel<bf16_t, true>), dim3(ew_blocks(total)), dim3(256), 0, s, p);
+  else if (dtype == CFP_F16) hipLaunchKernelGGL((resize_kernel<f16_t, true>), dim3(ew_blocks(total)), dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((resize_kernel<float, true>), dim3(ew_blocks(total)), dim3(256), 0, s, p);
+  return cfp_check_launch("cfp_resize_bilinear_dev");
 }
 
 static int add_rowtable_impl(const void* in, int in_ld, const float* table, void* out, int out_ld, int rows, int C, int H, int W, int Wt,

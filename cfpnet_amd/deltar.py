@@ -25,6 +25,7 @@ import torch.nn as nn
 
 from . import spec, weights
 from .config import args as _global_args
+from .geometry import static_zone_key
 
 
 def _flag(ns, name, default):
@@ -127,7 +128,7 @@ class Deltar(_Store):
         self._eval_caps: Dict = {}
         self._eval_offs = None            # int32[3, 2] on the device: the positional-table windows the captured graphs read
         self._eval_offs_host = None
-        self._sig_cache = None
+        self._sig_cache: Dict = {}        # id(patch_info) -> (patch_info, full signature, static key)
 
     # -- reference API ------------------------------------------------------------------
     def _get_name(self):
@@ -222,14 +223,23 @@ class Deltar(_Store):
         """Eval forward as a HIP-graph replay.  Two kinds of graph per input geometry and output-ring slot: one that reads PRIVATE copies
         of the inputs (any caller: three device copies, then the replay) and -- from the second consecutive call with the very same
         device tensors on -- one that reads the CALLER'S tensors in place: that replay is pure host logic + one graph launch, no torch
-        kernel, and sees whatever the tensors hold at that moment (the reference's latency loop, evaluate_time.py:73-82)."""
+        kernel, and sees whatever the tensors hold at that moment (the reference's latency loop, evaluate_time.py:73-82).
+
+        The input geometry is the STATIC key: tensor shapes, zone_num, the patch sizes and the output flags.  The first zone rectangle seen
+        for a key is served by graphs that hold it in their kernel arguments (a caller whose zone grid never moves runs exactly those).
+        When a forward arrives with the same key and another rectangle -- a sensor whose registration moves the grid from frame to frame
+        (zjuL5.py:106) -- the key is served from then on by graphs that read the rectangle from a device record
+        (`Engine.capture(dynamic_zones=True)`): one capture per ring slot for every rectangle, instead of one per rectangle."""
         rgb, add = input_data["rgb"], input_data["additional"]
         pinfo = add["patch_info"]
-        if self._sig_cache is None or self._sig_cache[0] is not pinfo:      # the same dict object again (kept alive here): same integers
-            self._sig_cache = (pinfo, _patch_signature(pinfo))
+        sig = self._sig_cache.get(id(pinfo))
+        if sig is None or sig[0] is not pinfo:      # the same dict object again (kept alive here): same integers
+            if len(self._sig_cache) >= 16:
+                self._sig_cache.clear()
+            sig = self._sig_cache[id(pinfo)] = (pinfo, _patch_signature(pinfo), static_zone_key(pinfo))
         # the positional windows (random per forward below the table size: fusion.py:87-91) are NOT part of the key: the graphs read them
         # from a device buffer, rewritten only when the drawn values change (never at 480x640, where they are all zero)
-        key = (tuple(rgb.shape), tuple(add["hist_data"].shape), self._sig_cache[1], bool(return_prob), bool(return_unc))
+        key = (tuple(rgb.shape), tuple(add["hist_data"].shape), sig[2], bool(return_prob), bool(return_unc))
         if self._eval_offs is None or self._eval_offs.device != eng.device:
             self._eval_offs = torch.zeros(3, 2, dtype=torch.int32, device=eng.device)
             self._eval_offs_host = (0,) * 6
@@ -241,9 +251,14 @@ class Deltar(_Store):
         pos_offsets = self._eval_offs_views
         st = self._eval_caps.get(key)
         if st is None:
-            if len(self._eval_caps) >= 4:                      # a handful of geometries at most: each pins its output ring
+            if len(self._eval_caps) >= 4:                      # a handful of static keys at most: each pins its output ring
                 self._eval_caps.pop(next(iter(self._eval_caps)))
-            st = self._eval_caps[key] = {"calls": 0, "last": None, "owned": {}, "adopted": {}}
+            st = self._eval_caps[key] = {"calls": 0, "last": None, "owned": {}, "adopted": {}, "rect": sig[1], "dynamic": False}
+        if not st["dynamic"] and sig[1] != st["rect"]:         # the rectangle moved: this key's graphs read it from the device from now on
+            st["dynamic"] = True
+            st["owned"].clear()
+            st["adopted"].clear()
+        dyn = st["dynamic"]
         m = add["mask"]
         ptrs = None
         if (rgb.is_cuda and rgb.device == eng.device and rgb.dtype == torch.float32 and rgb.is_contiguous() and add["hist_data"].device == eng.device
@@ -254,19 +269,28 @@ class Deltar(_Store):
         st["calls"] += 1
         same = ptrs is not None and ptrs == st["last"]
         st["last"] = ptrs
+        ring = max(1, int(self.eval_out_ring))
+        # a dynamic capture is good for every rectangle to come, so the whole ring is captured at once: a sensor loop pays for its captures
+        # in the one forward that saw the rectangle move, not in the `ring` forwards after it
+        slots = [s for s in range(ring) if s != slot] + [slot] if dyn else [slot]
         if same:
-            h = st["adopted"].get((ptrs, slot))
-            if h is None:
-                if len(st["adopted"]) >= 2 * max(1, int(self.eval_out_ring)):
+            if (ptrs, slot) not in st["adopted"]:
+                if len(st["adopted"]) >= 2 * ring:
                     st["adopted"].clear()
-                eng.capture(input_data, return_prob=return_prob, pos_offsets=pos_offsets, adopt_inputs=True, uncertainty=return_unc)
-                h = st["adopted"][(ptrs, slot)] = eng._graph
-            eng._graph, eng._slots = h, None
-            return eng.replay()
+                for s in slots:
+                    if (ptrs, s) not in st["adopted"]:
+                        eng.capture(input_data, return_prob=return_prob, pos_offsets=pos_offsets, adopt_inputs=True, uncertainty=return_unc,
+                                    dynamic_zones=dyn)
+                        st["adopted"][(ptrs, s)] = eng._graph
+            eng._graph, eng._slots = st["adopted"][(ptrs, slot)], None
+            return eng.replay(patch_info=pinfo) if dyn else eng.replay()
         h = st["owned"].get(slot)
         if h is None:
-            eng.capture(input_data, return_prob=return_prob, pos_offsets=pos_offsets, uncertainty=return_unc)
-            h = st["owned"][slot] = eng._graph
+            for s in slots:
+                if s not in st["owned"]:
+                    eng.capture(input_data, return_prob=return_prob, pos_offsets=pos_offsets, uncertainty=return_unc, dynamic_zones=dyn)
+                    st["owned"][s] = eng._graph
+            h = st["owned"][slot]
         eng._graph, eng._slots = h, None
         return eng.replay(input_data)
 
@@ -278,8 +302,7 @@ def _patch_signature(pinfo, rectangle: bool = True) -> tuple:
     """The batch geometry a training capture is specific to; `rectangle=False` (dynamic zone geometry): only the zone count and
     the per-zone token extents, which no grid offset changes."""
     if not rectangle:
-        return tuple(tuple(int(v) for v in torch.as_tensor((pinfo[s] if s in pinfo else pinfo[float(s)])["patch_size"]).reshape(-1).tolist())
-                     for s in (4, 8, 16)) + (tuple(int(v) for v in torch.as_tensor(pinfo["zone_num"]).reshape(-1).tolist()),)
+        return static_zone_key(pinfo)
     out = []
     for s in (4, 8, 16):
         e = pinfo[s] if s in pinfo else pinfo[float(s)]

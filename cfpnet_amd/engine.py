@@ -23,7 +23,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from . import hip, ops, spec
-from .geometry import FusionGeometry, gsa_keys
+from .geometry import FUSION_SCALES, FusionGeometry, gsa_keys, static_zone_key, zone_records as _zone_records
 from .ops import Act
 
 _BN_EPS = 1e-5
@@ -642,8 +642,10 @@ class Engine:
         return bufs[key]
 
     def _fusion(self, plan, name: str, x: Act, feat1: Act, zone_valid: torch.Tensor, geo: FusionGeometry, B, H, W, out: Act,
-                pos_offset, taps):
-        """fusion.py:52-188."""
+                pos_offset, taps, rec: Optional[torch.Tensor] = None):
+        """fusion.py:52-188.  `rec`: this scale's int32[9] zone record on the device -- the three launches that depend on the zone
+        rectangle (crop, paste, DAPM pair) then read it there instead of taking `geo`'s integers, so the launch list is the same for
+        every rectangle of one zone_num / patch_size."""
         D, (Hm, Wm), lk = self.fusion[name]
         p = f"decoder.{name}"
         ws = spec.window_size((Hm, Wm))
@@ -684,13 +686,20 @@ class Engine:
             if ln == "hist2image":
                 zin = self._act(plan, f"{name}.zin", Mz, 2 * D)
                 zsrc = tok[cur].slice(0, D) if self.change_embedding else emb0
-                ops.resize_bilinear(zsrc, H, W, rect, zin.slice(0, D), gh, gw, (0, 0, gh, gw), B)
+                if rec is None:
+                    ops.resize_bilinear(zsrc, H, W, rect, zin.slice(0, D), gh, gw, (0, 0, gh, gw), B)
+                else:
+                    ops.resize_bilinear(zsrc, H, W, None, zin.slice(0, D), gh, gw, (0, 0, gh, gw), B, rec=rec, rec_side=0)
                 zout = self._act(plan, f"{name}.zout", Mz, D)
                 self._loftr(plan, f"{name}.x2i", l, zin, Mz, src, B * Z * N, spec.X2I_HEADS, zout,
                             dict(groups=B * Z, NB=B * Z, Hk=1, Wk=N, th=1, tw=N, clip=(0, 1, 0, N), count_pad=False, v_length=float(N)),
                             dict(NB=B, Hq=gh, Wq=gw, qth=geo.p1, qtw=geo.p2), pre=plan.get("x2i_kv", {}).get((name, i)))
-                ops.resize_bilinear(zout, gh, gw, (0, 0, gh, gw), tok[cur].slice(0, D), H, W, rect, B, zone_valid=zone_valid,
-                                    zn=geo.zone_num, p1=geo.p1, p2=geo.p2, accumulate=not self.no_skip_inside)
+                if rec is None:
+                    ops.resize_bilinear(zout, gh, gw, (0, 0, gh, gw), tok[cur].slice(0, D), H, W, rect, B, zone_valid=zone_valid,
+                                        zn=geo.zone_num, p1=geo.p1, p2=geo.p2, accumulate=not self.no_skip_inside)
+                else:
+                    ops.resize_bilinear(zout, gh, gw, (0, 0, gh, gw), tok[cur].slice(0, D), H, W, None, B, zone_valid=zone_valid,
+                                        zn=geo.zone_num, p1=geo.p1, p2=geo.p2, accumulate=not self.no_skip_inside, rec=rec, rec_side=1)
             elif ln == "image":
                 nh, nw = math.ceil(H / ws), math.ceil(W / ws)
                 self._loftr(plan, f"{name}.lsa", l + ".lga.encoder_layer", tok[cur], M, None, 0, spec.TWINS_HEADS, tok[cur ^ 1].slice(0, D),
@@ -728,9 +737,13 @@ class Engine:
                 kv = self._f32(plan, f"{name}.dapm.kv", B * heads * d * d)
                 ks = self._f32(plan, f"{name}.dapm.ks", B * heads * d)
                 wsb = self._f32(plan, f"{name}.dapm.ws", ops.attn_kv_ws_floats(B, H, W, H, W, heads, d))
-                ops.attn_kv_reduce(qb.slice(D, D), qb.slice(2 * D, D), kv, ks, wsb, B, H, W, H, W, (y0, y1, x0, x1), False,
-                                   float(max(n_in, 1)), heads, d)
-                ops.attn_apply(qb.slice(0, D), kv, ks, xin.slice(D, D), B, H, W, H, W, (y0, y1, x0, x1), float(max(n_in, 1)), heads, d)
+                if rec is None:
+                    ops.attn_kv_reduce(qb.slice(D, D), qb.slice(2 * D, D), kv, ks, wsb, B, H, W, H, W, (y0, y1, x0, x1), False,
+                                       float(max(n_in, 1)), heads, d)
+                    ops.attn_apply(qb.slice(0, D), kv, ks, xin.slice(D, D), B, H, W, H, W, (y0, y1, x0, x1), float(max(n_in, 1)), heads, d)
+                else:
+                    ops.attn_kv_reduce(qb.slice(D, D), qb.slice(2 * D, D), kv, ks, wsb, B, H, W, H, W, None, False, None, heads, d, rec=rec)
+                    ops.attn_apply(qb.slice(0, D), kv, ks, xin.slice(D, D), B, H, W, H, W, None, None, heads, d, rec=rec)
                 c1 = self._act(plan, f"{name}.dapm.c1", M, D)
                 self._cv(t + ".conv1", xin, c1, B, H, W, 3)
                 self._cv(t + ".conv2", c1, tok[cur ^ 1].slice(0, D), B, H, W, 3, residual=xin.slice(0, D))
@@ -819,7 +832,7 @@ class Engine:
 
     # ------------------------------------------------------------------------------ HIP graph
     def capture(self, input_data: dict, *, return_prob: bool = True, pos_offsets: Optional[dict] = None, lanes: int = 1,
-                inflight: int = 1, adopt_inputs: bool = False, uncertainty: bool = False):
+                inflight: int = 1, adopt_inputs: bool = False, uncertainty: bool = False, dynamic_zones: bool = False):
         """Record the whole forward for this input shape into HIP graphs.  The launch list is static (all
         data-dependent geometry is host-side integers), so replaying costs one graph launch instead of ~280 kernel
         launches.  With `lanes` > 1 every batch lane gets its OWN graph, captured on and replayed from its own stream
@@ -835,12 +848,26 @@ class Engine:
         hold at that moment, with no copy in front of it (`Deltar.forward` uses this when it is called with the same tensors again).
 
         `uncertainty`: as in `forward` -- the captured forward also writes the uncertainty map, and this call, `replay` and
-        `replay_async` return (edges, pred, prob, unc) instead of the 3-tuple."""
+        `replay_async` return (edges, pred, prob, unc) instead of the 3-tuple.
+
+        `dynamic_zones`: the capture owns an int32[3, 9] record of the batch zone rectangle (`forward(zone_records=)`) and `replay`
+        rewrites it from the `patch_info` it is given, so ONE capture serves every rectangle that shares the static key
+        (`geometry.static_zone_key`: zone_num and the patch sizes) -- a sensor whose registration moves the zone grid from frame to
+        frame.  `lanes` share the one record (the rectangle is reduced over the whole batch); `inflight` > 1 is refused: every slot would
+        need its own.  `adopt_inputs` composes: the tensors are the caller's, the record is the engine's (`replay(patch_info=...)`)."""
+        if dynamic_zones and inflight > 1:
+            raise ValueError("capture(dynamic_zones=True) with inflight > 1: each in-flight slot would need its own zone record; use inflight=1")
         dev = self.device
         add = input_data["additional"]
         B = input_data["rgb"].shape[0]
         H, W = input_data["rgb"].shape[-2:]
         lanes = max(1, min(lanes, B))
+        zones = None
+        if dynamic_zones:
+            host = _zone_records(add["patch_info"], H, W)                  # validates (ValueError) before anything is written
+            zones = {"buf": torch.from_numpy(host).to(dev), "host": host.tobytes(), "key": static_zone_key(add["patch_info"]), "hw": (H, W),
+                     "seen": {}, "pinned": {}}
+        zrec = zones["buf"] if zones else None
         self._slots = None
         self._slot_next = 0
         if inflight > 1:
@@ -880,13 +907,15 @@ class Engine:
             st.wait_stream(cur)
             with torch.cuda.stream(st):
                 for _ in range(2):      # warm-up: allocates every buffer of the lane's plan, sets kernel attributes
-                    self.forward(subs[i], return_prob=return_prob, pos_offsets=pos_offsets, lane=i, out=outs[i], uncertainty=uncertainty)
+                    self.forward(subs[i], return_prob=return_prob, pos_offsets=pos_offsets, lane=i, out=outs[i], uncertainty=uncertainty,
+                                 zone_records=zrec)
             torch.cuda.synchronize(dev)
             g = torch.cuda.CUDAGraph()
             self._capturing = True
             try:
                 with torch.cuda.graph(g, stream=st):
-                    self.forward(subs[i], return_prob=return_prob, pos_offsets=pos_offsets, lane=i, out=outs[i], uncertainty=uncertainty)
+                    self.forward(subs[i], return_prob=return_prob, pos_offsets=pos_offsets, lane=i, out=outs[i], uncertainty=uncertainty,
+                                 zone_records=zrec)
             finally:
                 self._capturing = False
             graphs.append(g)
@@ -894,8 +923,34 @@ class Engine:
         self._lane = 0
         self._lanes_active = 1
         result = (edges, pred, prob, unc) if uncertainty else (edges, pred, prob)
+        if zones:
+            static["zones"] = zones
         self._graph = (graphs, static, result)
         return result
+
+    def _update_zone_record(self, zones: dict, pinfo):
+        """Bring a dynamic capture's device record up to `pinfo`: host integers, and when they differ from what the record holds one
+        asynchronous copy from pinned memory on the current stream (behind the previous replay, ahead of the next) -- no device
+        synchronise, no host wait.  A pinned tensor is written once, before its first copy, and never again; pinned tensors are kept
+        per RECORD (its 108 bytes), so a caller that builds a new `patch_info` every frame allocates one only for a rectangle not seen
+        before.  The integers of a `patch_info` object seen before are not derived again (a few dicts are kept alive for that)."""
+        ent = zones["seen"].get(id(pinfo))
+        if ent is None or ent[0] is not pinfo:
+            if static_zone_key(pinfo) != zones["key"]:
+                raise ValueError(f"replay: zone_num / patch_size {static_zone_key(pinfo)} differ from the captured {zones['key']}: "
+                                 "this input needs a capture of its own")
+            host = _zone_records(pinfo, *zones["hw"])
+            if len(zones["seen"]) >= 16:
+                zones["seen"].clear()
+            ent = zones["seen"][id(pinfo)] = (pinfo, host.tobytes())      # keeps pinfo alive: its id stays its own
+        if ent[1] != zones["host"]:
+            pinned = zones["pinned"].get(ent[1])
+            if pinned is None:
+                if len(zones["pinned"]) >= 64:
+                    zones["pinned"].clear()      # a dropped tensor's pending copy stays valid: the pinned allocator frees a block only after its copies
+                pinned = zones["pinned"][ent[1]] = torch.frombuffer(bytearray(ent[1]), dtype=torch.int32).view(len(FUSION_SCALES), -1).pin_memory()
+            zones["buf"].copy_(pinned, non_blocking=True)
+            zones["host"] = ent[1]
 
     def plan_mode(self, throughput: bool):
         """Which of the two kernel plans the convolutions launched from now on follow: the default one, fitted on isolated timings, or the
@@ -1024,8 +1079,10 @@ class Engine:
                 self.capture(input_data, return_prob=return_prob, pos_offsets=pos_offsets, inflight=n)
         return (kind, n), times
 
-    def replay(self, input_data: Optional[dict] = None):
-        """Re-run the captured forward; `input_data` (same shapes) is copied into the static inputs."""
+    def replay(self, input_data: Optional[dict] = None, *, patch_info=None):
+        """Re-run the captured forward; `input_data` (same shapes) is copied into the static inputs.  A `dynamic_zones` capture also
+        takes the zone rectangle of `input_data`'s `patch_info` -- or of `patch_info` alone, for adopted inputs that are read in place --
+        and raises ValueError when its zone_num / patch sizes are not the captured ones."""
         if self._slots:
             out, ev = self.replay_async(input_data)
             torch.cuda.current_stream(self.device).wait_event(ev)
@@ -1035,6 +1092,11 @@ class Engine:
         graphs, static, out = self._graph
         dev = self.device
         cur = torch.cuda.current_stream(dev)
+        zones = static.get("zones")
+        if zones is not None:
+            pinfo = patch_info if patch_info is not None else (input_data["additional"]["patch_info"] if input_data is not None else None)
+            if pinfo is not None:
+                self._update_zone_record(zones, pinfo)      # before any copy: a refused geometry leaves the capture as it was
         if input_data is not None:
             static["rgb"].copy_(input_data["rgb"], non_blocking=True)
             static["additional"]["hist_data"].copy_(input_data["additional"]["hist_data"], non_blocking=True)
@@ -1069,7 +1131,7 @@ class Engine:
     @torch.no_grad()
     def forward(self, input_data: dict, *, return_prob: bool = True, pos_offsets: Optional[dict] = None,
                 taps: Optional[dict] = None, img_features: Optional[Sequence[torch.Tensor]] = None, lane: int = 0,
-                out: Optional[tuple] = None, uncertainty: bool = False):
+                out: Optional[tuple] = None, uncertainty: bool = False, zone_records: Optional[torch.Tensor] = None):
         """Eval-mode forward.  Returns (bin_edges [B,n+1] f32, pred [B,1,H/2,W/2] f32, prob [B,n,H/2,W/2] | None).
         `lane` selects an independent set of scratch buffers / side stream (forward_lanes); `out` = preallocated
         (edges, pred, prob) views to write into.
@@ -1077,7 +1139,14 @@ class Engine:
         `uncertainty=True` returns a fourth tensor (and takes it as out[3]): unc [B,3,H/2,W/2] float32 in every numerics mode, the planes
         hip.UNC_STD (standard deviation of the bin distribution, metres), hip.UNC_ENTROPY (nats) and hip.UNC_PMAX (largest bin
         probability), written by the head kernel from the values its softmax holds -- three output planes instead of the n of `prob`
-        (`return_prob=False` composes with it); edges, pred and prob are bit-identical to the call without it."""
+        (`return_prob=False` composes with it); edges, pred and prob are bit-identical to the call without it.
+
+        `zone_records`: int32[3, 9] on the device, `geometry.zone_records(patch_info, H, W)` -- the batch zone rectangle of the three
+        fusion scales is then read from it by the kernels instead of being frozen into their arguments (what `capture(dynamic_zones=True)`
+        records); `patch_info` still supplies zone_num and patch_size.  Results are bit-identical to the call without it."""
+        if zone_records is not None:
+            assert (zone_records.dtype == torch.int32 and tuple(zone_records.shape) == (len(FUSION_SCALES), 9) and zone_records.is_contiguous()
+                    and zone_records.device == self.device), "zone_records: int32[3, 9] on the engine's device"
         self._lane = lane
         side = self._lane_streams[lane][1] if lane in self._lane_streams else self._side
         if not self.use_side_stream or self._lanes_active > 1:
@@ -1135,7 +1204,8 @@ class Engine:
             Wm = self.fusion[name][1][1]
             geo = FusionGeometry.from_patch_info(pinfo, self.base_resolution[1] / Wm)      # fusion.py:41 (the stride: 16 / 8 / 4)
             assert geo.zone_num * geo.zone_num == Z
-            self._fusion(plan, name, x, feat, zone_valid, geo, B, hh, ww, out, pos_offsets.get(name, (0, 0)), taps)
+            rec = zone_records[FUSION_SCALES.index(round(self.base_resolution[1] / Wm))] if zone_records is not None else None
+            self._fusion(plan, name, x, feat, zone_valid, geo, B, hh, ww, out, pos_offsets.get(name, (0, 0)), taps, rec)
 
         def up(i, src: Act, hs_, ws_, hd, wd, first_only=False):
             M = B * hd * wd

@@ -209,6 +209,48 @@ def zone_record(patch_info, scale, H: int, W: int) -> np.ndarray:
     return np.array([g.sy_wo, g.sx_wo, g.tzh, g.tzw, y0, y1, x0, x1, (y1 - y0) * (x1 - x0)], dtype=np.int32)
 
 
+def static_zone_key(patch_info) -> tuple:
+    """What a captured forward that reads its zone rectangle from device records is still specific to: the zone count and the
+    per-zone token extents (`patch_size`) at the three fusion scales.  No translation of the zone grid changes it, and neither
+    do the pad sizes: the overhang is a zero-extended read."""
+    def leaf(v):
+        return tuple(int(x) for x in _as_np(v).reshape(-1).tolist())
+    return tuple(leaf(_get(patch_info, s)["patch_size"]) for s in (4, 8, 16)) + (leaf(patch_info["zone_num"]),)
+
+
+def check_zone_records(records, patch_info, scales=FUSION_SCALES) -> None:
+    """Host-side check of the records a dynamic capture is fed -> ValueError, at any scale, for (a) an empty batch rectangle
+    (tzh <= 0 or tzw <= 0): the scalar-argument launches refuse it (`sh > 0 && dh > 0`), a record-reading launch cannot, it
+    writes zeros / nothing; (b) a sample whose own zone rectangle is larger than the zone grid it is resampled from (more than
+    zone_num * patch_size tokens).  (b) is a NEW restriction of the dynamic path, not a mirror of a launch check: the static
+    launches resample any extent (the paste reads the whole grid, the crop passes no zone flags), so a frame like that is served
+    by a static graph and refused once its key has turned dynamic.  No contiguous zone grid produces one (its extent is at most
+    ceil(zone_num * pitch / scale) <= zone_num * patch_size).  The grid bound is per SAMPLE: the batch rectangle is the union over the samples
+    (fusion.py:75-84), which may be wider than one grid when their zone grids sit apart, and the static path resamples that too;
+    for a single rect set the union is the sample's own rectangle.  Host integers."""
+    zn = int(_as_np(patch_info["zone_num"]).reshape(-1)[0])
+    for r, s in zip(np.asarray(records).reshape(len(scales), ZONE_REC_LEN), scales):
+        info = _get(patch_info, s)
+        ps = _as_np(info["patch_size"]).reshape(-1, 2)
+        idx = _as_np(info["index_wo_pad"]).reshape(-1, 4)
+        gh, gw = zn * int(ps[:, 0].max()), zn * int(ps[:, 1].max())
+        if int(r[2]) <= 0 or int(r[3]) <= 0:
+            raise ValueError(f"empty zone rectangle of {int(r[2])} x {int(r[3])} tokens at scale 1/{s}: nothing to resample onto the "
+                             f"{gh} x {gw} zone grid")
+        tzh, tzw = int((idx[:, 2] - idx[:, 0]).max()), int((idx[:, 3] - idx[:, 1]).max())
+        if tzh > gh or tzw > gw:
+            raise ValueError(f"zone rectangle of {tzh} x {tzw} tokens at scale 1/{s} does not fit the {gh} x {gw} zone grid "
+                             f"(zone_num {zn}, patch_size {int(ps[:, 0].max())} x {int(ps[:, 1].max())})")
+
+
+def zone_records(patch_info, H: int, W: int, scales=FUSION_SCALES) -> np.ndarray:
+    """Collated `patch_info` of an H x W input -> int32[len(scales), ZONE_REC_LEN], one validated `zone_record` per fusion scale
+    (the rows the record-reading inference kernels take).  Host integers only."""
+    recs = np.stack([zone_record(patch_info, s, *token_hw(H, W, s)) for s in scales])
+    check_zone_records(recs, patch_info, scales)
+    return recs
+
+
 def offsets_patch_info(offsets, zone_layout, image_hw: Tuple[int, int], cache: Optional[Dict] = None) -> Dict:
     """Collated patch_info of a batch whose sample b has its zone grid shifted by offsets[b] pixels in y and in x
     (dataloader.py:94-103); `zone_layout` = tof.zone_layout(...) = (zone_num, zone_px, sy0, sx0).  `cache`: offset ->

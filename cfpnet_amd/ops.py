@@ -378,13 +378,24 @@ def attn_kv_ws_floats(NB, Hk, Wk, th, tw, heads, d) -> int:
     return int(hip.load().cfp_attn_kv_ws_floats(NB, Hk, Wk, th, tw, heads, d))
 
 
-def attn_kv_reduce(k: Act, v: Act, kv, ksum, ws, NB, Hk, Wk, th, tw, clip, count_pad, v_length, heads, d):
+def attn_kv_reduce(k: Act, v: Act, kv, ksum, ws, NB, Hk, Wk, th, tw, clip, count_pad, v_length, heads, d, rec=None):
+    """`rec` (int32[9] device zone record, geometry.ZONE_REC_FIELDS): the clip rectangle and v_length are read from it on the device;
+    `clip` and `v_length` are then unused (pass None)."""
+    if rec is not None:
+        hip.call("cfp_attn_kv_reduce_dev", k.ptr, k.ld, v.ptr, v.ld, kv.data_ptr(), ksum.data_ptr(), hip.ptr(ws),
+                 NB, Hk, Wk, th, tw, _rec_ptr(rec), int(count_pad), heads, d, k.dt, _s())
+        return
     cy0, cy1, cx0, cx1 = clip
     hip.call("cfp_attn_kv_reduce", k.ptr, k.ld, v.ptr, v.ld, kv.data_ptr(), ksum.data_ptr(), hip.ptr(ws),
              NB, Hk, Wk, th, tw, cy0, cy1, cx0, cx1, int(count_pad), float(v_length), heads, d, k.dt, _s())
 
 
-def attn_apply(q: Act, kv, ksum, out: Act, NB, Hq, Wq, qth, qtw, excl, v_length, heads, d, eps=1e-6):
+def attn_apply(q: Act, kv, ksum, out: Act, NB, Hq, Wq, qth, qtw, excl, v_length, heads, d, eps=1e-6, rec=None):
+    """`rec`: as in attn_kv_reduce -- the exclusion rectangle and v_length come from the device zone record."""
+    if rec is not None:
+        hip.call("cfp_attn_apply_dev", q.ptr, q.ld, kv.data_ptr(), ksum.data_ptr(), out.ptr, out.ld,
+                 NB, Hq, Wq, qth, qtw, _rec_ptr(rec), float(eps), heads, d, q.dt, _s())
+        return
     ey0, ey1, ex0, ex1 = excl
     hip.call("cfp_attn_apply", q.ptr, q.ld, kv.data_ptr(), ksum.data_ptr(), out.ptr, out.ld,
              NB, Hq, Wq, qth, qtw, ey0, ey1, ex0, ex1, float(v_length), float(eps), heads, d, q.dt, _s())
@@ -406,11 +417,24 @@ def loftr_tail(q: Optional[Act], kv, ksum, x: Act, out: Act, w_q, w_merge, w_mlp
              float(ln_eps), NB, Hq, Wq, qth, qtw, float(v_length), float(eps), heads, D, hip.F32X3 if x3 else x.dt, _s())
 
 
+def _rec_ptr(rec) -> int:
+    assert rec.dtype == torch.int32 and rec.numel() == 9 and rec.is_cuda and rec.is_contiguous(), "zone record: int32[9] on the device"
+    return rec.data_ptr()
+
+
 def resize_bilinear(src: Act, Hs, Ws, srect, dst: Act, Hd, Wd, drect, B, zone_valid=None, zn=0, p1=0, p2=0,
-                    accumulate=False):
+                    accumulate=False, rec=None, rec_side=0):
+    """`rec` (int32[9] device zone record): the moving rectangle is read on the device -- `rec_side` 0: it is the SOURCE rectangle and
+    the whole Hd x Wd map is written (`srect` unused); 1: it is the DESTINATION rectangle and the whole Hs x Ws map is read (`drect`
+    unused).  The other rectangle must be the whole map."""
+    assert src.C == dst.C
+    if rec is not None:
+        assert (drect if rec_side == 0 else srect) == ((0, 0, Hd, Wd) if rec_side == 0 else (0, 0, Hs, Ws)), "resize_bilinear(rec=): the fixed side is the whole map"
+        hip.call("cfp_resize_bilinear_dev", src.ptr, src.ld, Hs, Ws, dst.ptr, dst.ld, Hd, Wd, _rec_ptr(rec), int(rec_side),
+                 hip.ptr(zone_valid), zn, p1, p2, int(accumulate), B, src.C, src.dt, _s())
+        return
     sy0, sx0, sh, sw = srect
     dy0, dx0, dh, dw = drect
-    assert src.C == dst.C
     hip.call("cfp_resize_bilinear", src.ptr, src.ld, Hs, Ws, sy0, sx0, sh, sw, dst.ptr, dst.ld, Hd, Wd, dy0, dx0, dh, dw,
              hip.ptr(zone_valid), zn, p1, p2, int(accumulate), B, src.C, src.dt, _s())
 

@@ -59,6 +59,44 @@ def make_inputs(batch: int, height: int = 480, width: int = 640, zone_num: int =
     }
 
 
+def pitched_zone_rects(pitch: float, origin_y: float, origin_x: float, zone_num: int = 8) -> np.ndarray:
+    """A zone_num x zone_num grid of `pitch`-pixel squares with its top-left corner at (origin_y, origin_x), row-major float32
+    (sy, sx, ey, ex) like `centered_zone_rects` -- but pitch and origin may be fractional, as a registered L5 + RGB rig delivers them
+    (the `fr` array of zjuL5.py:106)."""
+    rects = np.zeros((zone_num * zone_num, 4), dtype=np.float32)
+    p, oy, ox = np.float32(pitch), np.float32(origin_y), np.float32(origin_x)
+    for zy in range(zone_num):
+        for zx in range(zone_num):
+            sy, sx = oy + np.float32(zy) * p, ox + np.float32(zx) * p
+            rects[zy * zone_num + zx] = (sy, sx, sy + p, sx + p)
+    return rects
+
+
+def rects_patch_info(rects_per_sample, image_hw: Tuple[int, int] = (480, 640)) -> Dict:
+    """Collated `patch_info` (torch leaves, as `make_inputs` builds it) of a batch whose sample b has the zone rectangles
+    rects_per_sample[b]."""
+    pi = collate_patch_info([patch_info_from_rect_data(r, image_hw) for r in rects_per_sample])
+    patch_info = {s: {k: torch.from_numpy(v) for k, v in pi[s].items()} for s in (4, 8, 16)}
+    patch_info["zone_num"] = torch.from_numpy(pi["zone_num"])
+    return patch_info
+
+
+def moving_zone_frames(n: int, seed: int = SEED, height: int = 480, width: int = 640, batch: int = 1):
+    """`n` seeded frames of a sensor whose 8x8 zone grid moves from frame to frame: pitch in [53, 56] px and origin within +-24 px
+    of the centred grid, both in quarter pixels (exact in float32), so some frames overhang the image.  Every frame has the default
+    grid's zone_num and patch sizes (`geometry.static_zone_key`); the rectangles differ.  Returns a list of
+    {"rect_data": float32 [batch, 64, 4], "patch_info": collated patch_info} (the same rect set for every sample of a frame)."""
+    rng = np.random.default_rng(seed)
+    frames = []
+    for _ in range(n):
+        pitch = 53.0 + 0.25 * int(rng.integers(0, 13))
+        oy = (height - 8 * pitch) / 2 + 0.25 * int(rng.integers(-96, 97))
+        ox = (width - 8 * pitch) / 2 + 0.25 * int(rng.integers(-96, 97))
+        rects = pitched_zone_rects(pitch, oy, ox, 8)
+        frames.append({"rect_data": torch.from_numpy(np.stack([rects] * batch)), "patch_info": rects_patch_info([rects] * batch, (height, width))})
+    return frames
+
+
 def make_img_features(batch: int, height: int = 480, width: int = 640, seed: int = SEED + 1):
     """Stand-in encoder outputs (five maps, 16/40/56/136/232 channels at 1/2 .. 1/32): used to pin
     everything *after* the RGB encoder against the reference, whose encoder cannot run here."""

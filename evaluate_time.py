@@ -10,6 +10,9 @@ reference, on purpose: the datasets are not on this box, so the single input sam
 weights are the deterministic key-addressed set unless `--weight_path` names a checkpoint with the
 reference's state_dict layout.  The model is the HIP engine behind `cfpnet_amd.Deltar`; there is no
 PyTorch fallback.
+
+`--moving_zones N` (N >= 2): the same protocol on the same device tensors, with `patch_info` cycling through N prebuilt
+frames whose zone grid moves (`synthetic.moving_zone_frames`): what a sensor loop with per-frame registration costs.
 """
 import sys
 import time
@@ -25,6 +28,13 @@ def main(argv=None):
     argv = list(argv if argv is not None else sys.argv[1:])
     use_graph = "--eager" not in argv
     argv = [a for a in argv if a != "--eager"]
+    moving = 0
+    if "--moving_zones" in argv:
+        i = argv.index("--moving_zones")
+        if i + 1 >= len(argv) or not argv[i + 1].isdigit() or int(argv[i + 1]) < 2:
+            raise SystemExit("--moving_zones N: N >= 2 frames to cycle through")
+        moving = int(argv[i + 1])
+        del argv[i:i + 2]
     args = config.parse_args(argv)
     if "zjuL5" in str(getattr(args, "test_dataset", "")) or args.n_bins != 256:
         # evaluate_time.py:88-99 forces these for ZJU-L5; they are also the 480x640 benchmark shape
@@ -44,6 +54,12 @@ def main(argv=None):
     model.eval_graphs = use_graph
     model.eval_static_outputs = True          # a latency loop never holds a result past the next forward (evaluate_time.py:73-82)
     run = lambda: model(inp)
+    if moving:
+        frames = synthetic.moving_zone_frames(moving, synthetic.SEED, H, W)
+        variants = [{"rgb": inp["rgb"], "additional": dict(inp["additional"], rect_data=f["rect_data"].to(device), patch_info=f["patch_info"])}
+                    for f in frames]
+        turn = iter(range(10 ** 9))
+        run = lambda: model(variants[next(turn) % moving])
     with torch.no_grad():
         for _ in range(100):
             run()

@@ -282,6 +282,14 @@ int cfp_attn_kv_reduce(const void* k, int k_ld, const void* v, int v_ld, float* 
                        int NB, int Hk, int Wk, int th, int tw, int cy0, int cy1, int cx0, int cx1,
                        int count_pad, float v_length, int heads, int d, int dtype, cfp_stream_t stream);
 
+/* cfp_attn_kv_reduce with the clip rectangle and v_length read from DEVICE memory: rec = the int32[9] zone record of
+ * cfp_zone_crop (sy, sx, tzh, tzw, y0, y1, x0, x1, n_inside); the clip is [rec.y0,rec.y1) x [rec.x0,rec.x1), the zone_mask
+ * rectangle of fusion.py:104, and v_length = max(rec.n_inside, 1) (transformer.py:215-230: DAPM's keys are the inside-zone
+ * tokens).  Grid, split count and workspace depend on the tile only, so a captured graph serves every record. */
+int cfp_attn_kv_reduce_dev(const void* k, int k_ld, const void* v, int v_ld, float* kv, float* ksum, float* ws,
+                           int NB, int Hk, int Wk, int th, int tw, const int* rec, int count_pad, int heads, int d, int dtype,
+                           cfp_stream_t stream);
+
 /* Linear attention, query half (attention.py:48-49):
  *   out[q,h,:] = (Q_q,h . KV[g(q),h]) / (Q_q,h . Ksum[g(q),h] + eps) * v_length,  Q = elu(q)+1
  * Queries live on an [NB, Hq, Wq] grid; g(q) = (b, y / qth, x / qtw).  Queries inside the
@@ -290,6 +298,12 @@ int cfp_attn_kv_reduce(const void* k, int k_ld, const void* v, int v_ld, float* 
 int cfp_attn_apply(const void* q, int q_ld, const float* kv, const float* ksum, void* out, int out_ld,
                    int NB, int Hq, int Wq, int qth, int qtw, int ey0, int ey1, int ex0, int ex1,
                    float v_length, float eps, int heads, int d, int dtype, cfp_stream_t stream);
+
+/* cfp_attn_apply with the exclusion rectangle [rec.y0,rec.y1) x [rec.x0,rec.x1) and v_length = max(rec.n_inside, 1) read
+ * from the device zone record (transformer.py:233-234 with the zone_mask of fusion.py:104), as cfp_attn_kv_reduce_dev. */
+int cfp_attn_apply_dev(const void* q, int q_ld, const float* kv, const float* ksum, void* out, int out_ld,
+                       int NB, int Hq, int Wq, int qth, int qtw, const int* rec, float eps, int heads, int d, int dtype,
+                       cfp_stream_t stream);
 
 /* Fused tail of a LoFTR encoder layer, one launch (bf16 only; D in {32,64,128}, heads in {4,8}):
  *   msg = cfp_attn_apply(q, kv, ksum)                                   attention.py:48-49
@@ -319,6 +333,21 @@ int cfp_resize_bilinear(const void* src, int src_ld, int Hs, int Ws, int sy0, in
                         void* dst, int dst_ld, int Hd, int Wd, int dy0, int dx0, int dh, int dw,
                         const uint8_t* zone_valid, int zn, int p1, int p2, int accumulate,
                         int B, int C, int dtype, cfp_stream_t stream);
+
+/* cfp_resize_bilinear with the moving rectangle read from DEVICE memory: rec = the int32[9] zone record of cfp_zone_crop
+ * (sy, sx, tzh, tzw, y0, y1, x0, x1, n_inside), so one captured graph serves every zone rectangle.
+ *   rec_side 0 -- the crop of fusion.py:136-141: source rectangle (rec.sy, rec.sx, rec.tzh, rec.tzw) of the zero-extended
+ *                 Hs x Ws map -> the whole Hd x Wd destination.
+ *   rec_side 1 -- the paste of fusion.py:144-157: the whole Hs x Ws zone grid -> destination rectangle (rec.sy, rec.sx,
+ *                 rec.tzh, rec.tzw); only its pixels inside the Hd x Wd map are written, zone_valid / accumulate as in
+ *                 cfp_resize_bilinear.
+ * The launch walks the whole destination map whatever the record holds; the scales (sh-1)/(dh-1) are the host's float32
+ * expression evaluated on the device (bit-identical results).  tzh <= 0 or tzw <= 0: the crop writes zeros (adds nothing
+ * with accumulate), the paste writes nothing.  The caller checks the record against the zone grid (tzh <= zn*p1,
+ * tzw <= zn*p2) on the host: a launch cannot. */
+int cfp_resize_bilinear_dev(const void* src, int src_ld, int Hs, int Ws, void* dst, int dst_ld, int Hd, int Wd,
+                            const int* rec, int rec_side, const uint8_t* zone_valid, int zn, int p1, int p2,
+                            int accumulate, int B, int C, int dtype, cfp_stream_t stream);
 
 /* out[r,:] = in[r,:] + table[((r / W) % H + oy) * Wt + (r % W) + ox, :]   (table f32 [*, C])
  * Positional encodings: fusion.py:92-96 (H x W window of the [Hmax*Wmax, D] table) and
