@@ -171,6 +171,9 @@ class Engine:
         self.lkpm_min_rows = int(os.environ.get("CFP_LKPM_MIN_ROWS", "30000"))      # token rows from which the LKPM tail runs fused
         self.sr_ln_fused = os.environ.get("CFP_SR_LN_FUSED", "1") == "1"      # f16x3: the global attention's LayerNorm inside its patch conv (0: a launch of its own)
         self.head_fused = os.environ.get("CFP_HEAD_FUSED", "1") != "0"
+        # decoder.conv0 computed inside the fused head so that `unet` never reaches HBM (cfp_depth_head_conv0_fused);
+        # CFP_HEAD_CONV0=0 runs the pair conv0 launch + cfp_depth_head_fused.
+        self.head_conv0 = os.environ.get("CFP_HEAD_CONV0", "1") != "0"
         # EdgeResidual blocks (encoder stages conv1 / conv2): 3x3 expand + BN + SiLU + 1x1 project + BN (+ skip) as ONE launch with the expanded
         # tensor kept on the chip (cfp_conv3x3_pw_fused), 16-bit modes.  Characters: "1" = the four stride-1 blocks, "2" = the two stride-2
         # blocks, "d" = the decoder's up3.b -> conv1 pair; CFP_ER_FUSED=0 runs every pair as two launches.
@@ -1268,8 +1271,12 @@ class Engine:
         t = up(4, x, ph, pw, hs[0], wsz[0])
         Mh = B * hs[0] * wsz[0]
         HWh = hs[0] * wsz[0]
-        unet = self._act(plan, "unet", Mh, 128)
         fused_head = self.half and self.head_fused and self.n_bins == 256 and HWh % 16 == 0 and HWh >= 128 and "conv_out.wp" in self.P
+        # decoder.conv0 inside the head kernel (csrc/head_conv0.hip): no conv0 launch, no `unet` buffer.  The pair runs for the uncertainty
+        # planes, the hi + lo options, taps and shapes that are not whole 16 x 16 tiles.
+        head_conv0 = (fused_head and self.head_conv0 and taps is None and not uncertainty and self.head_hilo == (False, False)
+                      and os.environ.get("CFP_OLD_SUMS", "0") != "1" and t.C == 32 and ops.depth_head_conv0_fits(hs[0], wsz[0]))
+        unet = None if head_conv0 else self._act(plan, "unet", Mh, 128)
         ram = self._act(plan, "ram", Mh, 128) if (not fused_head or taps is not None) else None
         edges = out[0] if out is not None else torch.empty(B, self.n_bins + 1, dtype=torch.float32, device=dev)
         centers = self._f32(plan, "head.centers", B * self.n_bins)
@@ -1289,7 +1296,7 @@ class Engine:
             ops.bin_regressor(msum, 1, 1.0 / HWh, self.P[h + ".w1x1"], self.P[h + ".r0.w"], self.P[h + ".r0.b"], self.P[h + ".r2.w"],
                               self.P[h + ".r2.b"], self.P[h + ".r4.w"], self.P[h + ".r4.b"], self.min_val, self.max_val, self.norm,
                               edges, centers, B, 128, 256, self.n_bins)
-        if os.environ.get("CFP_OLD_SUMS", "0") != "1":
+        if os.environ.get("CFP_OLD_SUMS", "0") != "1" and not head_conv0:
             self._cv("decoder.conv0", t, unet, B, hs[0], wsz[0], 3)
         if not fused_head:
             self._cv("depth_head.conv3x3", unet, ram, B, hs[0], wsz[0], 3)
@@ -1302,7 +1309,11 @@ class Engine:
         unc = None
         if uncertainty:
             unc = out[3] if out is not None else torch.empty(B, 3, hs[0], wsz[0], dtype=torch.float32, device=dev)
-        if fused_head:
+        if head_conv0:
+            ops.depth_head_conv0_fused(t, self.P["decoder.conv0.w"], self.P["decoder.conv0.s"], self.P["decoder.conv0.t"], self.P[h + ".conv3x3.w"],
+                                       self.P[h + ".conv3x3.s"], self.P[h + ".conv3x3.t"], self.P["conv_out.wp"], self.P["conv_out.t"], centers,
+                                       prob, pred, B, hs[0], wsz[0])
+        elif fused_head:
             # conv3x3 + conv_out + softmax + expectation in one kernel: neither ram nor the logits reach HBM
             ops.depth_head_fused(unet, self.P[h + ".conv3x3.w"], self.P[h + ".conv3x3.s"], self.P[h + ".conv3x3.t"], self.P["conv_out.wp"],
                                  self.P["conv_out.t"], centers, prob, pred, B, hs[0], wsz[0], ram_out=ram, ram_hilo=self.head_hilo[1],

@@ -597,6 +597,22 @@ def depth_head_fused(x: Act, w3, scale3, shift3, wout_perm: torch.Tensor, bias_o
              x.dt, _s())
 
 
+def depth_head_conv0_fits(H: int, W: int) -> bool:
+    """The shapes cfp_depth_head_conv0_fused takes: whole 16 x 16 pixel tiles (ask before graph capture)."""
+    return H % 16 == 0 and W % 16 == 0
+
+
+def depth_head_conv0_fused(t: Act, w0, scale0, shift0, w3, scale3, shift3, wout_perm: torch.Tensor, bias_out, centers, prob, pred, B, H, W,
+                           probe: int = 0):
+    """decoder.conv0 (3x3, 32 -> 128) + depth_head_fused in one launch; `unet` stays on the chip.  prob / pred are bit-identical to
+    conv2d + depth_head_fused.  w0 [128, 9 * 32]; wout_perm = permute_wout(..., hilo=False)."""
+    assert t.C == 32 and t.rows >= B * H * W and tuple(w0.shape) == (128, 9 * 32) and tuple(w3.shape) == (128, 9 * 128)
+    assert tuple(wout_perm.shape) == (1, 256, 128) and wout_perm.dtype == t.buf.dtype and w0.dtype == t.buf.dtype and w3.dtype == t.buf.dtype
+    hip.call("cfp_depth_head_conv0_fused", t.ptr, t.ld, w0.data_ptr(), hip.ptr(scale0), hip.ptr(shift0), w3.data_ptr(), hip.ptr(scale3),
+             hip.ptr(shift3), wout_perm.data_ptr(), bias_out.data_ptr(), centers.data_ptr(), hip.ptr(prob), pred.data_ptr(), B, H, W,
+             probe << 8, t.dt, _s())
+
+
 def hist_encoder(hist: torch.Tensor, blob: torch.Tensor, layout, outs, R: int, pe=(None, None, None), n_pe: int = 0):
     """hist [R] f32, blob f32 parameters, layout = list of 9 (w_off, scale_off, shift_off, cin, cout); outs = three Acts [R, cout];
     pe = optional f32 tables [n_pe, cout] added to the taps (row = sample index % n_pe)."""

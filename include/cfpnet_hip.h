@@ -463,6 +463,18 @@ int cfp_depth_head_fused_stats(const void* x, int x_ld, const void* w3, const fl
                                const void* wout_perm, const float* bias_out, const float* centers, void* prob, float* pred,
                                float* stats, void* ram_out, int B, int H, int W, int flags, int dtype, cfp_stream_t stream);
 
+/* decoder.conv0 + the whole head in one kernel (csrc/head_conv0.hip): unet = conv0(t) (3x3, 32 -> 128, bias, no activation;
+ * decoder.py conv0) feeds cfp_depth_head_fused's chain (decoder.py:22-27, deltar.py:51-61) without reaching HBM.  A workgroup computes the
+ * 18 x 18 halo of `unet` of its 16 x 16 pixel tile from t, rounded to `dtype` exactly as cfp_conv2d_nhwc stores it and zero outside the
+ * image, so prob and pred are those of the two launches bit for bit.  t [B*H*W, t_ld] NHWC 16-bit with 32 channels; w0 [128][3*3*32],
+ * scale0 / shift0 [128] f32 (may be NULL = 1 / 0); the other operands as cfp_depth_head_fused takes them (one Wout plane: no hi + lo
+ * options, no uncertainty planes, no ram_out).  flags: 0.  bf16 / f16 only; H % 16 == 0 and W % 16 == 0, otherwise CFP_ESHAPE (run the
+ * pair); CFP_ESHAPE too if the device does not grant the kernel's 162 944 bytes of LDS. */
+int cfp_depth_head_conv0_fused(const void* t, int t_ld, const void* w0, const float* scale0, const float* shift0, const void* w3,
+                               const float* scale3, const float* shift3, const void* wout_perm, const float* bias_out,
+                               const float* centers, void* prob, float* pred, int B, int H, int W, int flags, int dtype,
+                               cfp_stream_t stream);
+
 /* Fused bin head: logits = x @ w^T + bias never leave the chip:
  *   1x1 conv (Cin -> 256) on the matrix cores, row softmax, expectation, optional prob write.
  * Replaces conv_out (deltar.py:18-19,51) + deltar.py:61.  nbins == 256.  dtype CFP_BF16 / CFP_F16: 16-bit x, w [256][Cin] and prob;

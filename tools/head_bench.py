@@ -3,7 +3,8 @@
 conv_out + softmax) against the one-kernel head (csrc/head_fused.hip) with its exactness islands on / off; back-to-back inside a
 replayed HIP graph, alone and with 4 copies side by side (the throughput mode of bench.py).  Every head also with the per-pixel
 uncertainty planes (`stats`: std, entropy, pmax -- 3 float32 planes) on, with and without `prob`; a block for the default numerics
-(f32x3: conv_out + softmax in bin_head_x3_kernel) and, for context, the torch post-processing of a float32 `prob` that the planes replace."""
+(f32x3: conv_out + softmax in bin_head_x3_kernel) and, for context, the torch post-processing of a float32 `prob` that the planes replace.
+`--conv0`: instead, decoder.conv0 + head in one kernel (csrc/head_conv0.hip) against the conv0 launch + depth_head_fused, with its phase probes."""
 import os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -12,9 +13,57 @@ from cfpnet_amd import hip, ops
 from cfpnet_amd.engine import concurrent_streams
 from _gtime import graph_time_us, graph_time_us_concurrent
 DEV = "cuda:0"
+CONV0 = "--conv0" in sys.argv      # only the block that sets cfp_depth_head_conv0_fused against the pair it replaces
+if CONV0:
+    sys.argv.remove("--conv0")
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 H, W = 240, 320
 M = B * H * W
+
+
+def conv0_block():
+    """decoder.conv0 + head in one kernel (csrc/head_conv0.hip) against the pair: the conv0 launch (halo kernel, 32 -> 128) + depth_head_fused.
+    Probes of the one-kernel form: 8 = phase 0 only (t halo + conv0 into LDS), 2 = ... + GEMM1, 4 = ... + GEMM2, 1 = zero-record descriptors."""
+    streams = concurrent_streams(DEV, 4)
+    fl0 = 2.0 * M * 128 * 9 * 32
+    for dt in (torch.bfloat16, torch.float16):
+        t = ops.Act(torch.randn(M, 32, device=DEV).to(dt), 0, 32)
+        w0 = (torch.randn(128, 9 * 32, device=DEV) * 0.06).to(dt)
+        b0 = torch.randn(128, device=DEV) * 0.5
+        w3 = (torch.randn(128, 9 * 128, device=DEV) * 0.03).to(dt)
+        sh = torch.zeros(128, device=DEV)
+        wp0 = ops.permute_wout(torch.randn(256, 128) * 0.3, dt, hilo=False).to(DEV)
+        bo = torch.zeros(256, device=DEV)
+        cen = torch.sort(torch.rand(B, 256, device=DEV) * 10, dim=1)[0].contiguous()
+        unet = ops.new_act(M, 128, dt, DEV)
+        prob = torch.empty(B, 256, H * W, dtype=dt, device=DEV)
+        pred = torch.empty(M, device=DEV)
+
+        def conv0():
+            ops.conv2d(t, w0, None, b0, unet, B, H, W, 3, 3, 1, 1, 1, H, W)
+
+        def head():
+            ops.depth_head_fused(unet, w3, None, sh, wp0, bo, cen, prob, pred, B, H, W, ram_hilo=False)
+
+        def pair():
+            conv0()
+            head()
+
+        def one(probe=0, pr=prob):
+            ops.depth_head_conv0_fused(t, w0, None, b0, w3, None, sh, wp0, bo, cen, pr, pred, B, H, W, probe=probe)
+        rows = [("conv0 launch (3x3, 32 -> 128)", conv0), ("depth_head_fused", head), ("the pair: conv0 + depth_head_fused", pair),
+                ("one kernel: depth_head_conv0_fused", one), ("one kernel, no prob output", lambda: one(pr=None)),
+                ("probe: phase 0 only", lambda: one(8)), ("probe: phase 0 + GEMM1", lambda: one(2)), ("probe: phase 0 + GEMM1 + GEMM2", lambda: one(4)),
+                ("probe: no fetch (zero-record descriptors)", lambda: one(1))]
+        for name, fn in rows:
+            a = graph_time_us(fn, calls=6, replays=5)
+            a4 = graph_time_us_concurrent(fn, streams, calls=6, replays=5)
+            print(f"{str(dt):16s} {name:52s} alone {a:7.1f} us   4 side by side {a4:7.1f} us per call", flush=True)
+
+
+if CONV0:
+    conv0_block()
+    sys.exit(0)
 FL = 2.0 * M * 128 * (9 * 128 + 256)
 for dt in (torch.bfloat16, torch.float16):
     x = ops.Act((torch.randn(M, 128, device=DEV)).to(dt), 0, 128)
