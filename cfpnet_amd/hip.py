@@ -20,6 +20,7 @@ TOF_SAMPLE_UNIFORM, TOF_SAMPLE_ICDF = 0, 1
 HEAD_WOUT_HILO, HEAD_RAM_HILO = 1, 2
 UNC_STD, UNC_ENTROPY, UNC_PMAX = 0, 1, 2     # planes of the heads' uncertainty output (CFP_UNC_*)
 SPARS_STD, SPARS_ENTROPY, SPARS_PMAX, SPARS_ORACLE_RMSE, SPARS_ORACLE_ABSREL = range(5)     # rankings of cfp_unc_sparsification (CFP_SPARS_*)
+RENDER_DEPTH, RENDER_GT, RENDER_ABS_ERR, RENDER_REL_ERR = range(4)     # `what` of cfp_render_depth (CFP_RENDER_*)
 REGION_ALL, REGION_FOV_IN, REGION_FOV_OUT, REGION_ZONE_VALID, REGION_ZONE_INVALID = range(5)     # region axis of cfp_eval_metrics_regions (CFP_REGION_*)
 CONV_PER_IMAGE, CONV_W2, CONV_IN_FLIGHT, CONV_X3, CONV_WS_TICKETS = 1, 2, 4, 8, 16
 CONV_TICKET_BYTES = 4096     # CFP_CONV_TICKET_BYTES
@@ -89,6 +90,9 @@ SIGNATURES = {
     "cfp_depth_unproject": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p]),
     "cfp_points_compact_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "cfp_points_compact": (_i, [_p, _p, _i, _i, _i, _i, _f, _f, _p, _i, _i, _ll, _f, _f, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "cfp_render_depth": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _f, _f, _i, _f, _f, _p, _p, _ll, _i, _p, _f, _p]),
+    "cfp_render_zones": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p, _i, _p, _ll, _i, _p]),
+    "cfp_render_rgb": (_i, [_p, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _i, _i, _p, _ll, _i, _p]),
     "cfp_conv2d_wgrad_ws_bytes": (_sz, [_i, _i, _i]),
     "cfp_grad_absmax": (_i, [_p, _i, _ll, _i, _p, _p]),
     "cfp_grad_scale": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _i, _p]),

@@ -34,6 +34,15 @@ default) whose depth lies strictly inside (min_depth, max_depth) and -- with `--
 (pixels of the full-resolution image) defaults to the ZJU-L5 sensor's.  One more stderr line reports the mean number of points kept; the
 `Metrics:` lines do not change.  The `--points_*` switches and `--intrinsics` without `--save_points` are an error.
 
+`--save_pred`, `--save_gt`, `--save_rgb`, `--save_error_map` and `--save_for_demo` (the reference's picture switches) paint on the device
+(`cfpnet_amd/render.py`: `cfp_render_depth`, `cfp_render_zones`, `cfp_render_rgb`) and write, per evaluated image index i, into `--save_dir D`
+(default `tmp`): `D/pred_<i>.png` (colour) and `D/pred_<i>_mm.png` (16-bit millimetres of the clipped, enlarged prediction the metrics
+evaluate); `D/gt_<i>.png` (invalid pixels white); `D/rgb_<i>.png`; `D/error_<i>.png` (absolute error over [0, `--error_max` = 1.0 m] in `jet`,
+with `--error_rel` the relative error over [0, `--error_max`]); `D/demo_<i>.png` (image | image under the ToF zones / prediction | error).
+`--vis_cmap NAME` (magma_r, magma, viridis, turbo, jet) and `--vis_range a,b` (default min_depth,max_depth) apply to the prediction, the
+ground truth and the zones.  One more stderr line reports the number of files; stdout does not change.  `--vis_cmap`, `--vis_range`,
+`--error_max` and `--error_rel` without one of the five switches, and an unknown table name, are errors raised before the model is built.
+
 Differences on purpose: the xlsx report (openpyxl) is not written; `--synthetic N` evaluates N seeded synthetic samples
 when the dataset is not on the box (without it a missing `filenames_file_eval` is an error); weights are the
 deterministic key-addressed set unless `weights/<name>/<selected_epoch>.pt` (the reference's location) exists or
@@ -67,6 +76,16 @@ def _intrinsics(v):
     return k
 
 
+def _vis_range(v):
+    r = tuple(float(x) for x in v.split(","))
+    if len(r) != 2 or not r[0] < r[1]:
+        raise ValueError(f"--vis_range takes a,b with a < b, got '{v}'")
+    return r
+
+
+PICTURE_SWITCHES = ("save_pred", "save_gt", "save_rgb", "save_error_map", "save_for_demo")
+
+
 def main(argv=None):
     from cfpnet_amd import config, data, geometry, metrics
     from cfpnet_amd.deltar import make_model
@@ -87,8 +106,22 @@ def main(argv=None):
     intrinsics = _pop(argv, "--intrinsics", None, _intrinsics)
     if not save_points and (points_stride is not None or points_max_std is not None or points_normals or intrinsics is not None):
         raise ValueError("--points_stride, --points_max_std, --points_normals and --intrinsics need --save_points")
+    vis_cmap = _pop(argv, "--vis_cmap", None)
+    vis_range = _pop(argv, "--vis_range", None, _vis_range)
+    error_max = _pop(argv, "--error_max", None, float)
+    error_rel = _pop(argv, "--error_rel", False, None)
     save_spars = "--save_dir" in argv
     args = config.parse_args(argv) if argv else config.defaults()
+    pics = [k for k in PICTURE_SWITCHES if getattr(args, k, False)]
+    if not pics and (vis_cmap is not None or vis_range is not None or error_max is not None or error_rel):
+        raise ValueError("--vis_cmap, --vis_range, --error_max and --error_rel need one of --" + ", --".join(PICTURE_SWITCHES))
+    if pics:
+        from cfpnet_amd import render
+        vis_cmap = vis_cmap or "magma_r"
+        render.colormap_table(vis_cmap)                  # an unknown table is an error before anything is built
+        if error_max is not None and not error_max > 0:
+            raise ValueError(f"--error_max must be positive, got {error_max}")
+        error_max = 1.0 if error_max is None else error_max
     area_in, area_out = bool(getattr(args, "zone_area_only", False)), bool(getattr(args, "outside_zone_area_only", False))
     if area_in and area_out:
         raise ValueError("--zone_area_only and --outside_zone_area_only exclude each other")
@@ -127,6 +160,10 @@ def main(argv=None):
         rgb_mean = torch.from_numpy(data.IMAGENET_MEAN).to(device)[None, :, None, None]
         rgb_std = torch.from_numpy(data.IMAGENET_STD).to(device)[None, :, None, None]
         n_points = 0
+    if pics:
+        os.makedirs(args.save_dir, exist_ok=True)
+        vmin, vmax = vis_range or (float(args.min_depth), float(args.max_depth))
+        n_pics = 0
     want_std = save_points and points_max_std is not None
     n_img, t0 = 0, time.perf_counter()
     with torch.no_grad():
@@ -162,6 +199,26 @@ def main(argv=None):
                 for b, one in enumerate(pc.split()):
                     n_points += pointcloud.write_ply(os.path.join(args.save_dir, f"points_{n_img + b}.ply"), one["points"], one["normals"],
                                                      one["colors"])
+            if pics:
+                lo, hi, add = float(args.min_depth), float(args.max_depth), inp["additional"]
+                todo = []
+                if "save_pred" in pics:
+                    todo += [("pred_{}.png", render.depth_image(pred, gt.shape[-2:], lo, hi, vmin, vmax, vis_cmap)),
+                             ("pred_{}_mm.png", render.depth_u16(pred, gt.shape[-2:], lo, hi))]
+                if "save_gt" in pics:
+                    todo.append(("gt_{}.png", render.gt_image(gt, lo, hi, vmin, vmax, vis_cmap)))
+                if "save_rgb" in pics:
+                    todo.append(("rgb_{}.png", render.rgb_image(inp["rgb"])))
+                if "save_error_map" in pics:
+                    todo.append(("error_{}.png", render.error_image(pred, gt, lo, hi, "rel" if error_rel else "abs", error_max)))
+                if "save_for_demo" in pics:
+                    todo.append(("demo_{}.png", render.demo_panel(inp["rgb"], pred, add["hist_data"], add["rect_data"], add["mask"], gt, lo, hi,
+                                                                  vmin, vmax, vis_cmap, error_kind="rel" if error_rel else "abs",
+                                                                  error_max=error_max)))
+                for pattern, t in todo:                      # uint8 / uint16 leave the device, never the float32 prediction
+                    for b, a in enumerate(t.cpu().numpy()):
+                        render.write_png(os.path.join(args.save_dir, pattern.format(n_img + b)), a)
+                        n_pics += 1
             n_img += img.shape[0]
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
@@ -190,6 +247,8 @@ def main(argv=None):
                            "images": [[regions.image_counts[r][q] for q in regions.labels] for r in metrics.REGIONS]}, f)
     if save_points:
         print(f"points: {n_points / max(n_img, 1):.1f} kept per image on average, written to {args.save_dir}/points_<index>.ply", file=sys.stderr)
+    if pics:
+        print(f"pictures: {n_pics} files written to {args.save_dir}", file=sys.stderr)
     print(f"{n_img} images in {dt:.2f} s ({n_img / dt:.1f} images/s incl. host-side sample generation/decoding)", file=sys.stderr)
     return res
 

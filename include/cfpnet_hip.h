@@ -661,6 +661,55 @@ int cfp_points_compact(const float* points, const float* normals, int H, int W, 
                        float* out_points /* [B][cap][3] */, float* out_normals /* [B][cap][3] or NULL */,
                        int* out_index /* [B][cap] */, int* counts /* [B] */, void* ws, size_t ws_bytes, cfp_stream_t stream);
 
+/* Pictures on the device: what the reference's `colorize` (src/utils/utils.py:44-64) paints on the host after moving the prediction
+ * there, defined on the value the metrics evaluate.  Three entry points, one launch each; no workspace, no atomics, no host
+ * synchronisation, capturable in a graph.  Every float32 operation below is rounded once (no fused multiply-add).
+ *   Output addressing, shared: out is uint8, channel c (0 red, 1 green, 2 blue) of pixel (b, y, x) lies at
+ *           out[b * image_stride + (y * pitch + x) * 3 + c]; pitch >= W in PIXELS, image_stride >= H * pitch * 3 in BYTES (CFP_ESHAPE
+ *           otherwise), so a caller renders into a sub-rectangle of a larger canvas by offsetting the base pointer.  Any byte alignment
+ *           is accepted: when base % 4 == 0, image_stride % 4 == 0 and pitch % 4 == 0 a lane stores the 12 bytes of 4 consecutive
+ *           pixels as whole dwords, otherwise -- and for the W % 4 tail of a row -- bytes; both give the same bytes.  Bytes outside the
+ *           H x W rectangle are never read or written.
+ *   Lookup  colour of a value v under (vmin, vmax, lut), lut [256][3] uint8 on the device -- matplotlib's rule for float input with
+ *           bytes=True:  t = (v - vmin) / (vmax - vmin) * 256.f;  NaN -> (0, 0, 0) (the "bad" colour);  t < 0 -> lut[0];
+ *           t >= 256 -> lut[255];  otherwise lut[(int)t].  vmin < vmax, both finite (CFP_EINVAL otherwise).
+ *
+ * cfp_render_depth: the prediction, the ground truth or their error as a picture and / or as 16-bit integers.
+ *   d       the float32 value cfp_eval_metrics and cfp_depth_unproject see at the pixel in mode 0 (evaluate_all.py:40-41): clip to
+ *           [lo, hi] at model resolution, then the align-corners bilinear blend; interpolate = 0 needs equal sizes.  One implementation
+ *           (csrc/metrics_pred.h): bit for bit.  valid means lo < gt < hi.
+ *   what    CFP_RENDER_DEPTH    v = d                     every pixel painted     gt may be NULL
+ *           CFP_RENDER_GT       v = gt                    painted iff valid       pred may be NULL (Hp, Wp, interpolate are ignored)
+ *           CFP_RENDER_ABS_ERR  v = fabsf(d - gt)         painted iff valid
+ *           CFP_RENDER_REL_ERR  v = fabsf(d - gt) / gt    painted iff valid
+ *           A painted pixel gets the lookup of v, an unpainted one (255, 255, 255) -- the invalid colour of `colorize`, utils.py:60.
+ *   u16_out optional, [B][H][W] contiguous uint16, with DEPTH and GT only:  m = v * u16_scale;  NaN or m <= 0 -> 0;
+ *           m >= 65535 -> 65535;  otherwise (uint16_t)rintf(m), ties to even;  an unpainted pixel -> 0.  u16_scale finite and > 0;
+ *           1000 gives the 16-bit millimetre PNG of NYU / BTS.  Whole dwords when the base is 4-byte aligned and W is even.
+ *   out may be NULL when u16_out is given (lut, vmin, vmax, image_stride and pitch are then ignored); both NULL is CFP_EINVAL. */
+enum { CFP_RENDER_DEPTH = 0, CFP_RENDER_GT = 1, CFP_RENDER_ABS_ERR = 2, CFP_RENDER_REL_ERR = 3 };
+int cfp_render_depth(const float* pred, int Hp, int Wp, const float* gt, int H, int W, int B, int interpolate, float lo, float hi,
+                     int what, float vmin, float vmax, const unsigned char* lut /* [256][3] */, unsigned char* out,
+                     long long image_stride, int pitch, unsigned short* u16_out /* [B][H][W] or NULL */, float u16_scale,
+                     cfp_stream_t stream);
+/* cfp_render_zones: the ToF input drawn over what `out` already holds.  hist [B][Z][S] f32 (the depth samples of a zone, the model's
+ * hist_data), rect [B][Z][4] f32 (sy, sx, ey, ex), mask [B][Z] u8, 1 <= Z <= 256, S >= 1 (CFP_ESHAPE otherwise).
+ *   Zone    pixel (y, x) belongs to the FIRST zone z in index order with sy <= y < ey && sx <= x < ex, compared in float: the
+ *           membership rule of cfp_eval_metrics_regions.  A pixel in no zone is left untouched.
+ *   Colour  c = (0, 0, 0) on the zone's one-pixel border, y < sy + 1 || y >= ey - 1 || x < sx + 1 || x >= ex - 1;  else
+ *           (128, 128, 128) if mask[b][z] == 0;  else the lookup of v = (hist[b][z][0] + ... + hist[b][z][S-1]) / S, summed in index
+ *           order in float32.
+ *   Blend   per channel, in integers: out = (c * alpha + out * (256 - alpha) + 128) >> 8, alpha 0 .. 256 (256 is opaque, 0 changes
+ *           nothing; CFP_EINVAL otherwise). */
+int cfp_render_zones(const float* hist /* [B][Z][S] */, const float* rect /* [B][Z][4] */, const unsigned char* mask /* [B][Z] */,
+                     int Z, int S, int H, int W, int B, float vmin, float vmax, const unsigned char* lut /* [256][3] */, int alpha,
+                     unsigned char* out, long long image_stride, int pitch, cfp_stream_t stream);
+/* cfp_render_rgb: the normalised colour image back to bytes.  rgb [B][3][H][W] f32 on the device; mean, std: HOST arrays of 3 finite
+ * floats, copied into the kernel arguments.  Per channel c:  v = x * std[c] + mean[c];  NaN or v <= 0 -> 0;  v >= 1 -> 255;  otherwise
+ * (uint8_t)rintf(v * 255.f). */
+int cfp_render_rgb(const float* rgb /* [B][3][H][W] */, const float* mean /* host, [3] */, const float* std /* host, [3] */, int H,
+                   int W, int B, unsigned char* out, long long image_stride, int pitch, cfp_stream_t stream);
+
 /* ---- training-step kernels: backward of the dense convolution, batch-statistics BatchNorm --------------------------
  * (the training row of SURVEY.md section 8: cfpnet_amd/autograd_hip.py chains them into the backward of the whole network) */
 
