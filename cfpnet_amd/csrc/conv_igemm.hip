@@ -377,6 +377,29 @@ static int chunk_x3_variant(long long M, int Cin, int Cout, bool tput) {
   if (M >= 30000) return tput ? 38 : 24;
   return -1;
 }
+int g_chunk16 = 1;              // cfp_debug_set key 40: the 16-bit 3x3 convolutions on deep inputs take the chunk kernel (conv3x3_chunk.hip) 0 = never, 1 = where planned,
+                                // 2 = wherever it can run (the 128-channel tile above 64 output channels, the 64-channel tile below)
+// Deep inputs (Cin > 64, Cin % 8 == 0) in the 16-bit modes: which tile of conv3x3_chunk.hip, or -1 = today's plan (implicit GEMM / direct kernel).
+// Fitted on tools/conv_bench.py --chunk at batch 8, alone and with four copies side by side (profiles/conv3x3_chunk_ab.txt; us per call, today's
+// plan three times -> tile 1, the 64-channel tile with three workgroups per CU; tile 0 ties it in flight at 128 output channels and loses alone):
+//                                    alone                          four in flight
+//   153600 px  168 ->  64   58.8 / 59.9 / 60.7 -> 43.1      50.5 / 50.7 / 51.1 -> 38.8
+//    38400 px  312 -> 128   48.1 / 48.5 / 49.0 -> 38.1      38.0 / 38.0 / 38.1 -> 30.4
+//    38400 px  128 -> 128   21.5 / 21.6 / 21.9 -> 18.3      15.1 / 15.1 / 15.2 -> 12.5
+//    38400 px  128 ->  64   15.7 / 15.8 / 16.1 -> 13.9       7.9 /  7.9 /  8.0 ->  6.6
+//     9600 px  392 -> 256   41.9 / 42.5 / 43.2 -> 37.1      21.6 / 22.1 / 22.2 -> 22.7  (stays: the 128 x 128 implicit GEMM)
+//     9600 px  256 -> 256   29.1 / 29.1 / 29.3 -> 23.7      12.4 / 12.4 / 12.4 -> 13.3  (stays)
+//     9600 px  256 -> 128   16.2 / 16.3 / 16.3 -> 18.8  (stays: direct tile 4)     10.4 / 10.6 / 10.6 ->  7.3
+//     9600 px  128 -> 128   10.8 / 10.9 / 10.9 -> 13.4  (stays)                      6.8 /  6.8 /  6.8 ->  5.0
+// Only what was measured moves: 30 000 ... 200 000 pixels, and around 9 600 pixels the wide outputs alone and the narrow ones in flight.
+static int chunk16_variant(long long M, int Cin, int Cout, bool tput) {
+  if (Cin <= 64 || Cin % 8 != 0 || Cout <= 0 || Cout % 8 != 0 || M <= 0 || g_chunk16 == 0) return -1;
+  if (g_chunk16 == 2) return Cout > 64 ? 0 : 1;
+  if (M >= 30000 && M < 200000) return 1;
+  if (M >= 8000 && M < 12000) return (Cout > 128) != tput ? 1 : -1;
+  return -1;
+}
+extern "C" int cfp_conv3x3_chunk_variant(int M, int Cin, int Cout, int in_flight) { return chunk16_variant(M, Cin, Cout, in_flight > 1); }
 static bool halo_wins_s2(long long M, int Cout) { return g_halo == 2 || (g_halo == 1 && g_halo_s2 && M >= 30000 && Cout <= 160); }
 static bool halo_wins(long long M, int Cout, bool tput) {
   if (g_halo == 2) return true;
@@ -405,6 +428,7 @@ extern "C" int cfp_debug_set(int key, int value) {
     case 37: cfp_fold_debug_set(value); return CFP_OK;
     case 38: cfp_attn_apply_debug_set(value); return CFP_OK;
     case 39: cfp_tail16_debug_set(value); return CFP_OK;
+    case 40: g_chunk16 = value; return CFP_OK;
     case 17: g_tput = value; return CFP_OK;
     case 16: g_probe = (g_probe & 16) | value; return CFP_OK;
     case 29: g_x3_ad = value; return CFP_OK;
@@ -583,7 +607,11 @@ extern "C" int cfp_conv2d_plan(int M, int Cout, int K, int KH, int stride, int d
   if (is16(dtype) && !g_use_v1) {
     Plan2 pl = plan2(M, Cout, K, rows_per_batch, B, rows_per_batch <= 0, KH == 3 && stride == 1 && K % 9 == 0);
     const int cin = K / 9;
-    if (KH == 3 && stride == 1 && K % 9 == 0 && cin % 8 == 0 && cin >= 8 && cin <= 64 && Cout % 8 == 0 && Cout <= 512 && rows_per_batch <= 0 &&
+    const int cv = (KH == 3 && stride == 1 && K % 9 == 0 && rows_per_batch <= 0 && g_force_variant < 0) ? chunk16_variant(M, cin, Cout, g_tput != 0) : -1;
+    if (cv >= 0) {
+      if (variant) *variant = 600 + cv;     // conv3x3_chunk.hip
+      if (splits) *splits = 1;
+    } else if (KH == 3 && stride == 1 && K % 9 == 0 && cin % 8 == 0 && cin >= 8 && cin <= 64 && Cout % 8 == 0 && Cout <= 512 && rows_per_batch <= 0 &&
         (g_force_variant < 0 ? halo_wins(M, Cout, g_tput != 0) : g_force_variant >= 300)) {
       if (variant) *variant = 300;          // conv3x3_halo.hip (the tile is chosen from Cout and the pixel count)
       if (splits) *splits = 1;
@@ -752,6 +780,20 @@ static int conv2d_impl(const void* in, int in_ld, const void* w, const float* sc
     if (w2) { pl.gen1 = false; pl.direct = -1; p.k2 = cdiv(p.K, 64); }
     // few input channels, many pixels: the whole-depth halo kernel (conv3x3_halo.hip); cfp_debug_set(0, 300 + v) forces its variant v,
     // any other forced variant / the gen-1 switch keeps the implicit GEMMs (A/B, tests)
+    // deep inputs: the chunk kernel (conv3x3_chunk.hip) where chunk16_variant measured it ahead; cfp_debug_set(0, 600 + v) forces its tile v
+    // and is an error for a problem the kernel does not take, cfp_debug_set(40, 0) keeps every problem on its earlier kernel
+    {
+      const bool forced = g_force_variant >= 600 && g_force_variant < 700;
+      const bool takes = !w2 && c33 && !want_mom && conv3x3_chunk_takes(p);
+      CFP_REQUIRE(!forced || (takes && g_force_variant - 600 < conv3x3_chunk_num_variants()), CFP_EHIP,
+                  "cfp_conv2d_nhwc: the forced chunk variant cannot run this problem");
+      const int cv = forced ? g_force_variant - 600 : (takes && g_force_variant < 0) ? chunk16_variant(p.M, Cin, Cout, tput) : -1;
+      if (cv >= 0) {
+        int rc = conv3x3_chunk_launch(cv, p, s);
+        CFP_REQUIRE(rc == 0, CFP_EHIP, "cfp_conv2d_nhwc: chunk 3x3 kernel launch failed");
+        return cfp_check_launch("cfp_conv2d_nhwc");
+      }
+    }
     const bool c33s2 = KH == 3 && KW == 3 && stride == 2 && !ln_gamma && rpb == 0;
     if (!w2 && (c33 || c33s2) && !want_mom && conv3x3_halo_takes(p) &&
         (g_force_variant < 0 ? (Cin <= 64 && (stride == 1 ? halo_wins(p.M, Cout, tput) : halo_wins_s2(p.M, Cout))) : g_force_variant >= 300)) {

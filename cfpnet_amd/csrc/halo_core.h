@@ -107,6 +107,11 @@ inline size_t halo16_lds(const HaloTileV& t, int stages, int stride, int pp) { r
 inline size_t halo_x3_plane(const HaloTileV& t, int pp) { return (size_t)(t.th + 2) * 18 * pp; }      // = the byte offset of the lo plane
 inline size_t halo_x3_lds(const HaloTileV& t, int pp) { return (size_t)2 * t.wstage + 2 * halo_x3_plane(t, pp); }
 inline size_t chunk_x3_lds(const HaloTileV& t, int nstw, bool single_buffer) { return (size_t)nstw * t.wstage + (single_buffer ? 1 : 2) * 2 * halo_x3_plane(t, 80); }
+// the 16-bit chunk kernel (conv3x3_chunk.hip): three weight stages + one halo buffer of a 64-channel chunk, 128-byte pixels in whole
+// passes of the workgroup's loader (32 pixels)
+constexpr int kChunk16Stages = 3;
+inline size_t chunk16_halo_buf(const HaloTileV& t) { return (size_t)cdiv((t.th + 2) * 18, 32) * 32 * 128; }
+inline size_t chunk16_lds(const HaloTileV& t) { return (size_t)kChunk16Stages * t.wstage + chunk16_halo_buf(t); }
 // PW (fused 3x3 -> 1x1): the padded 1x1 weights [16 ceil(Cout2 / 16)][32 ceil(mid / 32)] must fit one weight stage; the body is the K loop's
 // two stages + halo, or W2 (in stage 0) + the `mid` tile of the tail, whichever is larger; behind it the epilogue constants: scale | shift of
 // the 3x3 [npad each], scale2 | shift2 of the 1x1 [64 each]

@@ -60,6 +60,12 @@ int conv3x3_num_variants();
 void conv3x3_variant_shape(int v, int* th, int* bn);
 int conv3x3_launch(int v, const ConvP& p, hipStream_t s);
 
+// conv3x3_chunk.hip (16-bit, Cin > 64: 64-channel chunks of the halo through LDS, two workgroups per CU)
+int conv3x3_chunk_num_variants();
+size_t conv3x3_chunk_lds(int v);
+bool conv3x3_chunk_takes(const ConvP& p);
+int conv3x3_chunk_launch(int v, const ConvP& p, hipStream_t s);
+
 // conv3x3_halo.hip
 int conv3x3_halo_num_variants();
 void conv3x3_halo_debug_stages(int v);

@@ -163,6 +163,7 @@ SIGNATURES = {
     "cfp_mbconv_plan": (_i, [_i, _i, _i, _i, _i, _p, _p]),
     "cfp_mbconv_expand_dw": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _i, _p]),
     "cfp_conv3x3_pw_fused_variant": (_i, [_i] * 5),
+    "cfp_conv3x3_chunk_variant": (_i, [_i] * 4),
     "cfp_conv3x3_pw_fused": (_i, [_p, _i, _p, _p, _p, _i, _p, _p, _p, _i, _p, _i, _p, _i] + [_i] * 12 + [_p]),
     "cfp_hist_encoder": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "cfp_depth_head_fused": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),

@@ -127,7 +127,9 @@ DIRECT3_TILES = [(8, 128), (8, 64), (16, 64), (16, 32), (8, 32), (16, 16)]
 
 def conv2d_kernel_name(variant: int, splits: int, dt: int) -> str:
     t = {hip.BF16: "bf16", hip.F16: "f16"}.get(dt, "f32")
-    if variant >= 500:
+    if variant >= 600:
+        n = f"conv3x3_chunk<{t},{(128, 64)[variant - 600]}>"
+    elif variant >= 500:
         n = "conv3x3_halo_x3"
     elif variant >= 400:
         bm, bn, st = (GEN2_TILES + X3_ONLY_TILES)[variant - 400]

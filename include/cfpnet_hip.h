@@ -111,10 +111,18 @@ size_t cfp_conv2d_ws_bytes(int M, int Cout, int K, int dtype);
  * tools/conv_bench.py).  *variant: 0..3 = first-generation tiles 256x16 / 256x32 / 128x64 /
  * 128x128 (f32); 100 + v = second-generation (bf16, LDS-DMA staged) variant v; 200 + v = direct 3x3
  * (LDS halo tile) variant v; 400 + v = f16x3 implicit-GEMM variant v, 500 = the f16x3 whole-depth-halo 3x3 kernel (dtype CFP_F32X3: float32
- * storage, CFP_CONV_X3).  *splits = K-splits.  KH/stride describe the filter (K = KH*KH*Cin);
+ * storage, CFP_CONV_X3); 600 + v = tile v of the 16-bit chunk 3x3 kernel (conv3x3_chunk.hip).  *splits = K-splits.  KH/stride describe the filter (K = KH*KH*Cin);
  * rows_per_batch > 0 describes a per_image_weights call (B images of rows_per_batch rows). */
 int cfp_conv2d_plan(int M, int Cout, int K, int KH, int stride, int dtype, int rows_per_batch, int B, int* variant,
                     int* splits);
+
+/* The tile of the 16-bit chunk 3x3 kernel (csrc/conv3x3_chunk.hip: stride 1, more than 64 input channels, 64-channel chunks of the input
+ * halo through LDS; 0 = 128 channels x 8 x 16 pixels, 1 = 64 channels x 8 x 16 pixels) that cfp_conv2d_nhwc runs for a bf16 / f16
+ * 3x3 stride-1 convolution of M = B*Ho*Wo output pixels, or -1 where the problem keeps its implicit GEMM / direct kernel (always for
+ * Cin <= 64 or Cin % 8 != 0).  in_flight = graphs replayed side by side: above 1 the answer is the plan of CFP_CONV_IN_FLIGHT calls.
+ * cfp_debug_set(0, 600 + v) forces tile v (an error for a problem the kernel does not take); cfp_debug_set(40, 0) switches the kernel off
+ * everywhere, 2 runs it wherever it can, 1 is this plan. */
+int cfp_conv3x3_chunk_variant(int M, int Cin, int Cout, int in_flight);
 
 /* First-generation tile choice for (M, Cout): 0 = 256x16, 1 = 256x32, 2 = 128x64, 3 = 128x128. */
 int cfp_conv2d_variant(int M, int Cout);
@@ -123,7 +131,7 @@ int cfp_conv2d_variant(int M, int Cout);
  * key 0 = force second-generation variant v, or 200 + v = direct 3x3 variant v (-1 = automatic), key 1 = force K-splits (-1 = automatic),
  * key 2 = 1 routes bf16 through the first-generation kernel; keys 3 / 4 = depthwise 3x3 channel vectors per
  * workgroup (8 / 16) and output rows per strip (0 = automatic); key 5 = 1 forces the VALU depthwise kernel; key 6 = 16-bit depthwise
- * 3x3 kernel (1 or 2, CFP_EINVAL otherwise); keys 7 and 8 are unused (CFP_EINVAL); keys 9-39 are listed in README.md ("Kernel choices")
+ * 3x3 kernel (1 or 2, CFP_EINVAL otherwise); keys 7 and 8 are unused (CFP_EINVAL); keys 9-40 are listed in README.md ("Kernel choices")
  * and at the dispatch in csrc/conv_igemm.hip.  The depthwise keys change the slot counts of cfp_dwconv3x3_strips / _se_parts too. */
 int cfp_debug_set(int key, int value);
 

@@ -19,6 +19,8 @@ ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--sweep", action="store_true")
 ap.add_argument("--kgroups", action="store_true", help="pointwise problems: the plan against the eight-wave two-K-group tiles (variants 19-21)")
 ap.add_argument("--halo", action="store_true", help="3x3 stride-1 problems with <= 64 input channels only: every conv3x3_halo variant and the plan without that kernel")
+ap.add_argument("--chunk", action="store_true", help="3x3 stride-1 problems with more than 64 input channels only: every conv3x3_chunk tile, the direct "
+                "kernel's 128- and 32-channel tiles and the plan without the chunk kernel (three timings: their spread is the noise a tile has to beat)")
 ap.add_argument("--out", default="gpurun_out/conv_bench.json")
 ap.add_argument("--inflight", type=int, default=1, help="time every candidate with this many copies running side by side on "
                 "probed-concurrent streams (throughput mode) instead of alone")
@@ -68,12 +70,16 @@ def timeit(name, args, reps):
     return graph_time_us(fn, calls=max(4, reps // 2), replays=4)
 
 
+if a.chunk and a.inflight > 1:
+    lib.cfp_debug_set(17, 1)      # side by side the launches follow the in-flight plan: time that plan, with and without the kernel
 nvar = lib.cfp_conv2d_num_variants() if hasattr(lib, "cfp_conv2d_num_variants") else 19
 rows = []
 tot_auto = tot_v1 = tot_best = 0.0
 for key, (name, args, cnt) in uniq.items():
     B, H, W, Cin, Cout, KH, st, Ho, Wo, ln, piw, has_res = key
     if a.halo and not (KH == 3 and st in (1, 2) and Cin <= 64):
+        continue
+    if a.chunk and not (KH == 3 and st == 1 and Cin > 64 and Cin % 8 == 0 and not ln and not piw):
         continue
     if a.kgroups and (ln or B * Ho * Wo * Cout > 9600 * 1400):
         continue
@@ -146,12 +152,24 @@ for key, (name, args, cnt) in uniq.items():
         lib.cfp_debug_set(12, 1)
         lib.cfp_debug_set(0, -1)
         lib.cfp_debug_set(1, -1)
+    if a.chunk:
+        lib.cfp_debug_set(40, 0)                      # today's plan without the chunk kernel, three times
+        for i in range(3):
+            sweep[f"n_off{i}"] = timeit(name, args, a.reps)
+        lib.cfp_debug_set(40, 1)
+        for v, tag in [(600, "c0"), (601, "c1"), (200, "d0"), (204, "d4")]:
+            lib.cfp_debug_set(0, v)
+            try:
+                sweep[tag] = timeit(name, args, a.reps)
+            except RuntimeError:
+                pass
+        lib.cfp_debug_set(0, -1)
     import ctypes
     pv, ps = ctypes.c_int(0), ctypes.c_int(0)
     lib.cfp_conv2d_plan(M, Cout, K, KH, st, 1, Ho * Wo if piw else 0, B, ctypes.byref(pv), ctypes.byref(ps))
     ideal = max(fl / 1.5e15, byts / 5e12) * 1e6 + 1.5
     rows.append(dict(M=M, N=Cout, K=K, k=KH, stride=st, ln=ln, piw=piw, count=cnt, auto_us=t_auto, v1_us=t_v1, best_us=best[0],
-                     best=best[1], plan=("halo" if pv.value >= 300 else f"d{pv.value - 200}" if pv.value >= 200 else f"v{pv.value - 100}/s{ps.value}" if pv.value >= 100 else f"g1.{pv.value}/s{ps.value}"), ideal_us=ideal, gflop=fl / 1e9, sweep=sweep))
+                     best=best[1], plan=(f"c{pv.value - 600}" if pv.value >= 600 else "halo" if pv.value >= 300 else f"d{pv.value - 200}" if pv.value >= 200 else f"v{pv.value - 100}/s{ps.value}" if pv.value >= 100 else f"g1.{pv.value}/s{ps.value}"), ideal_us=ideal, gflop=fl / 1e9, sweep=sweep))
     tot_auto += cnt * t_auto; tot_v1 += cnt * t_v1; tot_best += cnt * best[0]
 
 rows.sort(key=lambda r: -r["auto_us"] * r["count"])
@@ -160,6 +178,7 @@ for r in rows:
     print(f"{r['M']:7d} {r['N']:5d} {r['K']:5d} {r['k']} {r['stride']} {r['count']:2d} {r['auto_us']:8.1f} {r['v1_us']:8.1f} {r['best_us']:8.1f} "
           f"{r['ideal_us']:7.1f}  {r['plan']:9s} {r['best']:10s} {r['gflop'] / r['auto_us'] * 1e-3:7.1f}" + (" LN" if r["ln"] else "") + (" PIW" if r["piw"] else "")
           + ("   " + "  ".join(f"{k}={v:.1f}" for k, v in r["sweep"].items() if k[0] in "hn") if a.halo else "")
+          + ("   " + "  ".join(f"{k}={v:.1f}" for k, v in r["sweep"].items() if k[0] in "cdn") if a.chunk else "")
           + ("   " + "  ".join(f"{k}={v:.1f}" for k, v in r["sweep"].items() if k[0] == "k") if a.kgroups else ""))
 print(f"total per forward: auto {tot_auto / 1e3:.3f} ms, v1 {tot_v1 / 1e3:.3f} ms, best-of-sweep {tot_best / 1e3:.3f} ms, launches {len(calls)}")
 os.makedirs(os.path.dirname(a.out), exist_ok=True)
