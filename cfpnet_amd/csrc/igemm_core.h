@@ -36,6 +36,12 @@ struct ConvP {
                            // the data gradient of a stride-`dil` convolution; H / W stay the REAL input size
 };
 
+// conv_igemm.hip: the first-generation tiles (variant 0..3 = 256x16 / 256x32 / 128x64 / 128x128; dtype = CFP_F32 / CFP_BF16 / CFP_F16), the few-row
+// float32 GEMM (pointwise, M <= 64) and the finishing sum of every split-K GEMM (dtype = the storage type of p.out)
+void igemm1_launch(int variant, int dtype, const ConvP& p, float* slabs, int splits, hipStream_t s);
+void rowgemm_f32_launch(const ConvP& p, hipStream_t s);
+void splitk_reduce_launch(int dtype, const ConvP& p, const float* slabs, int splits, hipStream_t s);
+
 // conv_igemm2.hip
 int igemm2_num_variants();
 void igemm2_variant_shape(int v, int* bm, int* bn, int* stages);

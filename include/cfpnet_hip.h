@@ -112,7 +112,12 @@ size_t cfp_conv2d_ws_bytes(int M, int Cout, int K, int dtype);
  * 128x128 (f32); 100 + v = second-generation (bf16, LDS-DMA staged) variant v; 200 + v = direct 3x3
  * (LDS halo tile) variant v; 400 + v = f16x3 implicit-GEMM variant v, 500 = the f16x3 whole-depth-halo 3x3 kernel (dtype CFP_F32X3: float32
  * storage, CFP_CONV_X3); 600 + v = tile v of the 16-bit chunk 3x3 kernel (conv3x3_chunk.hip).  *splits = K-splits.  KH/stride describe the filter (K = KH*KH*Cin);
- * rows_per_batch > 0 describes a per_image_weights call (B images of rows_per_batch rows). */
+ * rows_per_batch > 0 describes a per_image_weights call (B images of rows_per_batch rows).
+ * The answer is the launch's own decision (one function, csrc/conv_route.hip) for the CANONICAL problem of these arguments: KW = KH, padding 1
+ * for a 3x3 filter and 0 otherwise, channel strides equal to the channel counts, B images of M / B output pixels, no LayerNorm, no residual,
+ * no moments, a sufficient workspace, launches in flight only under cfp_debug_set(17, 1), and -- for the 16-bit types -- a problem within
+ * the second-generation kernel's limits (K <= 16384, operands within 32-bit byte offsets).  300 and 500 are first choices: those two launchers
+ * may decline a problem whose halo does not fit the LDS, and the call then runs the implicit GEMM. */
 int cfp_conv2d_plan(int M, int Cout, int K, int KH, int stride, int dtype, int rows_per_batch, int B, int* variant,
                     int* splits);
 
@@ -132,7 +137,7 @@ int cfp_conv2d_variant(int M, int Cout);
  * key 2 = 1 routes bf16 through the first-generation kernel; keys 3 / 4 = depthwise 3x3 channel vectors per
  * workgroup (8 / 16) and output rows per strip (0 = automatic); key 5 = 1 forces the VALU depthwise kernel; key 6 = 16-bit depthwise
  * 3x3 kernel (1 or 2, CFP_EINVAL otherwise); keys 7 and 8 are unused (CFP_EINVAL); keys 9-40 are listed in README.md ("Kernel choices")
- * and at the dispatch in csrc/conv_igemm.hip.  The depthwise keys change the slot counts of cfp_dwconv3x3_strips / _se_parts too. */
+ * and at the dispatch in csrc/conv_route.hip.  The depthwise keys change the slot counts of cfp_dwconv3x3_strips / _se_parts too. */
 int cfp_debug_set(int key, int value);
 
 /* Depthwise 3x3 convolution, stride 1/2, explicit (TF-"SAME", possibly asymmetric) padding, fused

@@ -291,6 +291,12 @@ def test_conv2d_x3_ticketed_split_k_is_bit_identical_to_the_reduce_launch(varian
         assert torch.equal(got[0], got[1])
         want = torch.stack([x[b * hw:(b + 1) * hw].double() @ w[b].double().t() for b in range(B)]).reshape(B * hw, Cout) * sc.double() + sh.double()
         assert float((got[1].double() - want).abs().max() / want.abs().max()) < 2e-5
+        # the same call without a workspace, and with one too short for the planned splits: un-split (the two-K-group plan of the problem)
+        for ws in (None, torch.empty((sp - 1) * B * hw * Cout, device=DEV)):
+            out = ops.new_act(B * hw, Cout, torch.float32, DEV)
+            ops.conv2d(xa, wx, sc, sh, out, B, hw, 1, 1, 1, 1, 0, 0, hw, 1, hip.ACT_NONE, None, ws, per_image_weights=True)
+            torch.cuda.synchronize()
+            assert float((out.torch().double() - want).abs().max() / want.abs().max()) < 2e-5
     finally:
         lib.cfp_debug_set(0, -1)
         lib.cfp_debug_set(1, -1)
@@ -477,7 +483,7 @@ def test_conv2d_x3_per_image_weights_and_layernorm():
     _x3_close(out.torch().cpu(), ref, "x3 per-image weights")
     # LayerNorm fused into the epilogue (Cout 128 / 64 / 32 / 16: a four-row-wave tile spans the row) and as a second kernel (knob 26 = 0)
     lib = hip.load()
-    for Co, rows in ((128, 300), (128, 40000), (64, 300), (64, 130000), (32, 5000), (16, 777)):
+    for Co, rows in ((128, 300), (128, 40000), (64, 300), (64, 130000), (32, 5000), (16, 777), (256, 300)):      # 256: no tile spans it, a second kernel either way
         xr = rnd(rows, Cin, seed=11)
         w1 = rnd(Co, Cin, seed=12, scale=1 / math.sqrt(Cin))
         g, bt = rnd(Co, seed=5).abs() + 0.5, rnd(Co, seed=6)
@@ -760,6 +766,27 @@ def test_conv3x3_halo_every_variant(variant, dtype):
     assert ops.conv2d_plan(8 * 240 * 320, 16, 360, hip.BF16, 0, 8, 3, 1)[0] == 300
     assert ops.conv2d_plan(8 * 15 * 20, 160, 360, hip.BF16, 0, 8, 3, 1)[0] != 300        # too few pixels: implicit GEMM
     assert ops.conv2d_plan(8 * 120 * 160, 160, 9 * 72, hip.BF16, 0, 8, 3, 1)[0] != 300      # too many input channels
+
+
+def test_conv3x3_halo_forced_variant_that_cannot_run_is_an_error():
+    """cfp_debug_set(0, 300 + v) on a problem the kernel takes but tile v cannot run (no such tile; a stride-2 halo deeper than the LDS):
+    an error, and nothing is launched."""
+    lib = hip.load()
+    dtype = torch.bfloat16
+    try:
+        for force, (B, H, W, Cin, Cout, s) in ((300 + len(HALO_CAP), (1, 12, 16, 16, 16, 1)), (302, (1, 24, 32, 128, 64, 2))):
+            pad = 1 if s == 1 else 0
+            Ho, Wo = (H + 2 * pad - 3) // s + 1, (W + 2 * pad - 3) // s + 1
+            x = ops.Act(torch.ones(B * H * W, Cin, dtype=dtype, device=DEV), 0, Cin)
+            w = torch.ones(Cout, 9 * Cin, dtype=dtype, device=DEV)
+            buf = torch.full((B * Ho * Wo, Cout), 777.0, dtype=dtype, device=DEV)
+            lib.cfp_debug_set(0, force)
+            with pytest.raises(RuntimeError, match="cannot run this problem"):
+                ops.conv2d(x, w, None, None, ops.Act(buf, 0, Cout), B, H, W, 3, 3, s, pad, pad, Ho, Wo, hip.ACT_NONE, None, None)
+            torch.cuda.synchronize()
+            assert bool((buf == 777.0).all()), force
+    finally:
+        lib.cfp_debug_set(0, -1)
 
 
 @pytest.mark.parametrize("dtype", HALF)

@@ -159,12 +159,17 @@ def test_batchnorm_running_statistics_survive_a_non_finite_batch(bad, via_partia
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 @pytest.mark.parametrize("case", [(2, 30, 40, 112, 448, 1, 1), (2, 60, 80, 40, 160, 3, 1), (1, 120, 160, 8, 40, 3, 2), (3, 13, 17, 136, 816, 1, 1),
-                                  (1, 9, 11, 232, 1392, 1, 1), (16, 26, 34, 448, 112, 1, 1), (2, 104, 136, 16, 16, 3, 1), (1, 1, 70, 8, 32, 1, 1)])
+                                  (1, 9, 11, 232, 1392, 1, 1), (16, 26, 34, 448, 112, 1, 1), (2, 104, 136, 16, 16, 3, 1), (1, 1, 70, 8, 32, 1, 1),
+                                  # shapes whose plan (with the "wherever it can run" switch / the forced tile) is the chunk, the halo and the direct
+                                  # 3x3 kernel, none of which writes moments: the call must take the implicit GEMM and report its row tiles
+                                  (1, 12, 16, 72, 64, 3, 1, (40, 2)), (1, 12, 16, 16, 16, 3, 1, (12, 2)), (2, 9, 11, 24, 32, 3, 2, (12, 2)),
+                                  (1, 12, 16, 72, 64, 3, 1, (0, 204))])
 def test_conv_epilogue_moments_feed_batchnorm(case, dtype):
     """cfp_conv2d_nhwc_moments: the conv kernel leaves per-row-tile (mean, M2) of its STORED output; BatchNorm merged from them must equal
     BatchNorm with its own statistics pass over that output (same values, another exact merge order) and torch's batch statistics of it.
     Data with a large common offset (mean >> std): the tile sums are shifted, so nothing cancels."""
-    B, H, W, Cin, Cout, k, s = case
+    B, H, W, Cin, Cout, k, s = case[:7]
+    knob = case[7] if len(case) > 7 else None      # (cfp_debug_set key, value) around the moments call
     pt = pl = (k - 1) // 2 if s == 1 else 0
     Ho, Wo = (H + 2 * pt - k) // s + 1, (W + 2 * pl - k) // s + 1
     x = (rnd(B * H * W, Cin, seed=1) + 3.0).to(dtype).to(DEV)
@@ -173,8 +178,21 @@ def test_conv_epilogue_moments_feed_batchnorm(case, dtype):
     M = B * Ho * Wo
     y1, y2 = torch.empty(M, Cout, dtype=dtype, device=DEV), torch.empty(M, Cout, dtype=dtype, device=DEV)
     A = lambda t: ops.Act(t, 0, t.shape[1])
-    mom, ns, rps = ops.conv2d_moments(A(x), w, bias, A(y1), B, H, W, k, k, s, pt, pl, Ho, Wo)
-    ops.conv2d(A(x), w, None, bias, A(y2), B, H, W, k, k, s, pt, pl, Ho, Wo)
+    lib = hip.load()
+    try:
+        if knob:
+            lib.cfp_debug_set(*knob)
+            assert ops.conv2d_plan(M, Cout, k * k * Cin, ops.DT[dtype], 0, B, k, s)[0] // 100 == {40: 6, 12: 3, 0: 2}[knob[0]]
+        mom, ns, rps = ops.conv2d_moments(A(x), w, bias, A(y1), B, H, W, k, k, s, pt, pl, Ho, Wo)
+    finally:
+        if knob:
+            lib.cfp_debug_set(knob[0], -1 if knob[0] == 0 else 1)
+    try:
+        if knob == (0, 204):
+            lib.cfp_debug_set(0, 14)      # the implicit-GEMM tile a direct-kernel plan takes when statistics are wanted
+        ops.conv2d(A(x), w, None, bias, A(y2), B, H, W, k, k, s, pt, pl, Ho, Wo)
+    finally:
+        lib.cfp_debug_set(0, -1)
     torch.cuda.synchronize()
     assert ns > 0 and (ns - 1) * rps < M <= ns * rps, (ns, rps, M)
     assert torch.equal(y1.view(torch.int16), y2.view(torch.int16)), "the moments epilogue must not change the output"
