@@ -10,6 +10,9 @@ model (sparsification curves, AUSE, AURG; `cfp_unc_sparsification`, `csrc/unc_me
 `region_metrics` / `RunningRegionAverage` split the nine metrics by where a pixel lies relative to the ToF zones (the reference's
 `my_mask`, `src/dataloader/nyu.py:182-187`, and its `--zone_area_only` / `--outside_zone_area_only` flags) and by depth range
 (`cfp_eval_metrics_regions`, `csrc/region_metrics.hip`).
+
+`normal_metrics` / `RunningNormalAverage` rate the geometry: the angle between the surface normal of the prediction and that of the
+ground-truth depth, both formed as `pointcloud.unproject` forms them (`cfp_normal_metrics`, `csrc/normal_metrics.hip`).
 """
 from __future__ import annotations
 
@@ -248,3 +251,76 @@ class RunningRegionAverage:
                 res[region][label] = dict(zip(KEYS, avg)) if count else {}
                 self.image_counts[region][label] = count
         return res
+
+
+NORMAL_METRIC_NAMES = ("mean_deg", "median_deg", "rmse_deg", "frac_11_25", "frac_22_5", "frac_30")   # CFP_NORMAL_* order; column 6 is n_valid
+NORMAL_BINS = 1800                                    # bins of 0.1 degree
+
+
+def normal_metrics(pred: torch.Tensor, gt: torch.Tensor, lo: float, hi: float, intrinsics=None, size=None, hist: bool = False,
+                   angle_map: bool = False):
+    """Surface-normal error of the prediction against the ground truth (`cfp_normal_metrics`, definition in include/cfpnet_hip.h).
+    pred and gt as in `eval_metrics`, in EVALUATE_ALL order; `intrinsics`: (fx, fy, cx, cy) in pixels of the ground-truth grid -- host
+    numbers, used for every image -- or a float32 [B,4] tensor, `pointcloud.ZJUL5_INTRINSICS` by default; `size` = (H, W), if given, must
+    be the ground truth's -> [B,7] f64 on the device: the six metrics in `NORMAL_METRIC_NAMES` order and the valid-pixel count.  With
+    `hist` and / or `angle_map` a tuple: the rows, then the histogram [B,1800] i32 (bins of 0.1 degree), then the angle per pixel
+    [B,H,W] f32 in degrees (NaN where the pixel is not valid), whichever were asked for.  No host synchronisation."""
+    from . import pointcloud
+    if not isinstance(gt, torch.Tensor) or gt.dtype != torch.float32 or not gt.is_cuda:
+        raise ValueError("gt must be a float32 device tensor")
+    pred = pointcloud._pred3(pred)
+    if gt.dim() == 4 and gt.shape[1] == 1:
+        gt = gt[:, 0]
+    if gt.dim() != 3 or min(gt.shape) < 1:
+        raise ValueError(f"gt must be [B,H,W] or [B,1,H,W], got {tuple(gt.shape)}")
+    gt = gt.contiguous()
+    B, Hp, Wp = pred.shape
+    if gt.shape[0] != B:
+        raise ValueError("batch sizes differ")
+    H, W = gt.shape[1:]
+    if size is not None and pointcloud._size(size, Hp, Wp) != (H, W):
+        raise ValueError(f"size must be the ground truth's {(H, W)}, got {tuple(size)}")
+    if not float(lo) < float(hi):
+        raise ValueError(f"empty depth range [{lo}, {hi}]")
+    K = pointcloud._intrinsics(pointcloud.ZJUL5_INTRINSICS if intrinsics is None else intrinsics, B, pred.device)
+    interp = int((Hp, Wp) != (H, W))                      # the rule of eval_metrics in EVALUATE_ALL order
+    nbytes = hip.load().cfp_normal_metrics_ws_bytes(B, H, W)
+    ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=pred.device)
+    out = torch.empty(B, 7, dtype=torch.float64, device=pred.device)
+    h = torch.empty(B, NORMAL_BINS, dtype=torch.int32, device=pred.device) if hist else None
+    amap = torch.empty(B, H, W, dtype=torch.float32, device=pred.device) if angle_map else None
+    hip.call("cfp_normal_metrics", pred.data_ptr(), Hp, Wp, gt.data_ptr(), H, W, B, interp, float(lo), float(hi), K.data_ptr(),
+             ws.data_ptr(), nbytes, out.data_ptr(), hip.ptr(h), hip.ptr(amap), hip.current_stream())
+    if not hist and not angle_map:
+        return out
+    return (out,) + ((h,) if hist else ()) + ((amap,) if angle_map else ())
+
+
+class RunningNormalAverage:
+    """Means of the normal metrics over a data set: `update` takes the [B,7] rows of `normal_metrics` (and optionally the [B,1800]
+    histograms) and keeps them on the device; `get_value` synchronises once and returns the plain means of the six metrics over the
+    images with n_valid > 0 plus "images", their number; `histogram` is the sum of the histograms given, as a list of 1800 ints."""
+
+    def __init__(self):
+        self._rows, self._hist = [], None
+
+    def update(self, rows: torch.Tensor, hist: Optional[torch.Tensor] = None) -> None:
+        if rows.dim() != 2 or rows.shape[1] != 7:
+            raise ValueError(f"rows must be [B,7], got {tuple(rows.shape)}")
+        self._rows.append(rows)
+        if hist is not None:
+            h = hist.to(torch.int64).sum(0)
+            self._hist = h if self._hist is None else self._hist + h
+
+    def get_value(self) -> Dict[str, float]:
+        if not self._rows:
+            return {}
+        rows = [r for r in torch.cat(self._rows, 0).cpu().tolist() if r[6] > 0]      # the only host synchronisation
+        if not rows:
+            return {}
+        res = {k: sum(r[i] for r in rows) / len(rows) for i, k in enumerate(NORMAL_METRIC_NAMES)}
+        res["images"] = len(rows)
+        return res
+
+    def histogram(self):
+        return [0] * NORMAL_BINS if self._hist is None else self._hist.cpu().tolist()

@@ -32,7 +32,15 @@ default) whose depth lies strictly inside (min_depth, max_depth) and -- with `--
 0 of the uncertainty map, metres) is at most S (`cfp_points_compact`), and writes `D/points_<image index>.ply` per image into `--save_dir D`
 (default `tmp`): binary PLY with x y z, the surface normal with `--points_normals`, and the de-normalised RGB.  `--intrinsics fx,fy,cx,cy`
 (pixels of the full-resolution image) defaults to the ZJU-L5 sensor's.  One more stderr line reports the mean number of points kept; the
-`Metrics:` lines do not change.  The `--points_*` switches and `--intrinsics` without `--save_points` are an error.
+`Metrics:` lines do not change.  The `--points_*` switches without `--save_points`, and `--intrinsics` without `--save_points` or
+`--normal_metrics`, are an error.
+
+`--normal_metrics` rates the geometry on the device (`cfp_normal_metrics`): the angle between the surface normal of the prediction and that
+of the ground-truth depth, both formed as `--save_points` forms its normals, over the pixels whose ground truth and its four neighbours are
+valid.  It prints one more line `Normals: {...}` (after `Regions:` and `Uncertainty:` when those are present) with the means of mean_deg,
+median_deg, rmse_deg and the shares below 11.25 / 22.5 / 30 degrees over the images with a valid pixel, rounded to 3 decimals, and the number
+of those images; with `--save_dir D` given it writes `D/normals.json` with the names, the means and the 0.1-degree histogram summed over the
+images.  `--intrinsics` applies.  The other lines do not change.
 
 `--save_pred`, `--save_gt`, `--save_rgb`, `--save_error_map` and `--save_for_demo` (the reference's picture switches) paint on the device
 (`cfpnet_amd/render.py`: `cfp_render_depth`, `cfp_render_zones`, `cfp_render_rgb`) and write, per evaluated image index i, into `--save_dir D`
@@ -104,8 +112,11 @@ def main(argv=None):
     points_max_std = _pop(argv, "--points_max_std", None, float)
     points_normals = _pop(argv, "--points_normals", False, None)
     intrinsics = _pop(argv, "--intrinsics", None, _intrinsics)
-    if not save_points and (points_stride is not None or points_max_std is not None or points_normals or intrinsics is not None):
-        raise ValueError("--points_stride, --points_max_std, --points_normals and --intrinsics need --save_points")
+    normal_metrics = _pop(argv, "--normal_metrics", False, None)
+    if not save_points and (points_stride is not None or points_max_std is not None or points_normals or
+                            (intrinsics is not None and not normal_metrics)):
+        raise ValueError("--points_stride, --points_max_std, --points_normals and --intrinsics need --save_points"
+                         " (--intrinsics also goes with --normal_metrics)")
     vis_cmap = _pop(argv, "--vis_cmap", None)
     vis_range = _pop(argv, "--vis_range", None, _vis_range)
     error_max = _pop(argv, "--error_max", None, float)
@@ -154,6 +165,7 @@ def main(argv=None):
         os.makedirs(args.save_dir, exist_ok=True)
     spars = metrics.RunningSparsification() if unc_metrics else None
     regions = metrics.RunningRegionAverage(range_edges) if want_regions else None
+    normals_avg = metrics.RunningNormalAverage() if normal_metrics else None
     if save_points:
         from cfpnet_amd import pointcloud
         os.makedirs(args.save_dir, exist_ok=True)
@@ -190,6 +202,8 @@ def main(argv=None):
                 avg.update(rows[:, area, 0])             # the region's "all depths" row; images without a valid pixel there are skipped
             else:
                 avg.update(metrics.eval_metrics(pred, gt, float(args.min_depth), float(args.max_depth), mode=metrics.EVALUATE_ALL))
+            if normal_metrics:
+                normals_avg.update(*metrics.normal_metrics(pred, gt, float(args.min_depth), float(args.max_depth), intrinsics, hist=True))
             if save_points:
                 pc = pointcloud.point_cloud(pred, intrinsics or pointcloud.ZJUL5_INTRINSICS, size=gt.shape[-2:], lo=float(args.min_depth),
                                             hi=float(args.max_depth), depth_range=(float(args.min_depth), float(args.max_depth)),
@@ -245,6 +259,15 @@ def main(argv=None):
                            "metrics": list(metrics.KEYS), "zone_type": str(getattr(args, "zone_type", "8x8")),
                            "table": [[[rv[r][q].get(k) for k in metrics.KEYS] for q in regions.labels] for r in metrics.REGIONS],
                            "images": [[regions.image_counts[r][q] for q in regions.labels] for r in metrics.REGIONS]}, f)
+    if normal_metrics:
+        nv = normals_avg.get_value()
+        print(f"Normals: { {k: (v if k == 'images' else round(v, 3)) for k, v in nv.items()} }")
+        if save_spars:
+            import json
+            os.makedirs(args.save_dir, exist_ok=True)
+            with open(os.path.join(args.save_dir, "normals.json"), "w") as f:
+                json.dump({"metrics": list(metrics.NORMAL_METRIC_NAMES), "means": [nv.get(k) for k in metrics.NORMAL_METRIC_NAMES],
+                           "images": nv.get("images", 0), "bin_deg": 0.1, "histogram": normals_avg.histogram()}, f)
     if save_points:
         print(f"points: {n_points / max(n_img, 1):.1f} kept per image on average, written to {args.save_dir}/points_<index>.ply", file=sys.stderr)
     if pics:

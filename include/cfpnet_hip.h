@@ -674,6 +674,41 @@ int cfp_points_compact(const float* points, const float* normals, int H, int W, 
                        float* out_points /* [B][cap][3] */, float* out_normals /* [B][cap][3] or NULL */,
                        int* out_index /* [B][cap] */, int* counts /* [B] */, void* ws, size_t ws_bytes, cfp_stream_t stream);
 
+/* Surface-normal error of the predicted geometry against the ground truth's, per image, without leaving the device: the standard set of
+ * the normal-estimation literature (mean, median and RMSE of the angle, share of pixels below 11.25, 22.5 and 30 degrees).
+ *   Inputs  pred [B,Hp,Wp] f32 and gt [B,H,W] f32 (device); interpolate, lo < hi exactly as cfp_eval_metrics in mode 0; K [B][4] f32 ON
+ *           THE DEVICE: (fx, fy, cx, cy) per image under the caller contract of cfp_depth_unproject (finite, fx and fy not 0).
+ *   Depths  d_p(x, y) is the float32 value cfp_eval_metrics evaluates at the pixel in mode 0 (one implementation, csrc/metrics_pred.h:
+ *           bit for bit); d_g(x, y) = gt[b][y][x].
+ *   Normals n_p from d_p and n_g from d_g, both by the `Normal` of cfp_depth_unproject: clamped neighbours, the T_x / T_y form without
+ *           cancellation, n = normalize(T_y x T_x), float32, no fused multiply-add, and (0, 0, 0) under the same rule (one of the five
+ *           depths involved not finite, or a cross product of zero or non-finite length).  For the same five depths and intrinsics the
+ *           three floats are the ones cfp_depth_unproject writes, bit for bit.
+ *   Valid   a pixel counts iff the ground truth at the pixel and at its four clamped neighbours all satisfy lo < g < hi (a hole at 0
+ *           next to a surface gives a meaningless tangent) and both normals are non-zero.  So H == 1 or W == 1 gives no valid pixel.
+ *   Angle   float32, in this order, with p = n_p and g = n_g:
+ *             c = (p.x * g.x + p.y * g.y) + p.z * g.z
+ *             u = (p.y * g.z - p.z * g.y,  p.z * g.x - p.x * g.z,  p.x * g.y - p.y * g.x)      s = sqrtf((u.x * u.x + u.y * u.y) + u.z * u.z)
+ *             a = atan2f(s, c) * (float)(180 / pi)                                              degrees, 0 <= a <= 180
+ *           Equal normals give exactly 0.  atan2 of (|cross|, dot) because acos(dot) loses half its digits near 0, where most pixels are.
+ *   Histogram  1800 bins of 0.1 degree: k = min((int)(a * 10.0f), 1799); hist[b][k] counts the valid pixels (int32).
+ *   out [B][7] f64 = {mean_deg, median_deg, rmse_deg, frac_11_25, frac_22_5, frac_30, n_valid} (CFP_NORMAL_*) with N = n_valid:
+ *           mean_deg = (float64 sum of a) / N;  rmse_deg = sqrt((float64 sum of the float32 products a * a) / N);  the fractions count
+ *           a < 11.25f, a < 22.5f, a < 30.0f;  median_deg = (k* + 0.5) * 0.1 with k* the smallest bin whose cumulative count reaches
+ *           (N + 1) / 2 in integer division.  N == 0 gives NaN for the six metrics and n_valid = 0, as cfp_eval_metrics does.
+ *   Optional outputs, each NULL to skip: hist [B][1800] i32; angle_map [B][H][W] f32 = a at the valid pixels, NaN elsewhere.  `out` is
+ *           bit-identical with and without them.
+ * Floating-point sums are float64 in a fixed order and never accumulated with atomics; the counts are integers (order-independent; LDS
+ * and workspace integer atomics): two calls on the same tensors give identical bits.  No host synchronisation, no allocation; everything
+ * runs on `stream` in the caller's workspace of cfp_normal_metrics_ws_bytes(B, H, W) bytes, 8-byte aligned; 0 for arguments that make
+ * no sense. */
+enum { CFP_NORMAL_MEAN = 0, CFP_NORMAL_MEDIAN, CFP_NORMAL_RMSE, CFP_NORMAL_FRAC_11_25, CFP_NORMAL_FRAC_22_5, CFP_NORMAL_FRAC_30,
+       CFP_NORMAL_N_VALID };
+size_t cfp_normal_metrics_ws_bytes(int B, int H, int W);
+int cfp_normal_metrics(const float* pred, int Hp, int Wp, const float* gt, int H, int W, int B, int interpolate, float lo, float hi,
+                       const float* K /* device, [B][4]: fx fy cx cy */, void* ws, size_t ws_bytes, double* out /* [B][7] */,
+                       int* hist /* [B][1800] or NULL */, float* angle_map /* [B][H][W] or NULL */, cfp_stream_t stream);
+
 /* Pictures on the device: what the reference's `colorize` (src/utils/utils.py:44-64) paints on the host after moving the prediction
  * there, defined on the value the metrics evaluate.  Three entry points, one launch each; no workspace, no atomics, no host
  * synchronisation, capturable in a graph.  Every float32 operation below is rounded once (no fused multiply-add).
