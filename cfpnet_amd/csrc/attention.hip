@@ -5,139 +5,19 @@
 // one wave: lane = (key lane, row chunk); the cross-lane sum over key lanes is a butterfly of
 // wavefront shuffles.  Which keys form a group (a ToF zone's 16 samples, a ws x ws window with
 // its zero padding, the sub-sampled global keys, the inside-zone rectangle) is pure addressing.
-#include "common.h"
+#include "kv_reduce_core.h"
 
 namespace {
 
-struct KvP {
-  const void* k; const void* v;
-  float* kv; float* ksum; float* ws;
-  int k_ld, v_ld;
-  int NB, Hk, Wk, th, tw, gy, gx;
-  int cy0, cy1, cx0, cx1;
-  int count_pad, heads, d, nsplit;
-  float inv_len;
-  const int* rec;      // DEV only (last: the scalar instantiation's argument offsets stay): the zone record, see cfp_attn_kv_reduce_dev
-};
-
-// IC rows of the d x d accumulator per lane; TPK = d / IC lanes per key; KL = 64 / TPK key lanes.
-template <int D> struct KvCfg;
-// The cross-lane sum over the KL key lanes is a butterfly of log2(KL) steps x (IC * d + IC) `ds_bpermute`s: with a lane holding all d
-// rows (IC = d at d = 8) that was 432 of the kernel's 946 vector instructions.  Two rows per lane (TPK = d / 2 lanes share a key and
-// load its V row together) leave 16 / 8 key lanes: 72 / 102 permutes at d = 8 / 16, the same two to four load rounds per lane.
-template <> struct KvCfg<4>  { static constexpr int IC = 1; };
-template <> struct KvCfg<8>  { static constexpr int IC = 2; };
-template <> struct KvCfg<16> { static constexpr int IC = 2; };
-template <> struct KvCfg<32> { static constexpr int IC = 2; };
-
-// DEV: the clip rectangle and v_length come from the int32[9] zone record in device memory (y0, y1, x0, x1, n_inside: uniform loads)
-// instead of the host's integers; everything after that is the scalar instantiation's own code.
+// One wave per (group, head, split): the keys' projected K / V rows come from global memory (kv_reduce_core.h has the arithmetic).
 template <typename T, int D, bool DEV>
 __global__ __launch_bounds__(64) void kv_reduce_kernel(KvP p) {
-  constexpr int IC = KvCfg<D>::IC;
-  constexpr int TPK = D / IC;
-  constexpr int KL = 64 / TPK;
-  const T* __restrict__ K = reinterpret_cast<const T*>(p.k);
-  const T* __restrict__ V = reinterpret_cast<const T*>(p.v);
   const int g = blockIdx.x, h = blockIdx.y, sp = blockIdx.z;
   const int lane = threadIdx.x;
-  const int ip = lane % TPK, kl = lane / TPK;
-
-  const int gpb = p.gy * p.gx;
-  const int b = g / gpb, gi = g % gpb;
-  const int ty = gi / p.gx, tx = gi % p.gx;
-  int cy0 = p.cy0, cy1 = p.cy1, cx0 = p.cx0, cx1 = p.cx1;
-  float inv_len = p.inv_len;
-  if constexpr (DEV) {
-    const int* __restrict__ rec = p.rec;
-    cy0 = rec[4]; cy1 = rec[5]; cx0 = rec[6]; cx1 = rec[7];
-    inv_len = 1.0f / (float)max(rec[8], 1);      // the host's expression: 1 / v_length, v_length = max(n_inside, 1)
-  }
-  // key rectangle of this group: tile, clipped to the grid and to the clip rectangle
-  const int y0 = max(max(ty * p.th, cy0), 0), y1 = min(min((ty + 1) * p.th, cy1), p.Hk);
-  const int x0 = max(max(tx * p.tw, cx0), 0), x1 = min(min((tx + 1) * p.tw, cx1), p.Wk);
-  const int rh = max(y1 - y0, 0), rw = max(x1 - x0, 0);
-  const int S = rh * rw;
-  const int per = (S + p.nsplit - 1) / p.nsplit;
-  const int s_begin = sp * per, s_end = min(S, s_begin + per);
-
-  float acc[IC][D];
-  float ks[IC];
-#pragma unroll
-  for (int i = 0; i < IC; ++i) {
-    ks[i] = 0.f;
-#pragma unroll
-    for (int j = 0; j < D; ++j) acc[i][j] = 0.f;
-  }
-  // KU keys per iteration, their loads issued together: the loop is a chain of memory round trips (one per key before), not FMAs
-  constexpr int KU = 4;
-  // key s of the rectangle sits at (y0 + s / rw, x0 + s % rw): the lane's position advances by KL keys per load, so the division happens
-  // once (the quotient / remainder of the step and of the first and last key) and every step after that is an add and one wrap -- the
-  // per-key signed division was ~35 VALU instructions against 2 D = 8 .. 64 FMAs
-  const int rwd = max(rw, 1);
-  const int step_q = KL / rwd, step_r = KL - step_q * rwd;
-  const int s_first = min(s_begin + kl, max(s_end - 1, 0));
-  int cy = s_first / rwd, cx = s_first - cy * rwd;                      // (row, column) of key s0 + u * KL, before clamping
-  const int ly = max(s_end - 1, 0) / rwd, lx = max(s_end - 1, 0) - ly * rwd;      // of the last key (what the clamped tail loads read)
-  for (int s0 = s_begin + kl; s0 < s_end; s0 += KL * KU) {
-    float kf[KU][IC], vf[KU][D];
-#pragma unroll
-    for (int u = 0; u < KU; ++u) {
-      const bool in = s0 + u * KL < s_end;
-      const int yy = y0 + (in ? cy : ly), xx = x0 + (in ? cx : lx);
-      cx += step_r; cy += step_q;
-      if (cx >= rwd) { cx -= rwd; ++cy; }
-      const long long row = ((long long)b * p.Hk + yy) * p.Wk + xx;
-      const T* kp = K + row * p.k_ld + h * D + ip * IC;
-      const T* vp = V + row * p.v_ld + h * D;
-#pragma unroll
-      for (int i = 0; i < IC; ++i) kf[u][i] = to_f32<T>(kp[i]);
-#pragma unroll
-      for (int j = 0; j < D; ++j) vf[u][j] = to_f32<T>(vp[j]);
-    }
-#pragma unroll
-    for (int u = 0; u < KU; ++u) {
-      if (s0 + u * KL >= s_end) continue;              // same order of accumulation per lane as the one-key loop
-#pragma unroll
-      for (int j = 0; j < D; ++j) vf[u][j] *= inv_len;
-#pragma unroll
-      for (int i = 0; i < IC; ++i) {
-        const float kk = elu1(kf[u][i]);
-        ks[i] += kk;
-#pragma unroll
-        for (int j = 0; j < D; ++j) acc[i][j] = fmaf(kk, vf[u][j], acc[i][j]);
-      }
-    }
-  }
-  // butterfly over the key lanes (lanes with equal ip)
-#pragma unroll
-  for (int o = TPK; o < 64; o <<= 1) {
-#pragma unroll
-    for (int i = 0; i < IC; ++i) {
-      ks[i] += __shfl_xor(ks[i], o, 64);
-#pragma unroll
-      for (int j = 0; j < D; ++j) acc[i][j] += __shfl_xor(acc[i][j], o, 64);
-    }
-  }
-  if (kl == 0) {
-    // zero-padded window positions: K' = elu(0)+1 = 1, V = 0 (only the first split adds them)
-    float padk = 0.f;
-    if (p.count_pad && sp == 0) padk = (float)(p.th * p.tw - S);
-    float* dkv; float* dks;
-    if (p.nsplit == 1) {
-      dkv = p.kv + ((long long)g * p.heads + h) * D * D;
-      dks = p.ksum + ((long long)g * p.heads + h) * D;
-    } else {
-      float* base = p.ws + (((long long)g * p.heads + h) * p.nsplit + sp) * (D * D + D);
-      dkv = base; dks = base + D * D;
-    }
-#pragma unroll
-    for (int i = 0; i < IC; ++i) {
-      dks[ip * IC + i] = ks[i] + padk;
-#pragma unroll
-      for (int j = 0; j < D; ++j) dkv[(ip * IC + i) * D + j] = acc[i][j];
-    }
-  }
+  const KvGeom q = kv_group_geom<DEV>(p, g, sp);
+  constexpr int TPK = D / KvCfg<D>::IC;
+  KvGlobalKeys<T> keys(p, q, lane / TPK, 64 / TPK);
+  kv_reduce_body<T, D>(p, q, g, h, sp, lane, keys);
 }
 
 __global__ __launch_bounds__(256) void kv_finalize_kernel(const float* __restrict__ ws, float* __restrict__ kv,
@@ -242,6 +122,7 @@ int pick_nsplit(int S, long long groups_heads) {
 }  // namespace
 
 void cfp_attn_debug_set(int value) { g_kv_target_waves = value; }
+int kv_pick_nsplit(int S, long long groups_heads) { return pick_nsplit(S, groups_heads); }
 void cfp_attn_apply_debug_set(int value) { g_ap_split_below = value; }
 
 extern "C" size_t cfp_attn_kv_ws_floats(int NB, int Hk, int Wk, int th, int tw, int heads, int d) {
@@ -252,18 +133,16 @@ extern "C" size_t cfp_attn_kv_ws_floats(int NB, int Hk, int Wk, int th, int tw, 
   return (size_t)(groups * heads * ns * (d * d + d));
 }
 
-// `rec` == nullptr: the scalar entry point (clip rectangle and v_length from the arguments); otherwise the record-reading one
-static int kv_reduce_impl(const void* k, int k_ld, const void* v, int v_ld, float* kv, float* ksum, float* ws,
-                          int NB, int Hk, int Wk, int th, int tw, int cy0, int cy1, int cx0, int cx1,
-                          int count_pad, float v_length, const int* rec, int heads, int d, int dtype, cfp_stream_t stream, const char* who) {
-  CFP_REQUIRE(dtype_ok(dtype), CFP_EINVAL, std::string(who) + ": bad dtype");
-  CFP_REQUIRE(k && v && kv && ksum, CFP_EINVAL, std::string(who) + ": null pointer");
-  CFP_REQUIRE(NB > 0 && Hk > 0 && Wk > 0 && th > 0 && tw > 0 && heads > 0 && (d == 4 || d == 8 || d == 16 || d == 32) &&
-                  k_ld >= heads * d && v_ld >= heads * d && v_length > 0.f,
+// What cfp_attn_kv_reduce[_dev] and cfp_attn_kv_project_reduce[_dev] share on the host: the checks of the geometry, the parameter block
+// and the split count.  `k` / `v` and their pitches are the caller's.
+int kv_fill_params(KvP& p, float* kv, float* ksum, float* ws, int NB, int Hk, int Wk, int th, int tw, int cy0, int cy1, int cx0, int cx1,
+                   int count_pad, float v_length, const int* rec, int heads, int d, const char* who) {
+  CFP_REQUIRE(kv && ksum, CFP_EINVAL, std::string(who) + ": null pointer");
+  CFP_REQUIRE(NB > 0 && Hk > 0 && Wk > 0 && th > 0 && tw > 0 && heads > 0 && (d == 4 || d == 8 || d == 16 || d == 32) && v_length > 0.f,
               CFP_ESHAPE, std::string(who) + ": bad shape (head dim must be 4, 8, 16 or 32)");
-  KvP p;
   p.rec = rec;
-  p.k = k; p.v = v; p.kv = kv; p.ksum = ksum; p.ws = ws; p.k_ld = k_ld; p.v_ld = v_ld;
+  p.k = nullptr; p.v = nullptr; p.k_ld = 0; p.v_ld = 0;
+  p.kv = kv; p.ksum = ksum; p.ws = ws;
   p.NB = NB; p.Hk = Hk; p.Wk = Wk; p.th = th; p.tw = tw; p.gy = cdiv(Hk, th); p.gx = cdiv(Wk, tw);
   p.cy0 = cy0; p.cy1 = cy1; p.cx0 = cx0; p.cx1 = cx1; p.count_pad = count_pad; p.heads = heads; p.d = d;
   p.inv_len = 1.0f / v_length;
@@ -272,8 +151,30 @@ static int kv_reduce_impl(const void* k, int k_ld, const void* v, int v_ld, floa
   p.nsplit = pick_nsplit(S, groups * heads);
   CFP_REQUIRE(p.nsplit == 1 || ws, CFP_EINVAL, std::string(who) + ": workspace required");
   CFP_REQUIRE(groups < (1ll << 31) && heads <= 65535, CFP_ESHAPE, std::string(who) + ": grid too large");
+  return CFP_OK;
+}
+
+// the split slabs of `ws` summed in split order into kv / ksum (p.nsplit > 1)
+void kv_finalize_launch(const KvP& p, hipStream_t s) {
+  long long items = (long long)p.NB * p.gy * p.gx * p.heads;
+  long long total = items * (p.d * p.d + p.d);
+  int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+  hipLaunchKernelGGL(kv_finalize_kernel, dim3(blocks), dim3(256), 0, s, p.ws, p.kv, p.ksum, p.nsplit, p.d, items);
+}
+
+// `rec` == nullptr: the scalar entry point (clip rectangle and v_length from the arguments); otherwise the record-reading one
+static int kv_reduce_impl(const void* k, int k_ld, const void* v, int v_ld, float* kv, float* ksum, float* ws,
+                          int NB, int Hk, int Wk, int th, int tw, int cy0, int cy1, int cx0, int cx1,
+                          int count_pad, float v_length, const int* rec, int heads, int d, int dtype, cfp_stream_t stream, const char* who) {
+  CFP_REQUIRE(dtype_ok(dtype), CFP_EINVAL, std::string(who) + ": bad dtype");
+  CFP_REQUIRE(k && v && kv && ksum, CFP_EINVAL, std::string(who) + ": null pointer");
+  CFP_REQUIRE(heads > 0 && d > 0 && k_ld >= heads * d && v_ld >= heads * d, CFP_ESHAPE, std::string(who) + ": bad shape (head dim must be 4, 8, 16 or 32)");
+  KvP p;
+  const int rc = kv_fill_params(p, kv, ksum, ws, NB, Hk, Wk, th, tw, cy0, cy1, cx0, cx1, count_pad, v_length, rec, heads, d, who);
+  if (rc != CFP_OK) return rc;
+  p.k = k; p.v = v; p.k_ld = k_ld; p.v_ld = v_ld;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  dim3 grid((unsigned)groups, heads, p.nsplit);
+  dim3 grid((unsigned)((long long)NB * p.gy * p.gx), heads, p.nsplit);
 #define KV_LAUNCH(T, D) do { if (rec) hipLaunchKernelGGL((kv_reduce_kernel<T, D, true>), grid, dim3(64), 0, s, p); \
                              else hipLaunchKernelGGL((kv_reduce_kernel<T, D, false>), grid, dim3(64), 0, s, p); } while (0)
 #define KV_SWITCH(T) switch (d) { case 4: KV_LAUNCH(T, 4); break; case 8: KV_LAUNCH(T, 8); break; \
@@ -281,12 +182,7 @@ static int kv_reduce_impl(const void* k, int k_ld, const void* v, int v_ld, floa
   if (dtype == CFP_BF16) { KV_SWITCH(bf16_t) } else if (dtype == CFP_F16) { KV_SWITCH(f16_t) } else { KV_SWITCH(float) }
 #undef KV_SWITCH
 #undef KV_LAUNCH
-  if (p.nsplit > 1) {
-    long long items = groups * heads;
-    long long total = items * (d * d + d);
-    int blocks = (int)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
-    hipLaunchKernelGGL(kv_finalize_kernel, dim3(blocks), dim3(256), 0, s, ws, kv, ksum, p.nsplit, d, items);
-  }
+  if (p.nsplit > 1) kv_finalize_launch(p, s);
   return cfp_check_launch(who);
 }
 

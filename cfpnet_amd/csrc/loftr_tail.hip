@@ -67,7 +67,9 @@ __device__ __forceinline__ void tail_gemm(f32x4 (&acc)[NT], const H* __restrict_
 }
 
 // WAVES waves of 16 token rows per workgroup: 4, or 1 / 2 for few token rows (tail_waves).
-template <typename H, int D, int HEADS, int WAVES>
+// MAP (cfp_loftr_tail_x2i): the rows are a zone grid laid 1:1 over a rectangle of the token map -- x is read from the map and the output is
+// pasted into it (tail_core.h); everything between the first load and the final store is the plain kernel's code.
+template <typename H, int D, int HEADS, int WAVES, bool MAP = false>
 __global__ __launch_bounds__(64 * WAVES) void loftr_tail_kernel(TailP<H, H> p) {
   constexpr int PA = D + 8, PH = 2 * D + 8;               // row pitches (elements): +16 bytes
   constexpr int WAVE_LDS = (2 * PA + PH) * 16 * 2;         // msg/y1 | x | h tiles of one wave
@@ -84,7 +86,8 @@ __global__ __launch_bounds__(64 * WAVES) void loftr_tail_kernel(TailP<H, H> p) {
   const long long row0 = (long long)blockIdx.x * (16 * WAVES) + wave * 16;
 
   // ---- x tile -> LDS (16-byte vectors) -----------------------------------------------------------
-  tail_tile_load<H, D, PA>(tX, p.x, p.x_ld, row0, p.rows, lane);
+  if constexpr (MAP) tail_tile_load_mapped<H, D, PA>(tX, p, row0, lane);
+  else tail_tile_load<H, D, PA>(tX, p.x, p.x_ld, row0, p.rows, lane);
 
   // ---- optional q projection for this wave's rows (transformer.py:45: q = q_proj(x)): one more GEMM of the chain instead of a separate
   // launch that writes [rows, D] and is read back here; q is rounded to the storage type like the unfused GEMM's output ----------------
@@ -144,7 +147,8 @@ __global__ __launch_bounds__(64 * WAVES) void loftr_tail_kernel(TailP<H, H> p) {
       }
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  tail_tile_store<H, D, PA>(p.out, p.out_ld, tMsg, row0, p.rows, lane);
+  if constexpr (MAP) tail_tile_store_mapped<H, D, PA>(p, tMsg, row0, lane);
+  else tail_tile_store<H, D, PA>(p.out, p.out_ld, tMsg, row0, p.rows, lane);
 }
 
 // ---- LKPM tail (Block14.forward after the depthwise conv, convnext.py:48-58): LayerNorm(1e-6) -> pwconv1 (D -> 4D) -> GELU ->
@@ -229,11 +233,12 @@ void cfp_tail16_debug_set(int value) { g_tail16_waves = value; }
 
 // dtype: bf16 / f16 storage (the kernels above) or CFP_F32X3: float32 tensors, f16x3 matrix math, weights = cfp_pack_w_x3 operands
 // (loftr_tail_x3.hip).  The checks are the same up to the elements per 16-byte vector.
-extern "C" int cfp_loftr_tail(const void* q, int q_ld, const float* kv, const float* ksum, const void* x, int x_ld,
-                              void* out, int out_ld, const void* w_q, const void* w_merge, const void* w_mlp0, const void* w_mlp2,
-                              const float* ln1_g, const float* ln1_b, const float* ln2_g, const float* ln2_b, float ln_eps,
-                              int NB, int Hq, int Wq, int qth, int qtw, float v_length, float eps, int heads, int D,
-                              int dtype, cfp_stream_t stream) {
+// `map` == nullptr: cfp_loftr_tail; otherwise cfp_loftr_tail_x2i (16-bit only, checked there)
+static int loftr_tail_impl(const void* q, int q_ld, const float* kv, const float* ksum, const void* x, int x_ld,
+                           void* out, int out_ld, const void* w_q, const void* w_merge, const void* w_mlp0, const void* w_mlp2,
+                           const float* ln1_g, const float* ln1_b, const float* ln2_g, const float* ln2_b, float ln_eps,
+                           int NB, int Hq, int Wq, int qth, int qtw, float v_length, float eps, int heads, int D,
+                           int dtype, cfp_stream_t stream, const TailMap* map) {
   const bool x3 = dtype == CFP_F32X3;
   const int vec = x3 ? 4 : 8;                 // pitch multiple = 16 / sizeof(storage element)
   // rows < 2^31 (FastDiv, int row indices).  The float32 side has always reported it with the grid and the 16-bit side after the alignment:
@@ -256,17 +261,43 @@ extern "C" int cfp_loftr_tail(const void* q, int q_ld, const float* kv, const fl
   };
   auto run = [&](auto tag) {
     using H = decltype(tag);
-    const TailP<H, H> p = params(tag, tag);
+    TailP<H, H> p = params(tag, tag);
+    if (map) p.map = *map;
     return tail_pick<32, 64, 128>(D, [&](auto d) { return tail_pick<4, 8>(heads, [&](auto h) {
       return tail_pick<1, 2, 4>(tail_waves(p.rows, g_tail16_waves), [&](auto w) {
         constexpr int D_ = d, W_ = w;
         constexpr size_t lds = 2 * (2 * D_ * 128) + W_ * ((2 * (D_ + 8) + 2 * D_ + 8) * 16 * 2);      // weight region + the waves' tiles
+        if (map) return tail_launch<loftr_tail_kernel<H, D_, h, W_, true>, lds>(p, W_, s);
         return tail_launch<loftr_tail_kernel<H, D_, h, W_>, lds>(p, W_, s);
       }); }); });
   };
   const int rc = x3 ? loftr_tail_x3_launch(params(float{}, f16_t{}), heads, D, s) : dtype == CFP_F16 ? run(f16_t{}) : run(bf16_t{});
   CFP_REQUIRE(rc == 0, CFP_EHIP, x3 ? "cfp_loftr_tail: f16x3 launch failed" : "cfp_loftr_tail: launch failed");
   return cfp_check_launch("cfp_loftr_tail");
+}
+
+extern "C" int cfp_loftr_tail(const void* q, int q_ld, const float* kv, const float* ksum, const void* x, int x_ld,
+                              void* out, int out_ld, const void* w_q, const void* w_merge, const void* w_mlp0, const void* w_mlp2,
+                              const float* ln1_g, const float* ln1_b, const float* ln2_g, const float* ln2_b, float ln_eps,
+                              int NB, int Hq, int Wq, int qth, int qtw, float v_length, float eps, int heads, int D,
+                              int dtype, cfp_stream_t stream) {
+  return loftr_tail_impl(q, q_ld, kv, ksum, x, x_ld, out, out_ld, w_q, w_merge, w_mlp0, w_mlp2, ln1_g, ln1_b, ln2_g, ln2_b, ln_eps, NB, Hq, Wq, qth, qtw,
+                         v_length, eps, heads, D, dtype, stream, nullptr);
+}
+
+extern "C" int cfp_loftr_tail_x2i(const float* kv, const float* ksum, void* tok, int tok_ld, int H, int W, int sy, int sx,
+                                  const void* w_q, const void* w_merge, const void* w_mlp0, const void* w_mlp2,
+                                  const float* ln1_g, const float* ln1_b, const float* ln2_g, const float* ln2_b, float ln_eps,
+                                  int NB, int gh, int gw, int p1, int p2, const uint8_t* zone_valid, int zn, int accumulate,
+                                  float v_length, float eps, int heads, int D, int dtype, cfp_stream_t stream) {
+  CFP_REQUIRE(is16(dtype), CFP_EINVAL, "cfp_loftr_tail_x2i: bf16 / f16 only");
+  CFP_REQUIRE(tok && w_q, CFP_EINVAL, "cfp_loftr_tail_x2i: null pointer (the kernel projects q itself: w_q must be given)");
+  CFP_REQUIRE(H > 0 && W > 0 && p1 > 0 && p2 > 0 && (long long)NB * H * W < (1ll << 31), CFP_ESHAPE, "cfp_loftr_tail_x2i: bad token map");
+  CFP_REQUIRE(!zone_valid || (zn > 0 && gh <= zn * p1 && gw <= zn * p2), CFP_ESHAPE, "cfp_loftr_tail_x2i: zone grid smaller than the query grid");
+  TailMap map;
+  map.zone_valid = zone_valid; map.H = H; map.W = W; map.sy = sy; map.sx = sx; map.zn = zn; map.p1 = p1; map.p2 = p2; map.accumulate = accumulate;
+  return loftr_tail_impl(nullptr, 0, kv, ksum, tok, tok_ld, tok, tok_ld, w_q, w_merge, w_mlp0, w_mlp2, ln1_g, ln1_b, ln2_g, ln2_b, ln_eps, NB, gh, gw,
+                         p1, p2, v_length, eps, heads, D, dtype, stream, &map);
 }
 
 extern "C" int cfp_lkpm_tail(const void* t, int t_ld, const void* xin, int x_ld, void* out, int out_ld, const void* w1, const float* b1,

@@ -5,7 +5,7 @@
 //   * tail_ring_begin/_step  the hand-over of the shared weight stages between consecutive GEMMs and the counted wait of the K loop
 //   * tail_layernorm         LayerNorm over the accumulator registers
 //   * tail_attn_apply        the linear-attention apply
-//   * tail_tile_load/_store  the 16-row tile copies in 16-byte chunks
+//   * tail_tile_load/_store  the 16-row tile copies in 16-byte chunks (and their forms through a row map: hist2image in place)
 //   * tail_row_layernorm     the LKPM input LayerNorm on the tile
 //   * host side: the parameter blocks and their fill, the waves-per-workgroup rule, the D x heads x waves dispatch and the launch helper
 // T is the storage type of the tensors and tiles (float, bf16_t, f16_t), W the element type of the weights (T, or f16_t for the packed
@@ -136,6 +136,12 @@ __device__ __forceinline__ void tail_row_layernorm(T* tile, const float* gamma, 
 }
 
 // ---- parameter blocks ---------------------------------------------------------------------------------------------------------------
+// Optional row map of the LoFTR tail (hist2image at 1:1, cfp_loftr_tail_x2i): the Hq x Wq query grid of image b is the rectangle with origin
+// (sy, sx) of an H x W token map, x and out are that map, and the final store is the paste of the zone grid -- see tail_tile_store_mapped.
+struct TailMap {
+  const uint8_t* zone_valid;     // [B][zn][zn] or null: the zone of grid position (gy, gx) is (gy / p1, gx / p2)
+  int H, W, sy, sx, zn, p1, p2, accumulate;
+};
 template <typename T, typename W> struct TailP {
   const T* q; const float* kv; const float* ksum; const T* x; T* out;
   const W* wq;                   // optional: q_proj weights [D][D]; the kernel then computes q = x @ wq^T for its own rows and `q` is unused
@@ -146,6 +152,7 @@ template <typename T, typename W> struct TailP {
   FastDiv fwq, fhq, fqth, fqtw;  // rows < 2^31: the token -> (image, y, x) -> key-group split without 64-bit divisions (four of them per lane and
                                  // row tile were ~600 VALU instructions: about a third of the kernel at D = 32)
   float v_length, eps, ln_eps;
+  TailMap map;                   // read by the mapped instantiations only (last: the plain kernels' argument offsets stay)
 };
 template <typename T, typename W> struct LkpmP {
   const T* t; const T* xin; T* out;
@@ -225,6 +232,68 @@ __device__ __forceinline__ void tail_attn_apply(const TailP<T, W>& p, long long 
   }
 }
 
+// ---- the same tile copies through the row map: tile row m = (b, gy, gx) of the grid <-> token row (b * H + sy + gy) * W + sx + gx ------------
+// The token row of tile row m, or -1 when the grid position lies outside the image.
+template <typename T, typename W>
+__device__ __forceinline__ long long tail_map_row(const TailP<T, W>& p, long long m, int& b, int& gy, int& gx) {
+  const unsigned t = fd_div((unsigned)m, p.fwq);
+  gx = (int)((unsigned)m - t * (unsigned)p.Wq);
+  const unsigned bu = fd_div(t, p.fhq);
+  gy = (int)(t - bu * (unsigned)p.Hq);
+  b = (int)bu;
+  const int y = p.map.sy + gy, x = p.map.sx + gx;
+  if (y < 0 || y >= p.map.H || x < 0 || x >= p.map.W) return -1;
+  return ((long long)b * p.map.H + y) * p.map.W + x;
+}
+// What the 1:1 crop of the rectangle gives: the token row, zeros outside the image (the crop applies no zone mask).
+template <typename T, int D, int PA, typename W>
+__device__ __forceinline__ void tail_tile_load_mapped(T* tile, const TailP<T, W>& p, long long row0, int lane) {
+  constexpr int E = 16 / sizeof(T), XCH = D / E;
+  for (int i = lane; i < 16 * XCH; i += 64) {
+    const int r = i / XCH, ch = i - r * XCH;
+    const long long m = row0 + r;
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (m < p.rows) {
+      int b, gy, gx;
+      const long long tr = tail_map_row(p, m, b, gy, gx);
+      if (tr >= 0) v = *reinterpret_cast<const u32x4*>(p.x + tr * p.x_ld + ch * E);
+    }
+    *reinterpret_cast<u32x4*>(tile + r * PA + ch * E) = v;
+  }
+}
+// What the 1:1 paste of the zone grid does with the tail's output (already rounded to the storage type in the tile, as the grid tensor
+// was), line by line as cfp_resize_bilinear at scale 1: o = zone kept ? out : 0, o += token when accumulating, stored unconditionally and
+// rounded once (a dropped zone stores token + 0); grid positions outside the image are skipped.  The token is read from the map, not from
+// the x tile, and each token row is read and written by the one wave that owns it: in place is safe.
+template <typename T, int D, int PA, typename W>
+__device__ __forceinline__ void tail_tile_store_mapped(const TailP<T, W>& p, const T* tile, long long row0, int lane) {
+  constexpr int E = Vec<T>::N, XCH = D / E;
+  for (int i = lane; i < 16 * XCH; i += 64) {
+    const int r = i / XCH, ch = i - r * XCH;
+    const long long m = row0 + r;
+    if (m >= p.rows) continue;
+    int b, gy, gx;
+    const long long tr = tail_map_row(p, m, b, gy, gx);
+    if (tr < 0) continue;
+    bool keep = true;
+    if (p.map.zone_valid)
+      keep = p.map.zone_valid[(long long)b * p.map.zn * p.map.zn + min(max(gy / p.map.p1, 0), p.map.zn - 1) * p.map.zn +
+                              min(max(gx / p.map.p2, 0), p.map.zn - 1)] != 0;
+    float o[E];
+    Vec<T>::load(tile + r * PA + ch * E, o);
+#pragma unroll
+    for (int e = 0; e < E; ++e) o[e] = keep ? o[e] : 0.f;
+    T* dp = p.out + tr * p.out_ld + ch * E;
+    if (p.map.accumulate) {
+      float d[E];
+      Vec<T>::load(dp, d);
+#pragma unroll
+      for (int e = 0; e < E; ++e) o[e] += d[e];
+    }
+    Vec<T>::store(dp, o);
+  }
+}
+
 // ---- host side ------------------------------------------------------------------------------------------------------------------------
 template <typename T, typename W>
 TailP<T, W> tail_params(const void* q, int q_ld, const float* kv, const float* ksum, const void* x, int x_ld, void* out, int out_ld, const void* w_q,
@@ -238,6 +307,7 @@ TailP<T, W> tail_params(const void* q, int q_ld, const float* kv, const float* k
   p.rows = NB * Hq * Wq; p.Hq = Hq; p.Wq = Wq; p.qth = qth; p.qtw = qtw; p.ggy = cdiv(Hq, qth); p.ggx = cdiv(Wq, qtw);
   p.fwq = make_fastdiv((unsigned)Wq); p.fhq = make_fastdiv((unsigned)Hq); p.fqth = make_fastdiv((unsigned)qth); p.fqtw = make_fastdiv((unsigned)qtw);
   p.v_length = v_length; p.eps = eps; p.ln_eps = ln_eps;
+  p.map = TailMap{};
   return p;
 }
 template <typename T, typename W>

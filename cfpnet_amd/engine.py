@@ -168,6 +168,10 @@ class Engine:
         self.cat_pad = os.environ.get("CFP_CAT_PAD", "1") == "1" and not self.up_fused_x3      # f16x3: zero-padded concatenation buffers (see _pack: decoder.up*.a)
         self.lkpm_fused = os.environ.get("CFP_LKPM_FUSED", "1") != "0"      # LKPM's LayerNorm + MLP + residual as one kernel (cfp_lkpm_tail)
         self.tail_q = os.environ.get("CFP_TAIL_Q", "1") == "1"          # q projection inside the fused LoFTR tail
+        # k|v projection inside the key/value reduction (cfp_attn_kv_project_reduce): LSA, GSA and the hoisted hist2image states
+        self.kv_project = os.environ.get("CFP_KV_PROJECT", "1") == "1"
+        # hist2image at 1:1: the fused tail addresses the token map itself instead of a crop and a paste launch (cfp_loftr_tail_x2i)
+        self.x2i_inplace = os.environ.get("CFP_X2I_INPLACE", "1") == "1"
         self.lkpm_min_rows = int(os.environ.get("CFP_LKPM_MIN_ROWS", "30000"))      # token rows from which the LKPM tail runs fused
         self.sr_ln_fused = os.environ.get("CFP_SR_LN_FUSED", "1") == "1"      # f16x3: the global attention's LayerNorm inside its patch conv (0: a launch of its own)
         self.head_fused = os.environ.get("CFP_HEAD_FUSED", "1") != "0"
@@ -570,22 +574,34 @@ class Engine:
         source is the ToF embedding (fusion.py:123-125, 143): it depends on nothing the image path computes, so `forward` runs it
         for all six hist2image layers on the side stream beside the RGB encoder (18 launches off the critical path)."""
         d = D // heads
-        kvb = self._act(plan, f"{tag}.kvsrc", rows_s, 2 * D)
-        self._lin(p + ".kv", src, kvb, rows_s)
         G = kvmode["groups"]
         kv = self._f32(plan, f"{tag}.kv", G * heads * d * d)
         ks = self._f32(plan, f"{tag}.ks", G * heads * d)
         nws = ops.attn_kv_ws_floats(kvmode["NB"], kvmode["Hk"], kvmode["Wk"], kvmode["th"], kvmode["tw"], heads, d)
         ws = self._f32(plan, f"{tag}.kvws", nws)
+        if self._kv_projects(kvmode, heads, d):
+            self._kv_project(p, src, kv, ks, ws, kvmode, heads, d)
+            return kv, ks
+        kvb = self._act(plan, f"{tag}.kvsrc", rows_s, 2 * D)
+        self._lin(p + ".kv", src, kvb, rows_s)
         ops.attn_kv_reduce(kvb.slice(0, D), kvb.slice(D, D), kv, ks, ws, kvmode["NB"], kvmode["Hk"], kvmode["Wk"], kvmode["th"], kvmode["tw"],
                            kvmode["clip"], kvmode["count_pad"], kvmode["v_length"], heads, d)
         return kv, ks
+
+    def _kv_projects(self, kvmode: dict, heads, d) -> bool:
+        """Whether the key/value state comes from cfp_attn_kv_project_reduce (k|v projection inside the reduction: no [keys, 2D] tensor)
+        instead of the `.kv` GEMM + cfp_attn_kv_reduce.  16-bit modes with single-term weights; results are bit-identical."""
+        return (self.kv_project and self.half and not self.weights2
+                and ops.attn_kv_project_fits(kvmode["NB"], kvmode["Hk"], kvmode["Wk"], kvmode["th"], kvmode["tw"], heads, d, self.dtype))
+
+    def _kv_project(self, p, src: Act, kv, ks, ws, kvmode: dict, heads, d):
+        ops.attn_kv_project_reduce(src, self.P[p + ".kv"], kv, ks, ws, kvmode["NB"], kvmode["Hk"], kvmode["Wk"], kvmode["th"], kvmode["tw"],
+                                   kvmode["clip"], kvmode["count_pad"], kvmode["v_length"], heads, d)
 
     def _loftr(self, plan, tag, p, xb: Act, rows_q, src: Optional[Act], rows_s, heads, out: Act, kvmode: dict, apmode: dict, pre=None):
         D = xb.C // 2
         d = D // heads
         x = xb.slice(0, D)
-        qb = self._act(plan, f"{tag}.qkv", rows_q, 3 * D)
         fused_tail = self.half or (self.x3 and os.environ.get("CFP_X3_TAIL", "1") != "0")      # apply + merge + norm1 + mlp + norm2 + residual in one kernel
         tail_q = fused_tail and self.tail_q       # the fused tail projects q for its own rows: no q GEMM, no q tensor
         if pre is not None and tail_q:
@@ -594,7 +610,12 @@ class Engine:
                            (self.P[p + ".norm1.g"], self.P[p + ".norm1.b"]), (self.P[p + ".norm2.g"], self.P[p + ".norm2.b"]),
                            apmode["NB"], apmode["Hq"], apmode["Wq"], apmode["qth"], apmode["qtw"], kvmode["v_length"], heads)
             return
-        if src is None and tail_q:
+        # no k|v tensor either when the reduction projects it itself: the layer is two launches
+        project = tail_q and self._kv_projects(kvmode, heads, d)
+        qb = None if project else self._act(plan, f"{tag}.qkv", rows_q, 3 * D)
+        if project:
+            kA = vA = None
+        elif src is None and tail_q:
             self._lin(p + ".kv", x, qb.slice(D, 2 * D), rows_q)
             kA, vA = qb.slice(D, D), qb.slice(2 * D, D)
         elif src is None:     # self attention: one GEMM for q|k|v
@@ -611,8 +632,11 @@ class Engine:
         ks = self._f32(plan, f"{tag}.ks", G * heads * d)
         nws = ops.attn_kv_ws_floats(kvmode["NB"], kvmode["Hk"], kvmode["Wk"], kvmode["th"], kvmode["tw"], heads, d)
         ws = self._f32(plan, f"{tag}.kvws", nws)
-        ops.attn_kv_reduce(kA, vA, kv, ks, ws, kvmode["NB"], kvmode["Hk"], kvmode["Wk"], kvmode["th"], kvmode["tw"],
-                           kvmode["clip"], kvmode["count_pad"], kvmode["v_length"], heads, d)
+        if project:
+            self._kv_project(p, x if src is None else src, kv, ks, ws, kvmode, heads, d)
+        else:
+            ops.attn_kv_reduce(kA, vA, kv, ks, ws, kvmode["NB"], kvmode["Hk"], kvmode["Wk"], kvmode["th"], kvmode["tw"],
+                               kvmode["clip"], kvmode["count_pad"], kvmode["v_length"], heads, d)
         if fused_tail:
             # apply + merge + norm1 + mlp + norm2 + residual in one kernel: the intermediates stay in LDS
             ops.loftr_tail(None if tail_q else qb.slice(0, D), kv, ks, x, out, self.P[p + ".q1"] if tail_q else None,
@@ -628,6 +652,12 @@ class Engine:
         hid = self._act(plan, f"{tag}.hid", rows_q, 2 * D)
         self._lin(p + ".mlp0", xb, hid, rows_q, hip.ACT_RELU)
         self._lin(p + ".mlp2", hid, out, rows_q, residual=x, ln=(self.P[p + ".norm2.g"], self.P[p + ".norm2.b"], 1e-5))
+
+    def _x2i_in_place(self, geo: FusionGeometry, rec) -> bool:
+        """hist2image through cfp_loftr_tail_x2i: the zone rectangle and the per-zone grid have the same size (geometry: no interpolation),
+        the rectangle is static, the crop source is the paste target (change_embedding), and the 16-bit fused tail projects q itself."""
+        return (self.x2i_inplace and self.half and self.tail_q and not geo.interpolate and rec is None
+                and self.change_embedding)
 
     def _piw_ws(self, plan, bi: int, B: int, hw: int, cout: int, k: int):
         """Split-K slab workspace of a per-image-weight project GEMM in the f16x3 mode, when the kernel plan wants one (single images: a few
@@ -687,22 +717,32 @@ class Engine:
             tag = f"{name}.L{i}"
             final_dst = out if (i == last and taps is None and os.environ.get("CFP_NO_DIRECT_OUT", "0") != "1") else None
             if ln == "hist2image":
-                zin = self._act(plan, f"{name}.zin", Mz, 2 * D)
-                zsrc = tok[cur].slice(0, D) if self.change_embedding else emb0
-                if rec is None:
-                    ops.resize_bilinear(zsrc, H, W, rect, zin.slice(0, D), gh, gw, (0, 0, gh, gw), B)
+                x2i_kv = dict(groups=B * Z, NB=B * Z, Hk=1, Wk=N, th=1, tw=N, clip=(0, 1, 0, N), count_pad=False, v_length=float(N))
+                x2i_pre = plan.get("x2i_kv", {}).get((name, i))
+                if self._x2i_in_place(geo, rec):
+                    # zone grid 1:1 over its rectangle: the tail reads and accumulates the token map itself (no crop, no paste, no grid tensors)
+                    assert (geo.tzh, geo.tzw) == (gh, gw)
+                    kvs = x2i_pre if x2i_pre is not None else self._kv_state(plan, f"{name}.x2i{i}", l, src, B * Z * N, D, spec.X2I_HEADS, x2i_kv)
+                    ops.loftr_tail_x2i(kvs[0], kvs[1], tok[cur].slice(0, D), H, W, geo.sy_wo, geo.sx_wo, self.P[l + ".q1"], self.P[l + ".merge"],
+                                       self.P[l + ".mlp0"], self.P[l + ".mlp2"], (self.P[l + ".norm1.g"], self.P[l + ".norm1.b"]),
+                                       (self.P[l + ".norm2.g"], self.P[l + ".norm2.b"]), B, gh, gw, geo.p1, geo.p2, zone_valid, geo.zone_num,
+                                       not self.no_skip_inside, float(N), spec.X2I_HEADS)
                 else:
-                    ops.resize_bilinear(zsrc, H, W, None, zin.slice(0, D), gh, gw, (0, 0, gh, gw), B, rec=rec, rec_side=0)
-                zout = self._act(plan, f"{name}.zout", Mz, D)
-                self._loftr(plan, f"{name}.x2i", l, zin, Mz, src, B * Z * N, spec.X2I_HEADS, zout,
-                            dict(groups=B * Z, NB=B * Z, Hk=1, Wk=N, th=1, tw=N, clip=(0, 1, 0, N), count_pad=False, v_length=float(N)),
-                            dict(NB=B, Hq=gh, Wq=gw, qth=geo.p1, qtw=geo.p2), pre=plan.get("x2i_kv", {}).get((name, i)))
-                if rec is None:
-                    ops.resize_bilinear(zout, gh, gw, (0, 0, gh, gw), tok[cur].slice(0, D), H, W, rect, B, zone_valid=zone_valid,
-                                        zn=geo.zone_num, p1=geo.p1, p2=geo.p2, accumulate=not self.no_skip_inside)
-                else:
-                    ops.resize_bilinear(zout, gh, gw, (0, 0, gh, gw), tok[cur].slice(0, D), H, W, None, B, zone_valid=zone_valid,
-                                        zn=geo.zone_num, p1=geo.p1, p2=geo.p2, accumulate=not self.no_skip_inside, rec=rec, rec_side=1)
+                    zin = self._act(plan, f"{name}.zin", Mz, 2 * D)
+                    zsrc = tok[cur].slice(0, D) if self.change_embedding else emb0
+                    if rec is None:
+                        ops.resize_bilinear(zsrc, H, W, rect, zin.slice(0, D), gh, gw, (0, 0, gh, gw), B)
+                    else:
+                        ops.resize_bilinear(zsrc, H, W, None, zin.slice(0, D), gh, gw, (0, 0, gh, gw), B, rec=rec, rec_side=0)
+                    zout = self._act(plan, f"{name}.zout", Mz, D)
+                    self._loftr(plan, f"{name}.x2i", l, zin, Mz, src, B * Z * N, spec.X2I_HEADS, zout, x2i_kv,
+                                dict(NB=B, Hq=gh, Wq=gw, qth=geo.p1, qtw=geo.p2), pre=x2i_pre)
+                    if rec is None:
+                        ops.resize_bilinear(zout, gh, gw, (0, 0, gh, gw), tok[cur].slice(0, D), H, W, rect, B, zone_valid=zone_valid,
+                                            zn=geo.zone_num, p1=geo.p1, p2=geo.p2, accumulate=not self.no_skip_inside)
+                    else:
+                        ops.resize_bilinear(zout, gh, gw, (0, 0, gh, gw), tok[cur].slice(0, D), H, W, None, B, zone_valid=zone_valid,
+                                            zn=geo.zone_num, p1=geo.p1, p2=geo.p2, accumulate=not self.no_skip_inside, rec=rec, rec_side=1)
             elif ln == "image":
                 nh, nw = math.ceil(H / ws), math.ceil(W / ws)
                 self._loftr(plan, f"{name}.lsa", l + ".lga.encoder_layer", tok[cur], M, None, 0, spec.TWINS_HEADS, tok[cur ^ 1].slice(0, D),

@@ -62,9 +62,13 @@ SIGNATURES = {
     "cfp_attn_kv_reduce": (_i, [_p, _i, _p, _i, _p, _p, _p] + [_i] * 10 + [_f, _i, _i, _i, _p]),
     "cfp_attn_apply": (_i, [_p, _i, _p, _p, _p, _i] + [_i] * 9 + [_f, _f, _i, _i, _i, _p]),
     "cfp_loftr_tail": (_i, [_p, _i, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _f] + [_i] * 5 + [_f, _f, _i, _i, _i, _p]),
+    "cfp_loftr_tail_x2i": (_i, [_p, _p, _p, _i, _i, _i, _i, _i] + [_p] * 8 + [_f] + [_i] * 5 + [_p, _i, _i, _f, _f, _i, _i, _i, _p]),
     "cfp_resize_bilinear": (_i, [_p, _i] + [_i] * 6 + [_p, _i] + [_i] * 6 + [_p] + [_i] * 7 + [_p]),
     "cfp_resize_bilinear_dev": (_i, [_p, _i, _i, _i, _p, _i, _i, _i, _p, _i, _p] + [_i] * 6 + [_i, _p]),
     "cfp_attn_kv_reduce_dev": (_i, [_p, _i, _p, _i, _p, _p, _p] + [_i] * 5 + [_p, _i, _i, _i, _i, _p]),
+    "cfp_attn_kv_project_fits": (_i, [_i] * 8),
+    "cfp_attn_kv_project_reduce": (_i, [_p, _i, _p, _p, _p, _p] + [_i] * 10 + [_f, _i, _i, _i, _p]),
+    "cfp_attn_kv_project_reduce_dev": (_i, [_p, _i, _p, _p, _p, _p] + [_i] * 5 + [_p, _i, _i, _i, _i, _p]),
     "cfp_attn_apply_dev": (_i, [_p, _i, _p, _p, _p, _i] + [_i] * 5 + [_p, _f, _i, _i, _i, _p]),
     "cfp_add_rowtable": (_i, [_p, _i, _p, _p, _i] + [_i] * 8 + [_p]),
     "cfp_upsample_cat_conv3x3": (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _i] + [_i] * 6 + [_p]),

@@ -392,6 +392,24 @@ def attn_kv_reduce(k: Act, v: Act, kv, ksum, ws, NB, Hk, Wk, th, tw, clip, count
              NB, Hk, Wk, th, tw, cy0, cy1, cx0, cx1, int(count_pad), float(v_length), heads, d, k.dt, _s())
 
 
+def attn_kv_project_fits(NB, Hk, Wk, th, tw, heads, d, dtype) -> bool:
+    """Whether attn_kv_project_reduce takes the problem (else: linear + attn_kv_reduce)."""
+    return bool(hip.load().cfp_attn_kv_project_fits(NB, Hk, Wk, th, tw, heads, d, DT.get(dtype, -1)))
+
+
+def attn_kv_project_reduce(x: Act, w_kv: torch.Tensor, kv, ksum, ws, NB, Hk, Wk, th, tw, clip, count_pad, v_length, heads, d, rec=None):
+    """attn_kv_reduce on the key tokens `x` ([rows, D], D = heads * d): K|V = x @ w_kv^T ([2 D, D] in the storage type) is projected inside
+    the kernel and never stored; bit-identical to linear(x, w_kv) + attn_kv_reduce.  `rec`: as in attn_kv_reduce."""
+    assert x.C == heads * d and w_kv.shape == (2 * x.C, x.C) and w_kv.dtype == x.buf.dtype and w_kv.is_contiguous()
+    if rec is not None:
+        hip.call("cfp_attn_kv_project_reduce_dev", x.ptr, x.ld, w_kv.data_ptr(), kv.data_ptr(), ksum.data_ptr(), hip.ptr(ws),
+                 NB, Hk, Wk, th, tw, _rec_ptr(rec), int(count_pad), heads, d, x.dt, _s())
+        return
+    cy0, cy1, cx0, cx1 = clip
+    hip.call("cfp_attn_kv_project_reduce", x.ptr, x.ld, w_kv.data_ptr(), kv.data_ptr(), ksum.data_ptr(), hip.ptr(ws),
+             NB, Hk, Wk, th, tw, cy0, cy1, cx0, cx1, int(count_pad), float(v_length), heads, d, x.dt, _s())
+
+
 def attn_apply(q: Act, kv, ksum, out: Act, NB, Hq, Wq, qth, qtw, excl, v_length, heads, d, eps=1e-6, rec=None):
     """`rec`: as in attn_kv_reduce -- the exclusion rectangle and v_length come from the device zone record."""
     if rec is not None:
@@ -417,6 +435,18 @@ def loftr_tail(q: Optional[Act], kv, ksum, x: Act, out: Act, w_q, w_merge, w_mlp
              out.ptr, out.ld, w_q.data_ptr() if w_q is not None else None, w_merge.data_ptr(),
              w_mlp0.data_ptr(), w_mlp2.data_ptr(), ln1[0].data_ptr(), ln1[1].data_ptr(), ln2[0].data_ptr(), ln2[1].data_ptr(),
              float(ln_eps), NB, Hq, Wq, qth, qtw, float(v_length), float(eps), heads, D, hip.F32X3 if x3 else x.dt, _s())
+
+
+def loftr_tail_x2i(kv, ksum, tok: Act, H, W, sy, sx, w_q, w_merge, w_mlp0, w_mlp2, ln1, ln2, NB, gh, gw, p1, p2, zone_valid, zn, accumulate,
+                   v_length, heads, eps=1e-6, ln_eps=1e-5):
+    """loftr_tail of a hist2image layer at 1:1, in place on the token map `tok` ([NB * H * W, D] view): the gh x gw zone grid is the rectangle
+    with origin (sy, sx); replaces resize_bilinear (crop) + loftr_tail + resize_bilinear (paste).  16-bit modes."""
+    D = tok.C
+    assert w_q.shape == (D, D) and w_merge.shape == (D, D) and w_mlp0.shape == (2 * D, 2 * D) and w_mlp2.shape == (D, 2 * D)
+    assert tok.rows >= NB * H * W and (zone_valid is None or (zone_valid.dtype == torch.uint8 and zone_valid.numel() >= NB * zn * zn))
+    hip.call("cfp_loftr_tail_x2i", kv.data_ptr(), ksum.data_ptr(), tok.ptr, tok.ld, H, W, sy, sx, w_q.data_ptr(), w_merge.data_ptr(),
+             w_mlp0.data_ptr(), w_mlp2.data_ptr(), ln1[0].data_ptr(), ln1[1].data_ptr(), ln2[0].data_ptr(), ln2[1].data_ptr(), float(ln_eps),
+             NB, gh, gw, p1, p2, hip.ptr(zone_valid), zn, int(accumulate), float(v_length), float(eps), heads, D, tok.dt, _s())
 
 
 def _rec_ptr(rec) -> int:

@@ -303,6 +303,21 @@ int cfp_attn_kv_reduce_dev(const void* k, int k_ld, const void* v, int v_ld, flo
                            int NB, int Hk, int Wk, int th, int tw, const int* rec, int count_pad, int heads, int d, int dtype,
                            cfp_stream_t stream);
 
+/* cfp_attn_kv_reduce[_dev] on the key TOKENS: the k|v projection runs inside the reduction, K|V = x @ w_kv^T never reaches memory.
+ * x: [NB * Hk * Wk][D] tokens (pitch x_ld, a multiple of 8), D = heads * d; w_kv: [2 D][D] in the storage type, rows 0 .. D-1 the
+ * k projection, D .. 2D-1 the v projection (a linear layer without bias).  bf16 / f16 only.  kv, ksum and the split slabs in ws are
+ * bit-identical to cfp_linear (no scale, shift or activation) followed by cfp_attn_kv_reduce[_dev] on its output; geometry, split count
+ * and workspace are cfp_attn_kv_reduce's.  cfp_attn_kv_project_fits: 1 if the launch takes the problem (D in 32 / 64 / 128, heads 4 / 8,
+ * a 16-bit dtype, and the rows of one split within the kernel's LDS budget), else 0 -- the launch then refuses it with CFP_ESHAPE
+ * (CFP_EINVAL for the dtype) before anything runs, and the caller keeps the pair. */
+int cfp_attn_kv_project_fits(int NB, int Hk, int Wk, int th, int tw, int heads, int d, int dtype);
+int cfp_attn_kv_project_reduce(const void* x, int x_ld, const void* w_kv, float* kv, float* ksum, float* ws,
+                               int NB, int Hk, int Wk, int th, int tw, int cy0, int cy1, int cx0, int cx1,
+                               int count_pad, float v_length, int heads, int d, int dtype, cfp_stream_t stream);
+int cfp_attn_kv_project_reduce_dev(const void* x, int x_ld, const void* w_kv, float* kv, float* ksum, float* ws,
+                                   int NB, int Hk, int Wk, int th, int tw, const int* rec, int count_pad, int heads, int d, int dtype,
+                                   cfp_stream_t stream);
+
 /* Linear attention, query half (attention.py:48-49):
  *   out[q,h,:] = (Q_q,h . KV[g(q),h]) / (Q_q,h . Ksum[g(q),h] + eps) * v_length,  Q = elu(q)+1
  * Queries live on an [NB, Hq, Wq] grid; g(q) = (b, y / qth, x / qtw).  Queries inside the
@@ -333,6 +348,21 @@ int cfp_loftr_tail(const void* q, int q_ld, const float* kv, const float* ksum, 
                    const float* ln1_g, const float* ln1_b, const float* ln2_g, const float* ln2_b, float ln_eps,
                    int NB, int Hq, int Wq, int qth, int qtw, float v_length, float eps, int heads, int D,
                    int dtype, cfp_stream_t stream);
+
+/* cfp_loftr_tail for a hist2image layer whose zone grid lies 1:1 over a rectangle of the token map (bf16 / f16): instead of
+ * cfp_resize_bilinear (crop) -> cfp_loftr_tail -> cfp_resize_bilinear (paste) through two grid tensors, the kernel reads its x rows from
+ * the map and pastes its output into it.  tok: [NB, H, W] tokens of D channels (pitch tok_ld), read and written in place; the gh x gw query
+ * grid of image b is the rectangle with origin (sy, sx), which may overhang the map: grid row (b, gy, gx) is token
+ * (b, sy + gy, sx + gx), reads zero outside the map (the crop's zero padding, no zone mask) and is not stored there.  The store is the
+ * paste at scale 1: o = zone_valid[b][gy / p1][gx / p2] ? out : 0 (zone_valid NULL: always out), o += token when accumulate != 0, stored
+ * unconditionally, rounded once.  Key groups are the zones (qth = p1, qtw = p2); w_q is required.  For finite tokens the result is
+ * bit-identical to the three launches (their bilinear weights are exactly 1 and 0; what the products by 0 do to the sign of a zero
+ * and to non-finite neighbours is not reproduced). */
+int cfp_loftr_tail_x2i(const float* kv, const float* ksum, void* tok, int tok_ld, int H, int W, int sy, int sx,
+                       const void* w_q, const void* w_merge, const void* w_mlp0, const void* w_mlp2,
+                       const float* ln1_g, const float* ln1_b, const float* ln2_g, const float* ln2_b, float ln_eps,
+                       int NB, int gh, int gw, int p1, int p2, const uint8_t* zone_valid, int zn, int accumulate,
+                       float v_length, float eps, int heads, int D, int dtype, cfp_stream_t stream);
 
 /* Bilinear resampling (align_corners=True) of a rectangle of an NHWC map into a rectangle of
  * another one.  The source rectangle may overhang the source map (reads 0 there: F.pad in

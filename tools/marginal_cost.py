@@ -39,13 +39,17 @@ def run(skip):
     return (time.perf_counter() - t0) / 40 * 1e3
 
 
+# the head as the engine launches it: conv0 + head conv + bins in one kernel (or the two-kernel and the bins-only forms, with or without the
+# uncertainty planes)
+HEAD = ("cfp_depth_head_conv0_fused", "cfp_depth_head_fused", "cfp_depth_head_fused_stats", "cfp_bin_head_fused", "cfp_bin_head_fused_stats")
 is_conv = lambda n: n in ("cfp_conv2d_nhwc", "cfp_conv2d_nhwc_ex")
 base = run(lambda n, a: False)
 print(f"full graph: {base:.3f} ms/step")
 cases = [("dw3x3", lambda n, a: n.startswith("cfp_dwconv3x3")), ("se_gate_fold", lambda n, a: n == "cfp_se_gate_fold"),
          ("loftr_tail", lambda n, a: n == "cfp_loftr_tail"), ("kv_reduce", lambda n, a: n == "cfp_attn_kv_reduce"),
+         ("kv_project_reduce", lambda n, a: n.startswith("cfp_attn_kv_project_reduce")),
          ("attn_apply", lambda n, a: n == "cfp_attn_apply"), ("resize", lambda n, a: n == "cfp_resize_bilinear"),
-         ("bin_head_fused", lambda n, a: n == "cfp_bin_head_fused"), ("bin_regressor", lambda n, a: n == "cfp_bin_regressor"),
+         ("fused head", lambda n, a: n in HEAD), ("bin_regressor", lambda n, a: n == "cfp_bin_regressor"),
          ("dwlarge", lambda n, a: n.startswith("cfp_dwconv_large")), ("layernorm", lambda n, a: n == "cfp_layernorm"),
          ("conv < 0.5 GF", lambda n, a: is_conv(n) and conv_gflop(a) < 0.5), ("conv 0.5-2 GF", lambda n, a: is_conv(n) and 0.5 <= conv_gflop(a) < 2),
          ("conv 2-10 GF", lambda n, a: is_conv(n) and 2 <= conv_gflop(a) < 10), ("conv 10-60 GF", lambda n, a: is_conv(n) and 10 <= conv_gflop(a) < 60),
