@@ -217,10 +217,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo_kernel(ConvP p, HaloP hp)
 
   for (int ks = 0; ks < nk; ++ks) {
     const int buf = (ks + sb) % STAGES;
-    const int ahead = min(nk - 1 - ks, STAGES - 2);
-    if (ahead >= 2) wait_vmcnt<(STAGES > 3 ? 2 : 1) * NB>();
-    else if (ahead == 1) wait_vmcnt<NB>();
-    else wait_vmcnt<0>();
+    wait_stage<STAGES, NB>(min(nk - 1 - ks, STAGES - 2));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's halo stores (first time round) and fragment reads of the previous step
     __builtin_amdgcn_s_barrier();          // stage `buf` (and the halo) landed for every wave; stage buf-1 fully consumed.  Raw: a __syncthreads() would drain the DMA queue
     asm volatile("" ::: "memory");

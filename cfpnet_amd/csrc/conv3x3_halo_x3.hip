@@ -150,10 +150,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_x3_kernel(ConvP p, HaloX3P h
 
   for (int ks = 0; ks < nk; ++ks) {
     const int buf = ks % STAGES;
-    const int ahead = min(nk - 1 - ks, STAGES - 2);
-    if (ahead >= 2) wait_vmcnt<(STAGES > 3 ? 2 : 1) * NB>();
-    else if (ahead == 1) wait_vmcnt<NB>();
-    else wait_vmcnt<0>();
+    wait_stage<STAGES, NB>(min(nk - 1 - ks, STAGES - 2));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this wave's halo stores (first time round) and the fragment reads of the previous step
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");

@@ -29,12 +29,9 @@
 //   * `rows_per_batch > 0`: M-tiles never straddle an image and image b uses weights
 //     w + b * w_bstride (squeeze-excite gates folded into per-image project weights).
 //   * split-K as in conv_igemm.hip: f32 slabs + the shared reduce kernel.
-#include "igemm_core.h"
-#include "lds_dma.h"
+#include "igemm_dma_core.h"
 
 namespace {
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // KG = 2 (round 3): EIGHT waves, two groups of four.  Both groups own the whole tile; group g takes the K-steps k0 + g, k0 + g + 2, ...
 // through its own LDS stages, and the groups' accumulators are added through LDS before the epilogue.  For the launches that cannot
@@ -66,34 +63,11 @@ __global__ __launch_bounds__(256 * KG) void igemm2_kernel(ConvP p, float* __rest
   const int lc = (lane & 7) ^ rsub;              // logical K-chunk this lane fetches
   unsigned char* gsm = smem + kg * (STAGES * STAGE_BYTES);      // this group's operand stages
 
-  // ---- tile coordinates -------------------------------------------------------------------
-  const int tiles_n = (p.Cout + BN - 1) / BN;
-  int bid = xcd_remap(blockIdx.x, gridDim.x);   // an XCD's L2 sees a contiguous run of tiles (shared A rows / halos / weights)
-  int sp = 0;
-  if constexpr (SPLITK) { sp = bid % splits; bid /= splits; }
-  const int tile_n = bid % tiles_n;
-  const int tile_m = bid / tiles_n;
-  int m0, m_end;
-  const H* __restrict__ wt = reinterpret_cast<const H*>(p.w);
-  if (p.rows_per_batch > 0) {
-    const int tpb = (p.rows_per_batch + BM - 1) / BM;
-    const int b = tile_m / tpb;
-    m0 = b * p.rows_per_batch + (tile_m % tpb) * BM;
-    m_end = (b + 1) * p.rows_per_batch;
-    wt += (long long)b * p.w_bstride;
-  } else {
-    m0 = tile_m * BM;
-    m_end = p.M;
-  }
-  const int n0 = tile_n * BN;
   const int nk_all = p.k2 > 0 ? 2 * p.k2 : ((p.K + 63) >> 6);
   const int wrow = p.k2 > 0 ? 2 * p.k2 * 64 : p.K;          // elements per weight row (two-term weights: [hi | lo], each k2 K-steps long)
-  int k0 = 0, k1 = nk_all;
-  if constexpr (SPLITK) {
-    const int per = (nk_all + splits - 1) / splits;
-    k0 = sp * per;
-    k1 = min(nk_all, k0 + per);
-  }
+  const IgemmTile tile = igemm_tile<BM, BN, SPLITK>(p, splits, nk_all);
+  const int m0 = tile.m0, m_end = tile.m_end, n0 = tile.n0, k0 = tile.k0, k1 = tile.k1, sp = tile.sp, tile_m = tile.tile_m;
+  const H* __restrict__ wt = reinterpret_cast<const H*>(p.w) + tile.w_off;
   const H* __restrict__ in = reinterpret_cast<const H*>(p.in);
 
   // ---- per-lane row bookkeeping -----------------------------------------------------------
@@ -193,10 +167,7 @@ __global__ __launch_bounds__(256 * KG) void igemm2_kernel(ConvP p, float* __rest
   const int a_row0 = wm * (BM / WM), b_row0 = wn * (BN / WN);
   for (int it = 0; it < nit; ++it) {
     const int buf = it % STAGES;
-    const int ahead = min(nkg - 1 - it, STAGES - 2);   // younger stages that may stay in flight
-    if (ahead >= 2) wait_vmcnt<(STAGES > 3 ? 2 : 1) * LPS>();
-    else if (ahead == 1) wait_vmcnt<LPS>();
-    else wait_vmcnt<0>();
+    wait_stage<STAGES, LPS>(min(nkg - 1 - it, STAGES - 2));   // younger stages that may stay in flight
     __builtin_amdgcn_s_barrier();                     // stage `buf` landed for every wave; stage buf-1 fully consumed
     asm volatile("" ::: "memory");
     if (KG == 2 && it >= nkg) continue;               // the second group's missing last step (odd step count): it only keeps the barrier count
@@ -223,41 +194,15 @@ __global__ __launch_bounds__(256 * KG) void igemm2_kernel(ConvP p, float* __rest
   wait_vmcnt<0>();
   __syncthreads();   // every wave is done with the operand stages: LDS becomes the C tile
   if constexpr (KG == 2) {
-    // the second group's accumulators travel through LDS (float32, lane-contiguous 16-byte pieces) and are added by the first
     static_assert(BM * BN * 4 <= KG * STAGES * STAGE_BYTES, "accumulator exchange must fit in the operand LDS");
-    f32x4* xch = reinterpret_cast<f32x4*>(smem) + wave * (TM * TN * 64) + lane;
-    if (kg == 1) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) xch[(i * TN + j) * 64] = acc[i][j];
-    }
-    __syncthreads();
-    if (kg == 0) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const f32x4 o = xch[(i * TN + j) * 64];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[i][j][r] += o[r];
-        }
-    }
-    __syncthreads();
+    kg_exchange(acc, smem, kg, wave, lane);
+    __syncthreads();   // the second group stays: it takes part in the C-tile copy and the moments
   }
 
   // The accumulators are held transposed (weights as the MFMA's row operand): a lane owns four consecutive output channels of one
   // pixel, so the epilogue moves 8-byte (16-bit) / 16-byte (float32 slab) vectors instead of sixteen 2-byte LDS writes per thread.
   if constexpr (SPLITK) {
-    float* slab = slabs + (long long)sp * p.M * p.Cout;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int m = m0 + a_row0 + i * 16 + fr;
-        const int n = n0 + b_row0 + j * 16 + fq * 4;
-        if (m < m_end && n < p.Cout) *reinterpret_cast<f32x4*>(slab + (long long)m * p.Cout + n) = acc[i][j];      // Cout % 8 == 0, n % 4 == 0
-      }
+    store_slab(acc, slabs + (long long)sp * p.M * p.Cout, p.Cout, m0 + a_row0, m_end, n0 + b_row0, fr, fq);      // Cout % 8 == 0
     return;
   } else {
     constexpr int CP = BN + 8;   // C-tile pitch in elements (one 16-byte chunk of padding)
@@ -337,86 +282,29 @@ __global__ __launch_bounds__(256 * KG) void igemm2_kernel(ConvP p, float* __rest
   }
 }
 
-struct Cfg { int bm, bn, stages, kg = 1; };
-// variant ids (cfp_conv2d_variant2): keep in sync with launch_variant below
-constexpr Cfg kCfg[] = {
-    {128, 128, 3},  // 0
-    {128, 128, 2},  // 1
-    {128, 64, 3},   // 2
-    {128, 64, 4},   // 3
-    {64, 64, 3},    // 4
-    {64, 64, 4},    // 5
-    {256, 32, 3},   // 6
-    {256, 32, 2},   // 7
-    {128, 32, 3},   // 8
-    {128, 32, 4},   // 9
-    {256, 16, 2},   // 10
-    {128, 16, 4},   // 11
-    {64, 128, 3},   // 12
-    {64, 64, 2},    // 13
-    {128, 64, 2},   // 14
-    {64, 128, 2},   // 15
-    {128, 32, 2},   // 16
-    {32, 64, 3},    // 17: few-row / long-K problems with per-image weights (the squeeze-excite project GEMMs at 1/32: 300 rows per image):
-    {32, 128, 3},   // 18  twice the workgroups of the 64-row tiles, so that 8 images x 232 channels fill the chip
-    {64, 64, 2, 2},   // 19: two K groups (eight waves): long-K launches of a few hundred tiles
-    {64, 64, 3, 2},   // 20
-    {64, 128, 2, 2},  // 21
-};
-constexpr int kNumCfg = sizeof(kCfg) / sizeof(kCfg[0]);
-
-template <typename H, int BM, int BN, int WM, int WN, int STAGES, int KG = 1>
+template <typename H, int BM, int BN, int WM, int WN, int STAGES, int KG>
 int launch2(const ConvP& p, float* slabs, int splits, hipStream_t s) {
-  const size_t lds = (size_t)KG * STAGES * (BM + BN) * 128;
-  if (lds > 160 * 1024) return -1;
+  constexpr size_t lds = igemm_lds_bytes(BM, BN, STAGES, KG, false);
+  if (lds > kIgemmLdsMax) return -1;
   if (KG == 2 && splits > 1) return -4;
-  long long tiles_m = p.rows_per_batch > 0 ? (long long)p.B * cdiv(p.rows_per_batch, BM) : cdiv(p.M, BM);
-  long long tiles = tiles_m * cdiv(p.Cout, BN);
-  if (splits <= 1) {
-    auto k = igemm2_kernel<H, BM, BN, WM, WN, STAGES, false, KG>;
-    static bool attr = false;
-    if (!attr) { if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -2; attr = true; }
-    hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(256 * KG), lds, s, p, slabs, 1);
-  } else if constexpr (KG == 1) {
-    auto k = igemm2_kernel<H, BM, BN, WM, WN, STAGES, true>;
-    static bool attr = false;
-    if (!attr) { if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -2; attr = true; }
-    hipLaunchKernelGGL(k, dim3((unsigned)(tiles * splits)), dim3(256), lds, s, p, slabs, splits);
-  }
+  const long long tiles = igemm_tiles(p, BM, BN);
+  if (splits <= 1) return igemm_launch<igemm2_kernel<H, BM, BN, WM, WN, STAGES, false, KG>>(tiles, 256 * KG, lds, s, p, slabs, 1);
+  if constexpr (KG == 1) return igemm_launch<igemm2_kernel<H, BM, BN, WM, WN, STAGES, true>>(tiles * splits, 256, lds, s, p, slabs, splits);
   return 0;
 }
 
 }  // namespace
 
-int igemm2_num_variants() { return kNumCfg; }
-void igemm2_variant_shape(int v, int* bm, int* bn, int* stages) { *bm = kCfg[v].bm; *bn = kCfg[v].bn; *stages = kCfg[v].stages; }
+int igemm2_num_variants() { return kNumIgemmCfg16; }
+void igemm2_variant_shape(int v, int* bm, int* bn, int* stages) { *bm = kIgemmCfg[v].bm; *bn = kIgemmCfg[v].bn; *stages = kIgemmCfg[v].stages; }
 
-// Launch variant v.  Returns 0, or a negative value if the variant cannot run this problem.
-#define L2(...) (p.f16 ? launch2<f16_t, __VA_ARGS__>(p, slabs, splits, s) : launch2<bf16_t, __VA_ARGS__>(p, slabs, splits, s))
+// Launch variant v (cfp_conv2d_variant2's ids).  Returns 0, or a negative value if the variant cannot run this problem.
 int igemm2_launch(int v, const ConvP& p, float* slabs, int splits, hipStream_t s) {
+#define L2(id, BM, BN, STAGES, KG, WM, WN, ...) \
+  case id: return p.f16 ? launch2<f16_t, BM, BN, WM, WN, STAGES, KG>(p, slabs, splits, s) : launch2<bf16_t, BM, BN, WM, WN, STAGES, KG>(p, slabs, splits, s);
   switch (v) {
-    case 0: return L2(128, 128, 2, 2, 3);
-    case 1: return L2(128, 128, 2, 2, 2);
-    case 2: return L2(128, 64, 2, 2, 3);
-    case 3: return L2(128, 64, 2, 2, 4);
-    case 4: return L2(64, 64, 2, 2, 3);
-    case 5: return L2(64, 64, 2, 2, 4);
-    case 6: return L2(256, 32, 4, 1, 3);
-    case 7: return L2(256, 32, 4, 1, 2);
-    case 8: return L2(128, 32, 4, 1, 3);
-    case 9: return L2(128, 32, 4, 1, 4);
-    case 10: return L2(256, 16, 4, 1, 2);
-    case 11: return L2(128, 16, 4, 1, 4);
-    case 12: return L2(64, 128, 2, 2, 3);
-    case 13: return L2(64, 64, 2, 2, 2);
-    case 14: return L2(128, 64, 2, 2, 2);
-    case 15: return L2(64, 128, 2, 2, 2);
-    case 16: return L2(128, 32, 4, 1, 2);
-    case 17: return L2(32, 64, 1, 4, 3);
-    case 18: return L2(32, 128, 1, 4, 3);
-    case 19: return L2(64, 64, 2, 2, 2, 2);
-    case 20: return L2(64, 64, 2, 2, 3, 2);
-    case 21: return L2(64, 128, 2, 2, 2, 2);
+    IGEMM_VARIANTS(L2)
     default: return -3;
   }
+#undef L2
 }

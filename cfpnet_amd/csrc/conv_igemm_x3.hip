@@ -20,13 +20,10 @@
 //     [hi(32) | lo(32)] in the lane order above (position 8 fq + e <-> channel 4 fq + e for e < 4, 16 + 4 fq + e - 4 for e >= 4), zero
 //     padded to whole K-steps -- the B fragments are plain 16-byte LDS reads.
 //   * the epilogue stores float32 straight from the accumulators (a lane owns 4 consecutive output channels of one pixel: 16 bytes).
-#include "igemm_core.h"
+#include "igemm_dma_core.h"
 #include "head_stats.h"
-#include "lds_dma.h"
 
 namespace {
-
-template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // The K loop: accumulates C[m0.., n0..] over K-steps [k0, k1) into acc.  smem: KG * STAGES * (BM + BN) * 128 bytes.  All 256 * KG threads call it.
 // INTERLEAVE: fragment i of wave-row wm covers tile rows (i * WM + wm) * 16 .. + 15 instead of (wm * TM + i) * 16 .. (the fused bin head wants
@@ -176,12 +173,7 @@ __device__ __forceinline__ void x3_mainloop(const ConvP& p, const f16_t* __restr
         for (int i = 0; i < TM; ++i) split8(xr[i][0], xr[i][1], ah[S][i], al[S][i]);
       };
       // stage 0 -> register set 0
-      {
-        const int ahead = min(nkg - 1, STAGES - 2);             // stages younger than stage 0 that may stay in flight
-        if (ahead >= 2) wait_vmcnt<(STAGES > 3 ? 2 : 1) * LPS>();
-        else if (ahead == 1) wait_vmcnt<LPS>();
-        else wait_vmcnt<0>();
-      }
+      wait_stage<STAGES, LPS>(min(nkg - 1, STAGES - 2));             // stages younger than stage 0 that may stay in flight
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
       if (STAGES - 1 < nkg) issue(k0 + (STAGES - 1), (STAGES - 1) % STAGES);
@@ -191,10 +183,7 @@ __device__ __forceinline__ void x3_mainloop(const ConvP& p, const f16_t* __restr
         constexpr int C = decltype(CUR)::value, N = C ^ 1;
         const bool more = it + 1 < nit;
         if (more) {
-          const int ahead = min(nkg - 2 - it, STAGES - 2);      // younger stages than it + 1 that may stay in flight
-          if (ahead >= 2) wait_vmcnt<(STAGES > 3 ? 2 : 1) * LPS>();
-          else if (ahead == 1) wait_vmcnt<LPS>();
-          else wait_vmcnt<0>();
+          wait_stage<STAGES, LPS>(min(nkg - 2 - it, STAGES - 2));      // younger stages than it + 1 that may stay in flight
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's fragment reads of stage `it` are in its registers
           __builtin_amdgcn_s_barrier();
           asm volatile("" ::: "memory");
@@ -220,10 +209,7 @@ __device__ __forceinline__ void x3_mainloop(const ConvP& p, const f16_t* __restr
   }
   for (int it = 0; it < nit; ++it) {
     const int buf = it % STAGES;
-    const int ahead = min(nkg - 1 - it, STAGES - 2);
-    if (ahead >= 2) wait_vmcnt<(STAGES > 3 ? 2 : 1) * LPS>();
-    else if (ahead == 1) wait_vmcnt<LPS>();
-    else wait_vmcnt<0>();
+    wait_stage<STAGES, LPS>(min(nkg - 1 - it, STAGES - 2));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // this wave's fragment reads of the previous step are complete (see loftr_tail_x3.hip)
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -498,32 +484,10 @@ __global__ __launch_bounds__(256 * KG, (OCC > 0 ? OCC : 1)) void igemm_x3_kernel
   const int wm = wave / WN, wn = wave % WN;
   const int fr = lane & 15, fq = lane >> 4;
 
-  const int tiles_n = (p.Cout + BN - 1) / BN;
-  int bid = xcd_remap(blockIdx.x, gridDim.x);
-  int sp = 0;
-  if constexpr (SPLITK) { sp = bid % splits; bid /= splits; }
-  const int tile_n = bid % tiles_n;
-  const int tile_m = bid / tiles_n;
   const int nk_all = (p.K + 31) >> 5;
-  int m0, m_end;
-  const f16_t* __restrict__ wt = reinterpret_cast<const f16_t*>(p.w);
-  if (p.rows_per_batch > 0) {
-    const int tpb = (p.rows_per_batch + BM - 1) / BM;
-    const int b = tile_m / tpb;
-    m0 = b * p.rows_per_batch + (tile_m % tpb) * BM;
-    m_end = (b + 1) * p.rows_per_batch;
-    wt += (long long)b * p.w_bstride;
-  } else {
-    m0 = tile_m * BM;
-    m_end = p.M;
-  }
-  const int n0 = tile_n * BN;
-  int k0 = 0, k1 = nk_all;
-  if constexpr (SPLITK) {
-    const int per = (nk_all + splits - 1) / splits;
-    k0 = sp * per;
-    k1 = min(nk_all, k0 + per);
-  }
+  const IgemmTile tile = igemm_tile<BM, BN, SPLITK>(p, splits, nk_all);
+  const int m0 = tile.m0, m_end = tile.m_end, n0 = tile.n0, sp = tile.sp, bid = tile.tile, k0 = tile.k0, k1 = tile.k1;
+  const f16_t* __restrict__ wt = reinterpret_cast<const f16_t*>(p.w) + tile.w_off;
   f32x4 acc[TM][TN];
   if constexpr (AD) x3_mainloop_ad<BM, BN>(p, wt, m0, m_end, n0, nk_all, smem, acc);
   else x3_mainloop<BM, BN, WM, WN, STAGES, KG>(p, wt, m0, m_end, n0, k0, k1, smem, acc);
@@ -531,36 +495,13 @@ __global__ __launch_bounds__(256 * KG, (OCC > 0 ? OCC : 1)) void igemm_x3_kernel
   if constexpr (KG == 2) {
     __syncthreads();   // every wave is done with the operand stages: LDS carries the second group's accumulators to the first
     static_assert(BM * BN * 4 <= KG * STAGES * STAGE_BYTES, "accumulator exchange must fit in the operand LDS");
-    f32x4* xch = reinterpret_cast<f32x4*>(smem) + wave * (TM * TN * 64) + lane;
-    if (kg == 1) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) xch[(i * TN + j) * 64] = acc[i][j];
-    }
-    __syncthreads();
+    kg_exchange(acc, smem, kg, wave, lane);
     if (kg == 1) return;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const f32x4 o = xch[(i * TN + j) * 64];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[i][j][r] += o[r];
-      }
   }
 
   if constexpr (SPLITK) {
     if (tickets == nullptr) {                   // the finishing sum is a second launch (splitk_reduce_kernel)
-      float* slab = slabs + (long long)sp * p.M * p.Cout;
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int m = m0 + a_row0 + i * 16 + fr;
-          const int n = n0 + b_row0 + j * 16 + fq * 4;
-          if (m < m_end && n < p.Cout) *reinterpret_cast<f32x4*>(slab + (long long)m * p.Cout + n) = acc[i][j];
-        }
+      store_slab(acc, slabs + (long long)sp * p.M * p.Cout, p.Cout, m0 + a_row0, m_end, n0 + b_row0, fr, fq);
       return;
     }
     // Ticketed finish: the workgroup that arrives LAST at its output tile sums the slabs -- every one read back from memory in split order, so the
@@ -703,40 +644,17 @@ __global__ __launch_bounds__(256 * KG, (OCC > 0 ? OCC : 1)) void igemm_x3_kernel
   }
 }
 
-struct Cfg { int bm, bn, stages, kg = 1; bool ad = false; };
-// same variant ids as conv_igemm2.hip (the plan function is shared); a K-step here is 32 channels
-constexpr Cfg kCfg[] = {
-    {128, 128, 3}, {128, 128, 2}, {128, 64, 3}, {128, 64, 4}, {64, 64, 3}, {64, 64, 4}, {256, 32, 3}, {256, 32, 2}, {128, 32, 3}, {128, 32, 4},
-    {256, 16, 2}, {128, 16, 4}, {64, 128, 3}, {64, 64, 2}, {128, 64, 2}, {64, 128, 2}, {128, 32, 2}, {32, 64, 3}, {32, 128, 3},
-    {64, 64, 2, 2}, {64, 64, 3, 2}, {64, 128, 2, 2},
-    // f16x3 only (ids >= 22): larger row tiles (fewer L2 -> LDS bytes per MFMA) and the other wave layouts of the common shapes
-    {256, 128, 2}, {256, 64, 2}, {64, 64, 2}, {128, 64, 2}, {128, 128, 2}, {64, 128, 2},
-    // A-direct (ids >= 28): 4 x 1 waves, the A values go global -> registers, only the W tile through LDS
-    {128, 128, 2, 1, true}, {128, 64, 2, 1, true}, {64, 64, 2, 1, true}, {256, 64, 2, 1, true}, {128, 32, 2, 1, true}, {256, 128, 2, 1, true},
-    // ids 34-36: ids 13 / 16 / 15 compiled for 4 / 4 / 3 waves per SIMD (in-flight plans; the same arithmetic in the same order)
-    {64, 64, 2}, {128, 32, 2}, {64, 128, 2},
-};
-constexpr int kNumCfg = sizeof(kCfg) / sizeof(kCfg[0]);
-
-template <int BM, int BN, int WM, int WN, int STAGES, int KG = 1, bool AD = false, int OCC = 0>
+template <int BM, int BN, int WM, int WN, int STAGES, int KG, bool AD, int OCC>
 int launch_x3(const ConvP& p, float* slabs, int splits, hipStream_t s, unsigned* tickets) {
-  const size_t lds = AD ? (size_t)STAGES * BN * 128 : (size_t)KG * STAGES * (BM + BN) * 128;
-  if (lds > 160 * 1024) return -1;
+  constexpr size_t lds = igemm_lds_bytes(BM, BN, STAGES, KG, AD);
+  if (lds > kIgemmLdsMax) return -1;
   if ((KG == 2 || AD || OCC > 0) && splits > 1) return -4;
   if (AD && p.Cin < 8) return -5;
-  long long tiles_m = p.rows_per_batch > 0 ? (long long)p.B * cdiv(p.rows_per_batch, BM) : cdiv(p.M, BM);
-  long long tiles = tiles_m * cdiv(p.Cout, BN);
-  if (splits <= 1) {
-    auto k = igemm_x3_kernel<BM, BN, WM, WN, STAGES, false, KG, AD, OCC>;
-    static bool attr = false;
-    if (!attr) { if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -2; attr = true; }
-    hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(256 * KG), lds, s, p, slabs, 1, (unsigned*)nullptr);
-  } else if constexpr (KG == 1 && !AD && OCC == 0) {
-    auto k = igemm_x3_kernel<BM, BN, WM, WN, STAGES, true>;
-    static bool attr = false;
-    if (!attr) { if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return -2; attr = true; }
+  const long long tiles = igemm_tiles(p, BM, BN);
+  if (splits <= 1) return igemm_launch<igemm_x3_kernel<BM, BN, WM, WN, STAGES, false, KG, AD, OCC>>(tiles, 256 * KG, lds, s, p, slabs, 1, (unsigned*)nullptr);
+  if constexpr (KG == 1 && !AD && OCC == 0) {
     if (tickets && tiles > CFP_TICKET_SLOTS) return -6;
-    hipLaunchKernelGGL(k, dim3((unsigned)(tiles * splits)), dim3(256), lds, s, p, slabs, splits, tickets);
+    return igemm_launch<igemm_x3_kernel<BM, BN, WM, WN, STAGES, true>>(tiles * splits, 256, lds, s, p, slabs, splits, tickets);
   }
   return 0;
 }
@@ -918,51 +836,18 @@ extern "C" int cfp_pack_w_x3_batch(const float* src_base, void* dst_base, const 
   return cfp_check_launch("cfp_pack_w_x3_batch");
 }
 
-int igemm_x3_num_variants() { return kNumCfg; }
-void igemm_x3_variant_shape(int v, int* bm, int* bn, int* stages) { *bm = kCfg[v].bm; *bn = kCfg[v].bn; *stages = kCfg[v].stages; }
+int igemm_x3_num_variants() { return kNumIgemmCfgX3; }
+void igemm_x3_variant_shape(int v, int* bm, int* bn, int* stages) { *bm = kIgemmCfg[v].bm; *bn = kIgemmCfg[v].bn; *stages = kIgemmCfg[v].stages; }
 
 // Launch variant v (conv_igemm2.hip's ids).  Returns 0, or a negative value if the variant cannot run this problem.
 int igemm_x3_launch(int v, const ConvP& p, float* slabs, int splits, hipStream_t s, unsigned* tickets) {
+#define LX3(id, BM, BN, STAGES, KG, WM16, WN16, WM, WN, AD, OCC) case id: return launch_x3<BM, BN, WM, WN, STAGES, KG, AD, OCC>(p, slabs, splits, s, tickets);
   switch (v) {
-    case 0: return launch_x3<128, 128, 2, 2, 3>(p, slabs, splits, s, tickets);
-    case 1: return launch_x3<128, 128, 2, 2, 2>(p, slabs, splits, s, tickets);
-    case 2: return launch_x3<128, 64, 4, 1, 3>(p, slabs, splits, s, tickets);
-    case 3: return launch_x3<128, 64, 4, 1, 4>(p, slabs, splits, s, tickets);
-    case 4: return launch_x3<64, 64, 4, 1, 3>(p, slabs, splits, s, tickets);
-    case 5: return launch_x3<64, 64, 4, 1, 4>(p, slabs, splits, s, tickets);
-    case 6: return launch_x3<256, 32, 4, 1, 3>(p, slabs, splits, s, tickets);
-    case 7: return launch_x3<256, 32, 4, 1, 2>(p, slabs, splits, s, tickets);
-    case 8: return launch_x3<128, 32, 4, 1, 3>(p, slabs, splits, s, tickets);
-    case 9: return launch_x3<128, 32, 4, 1, 4>(p, slabs, splits, s, tickets);
-    case 10: return launch_x3<256, 16, 4, 1, 2>(p, slabs, splits, s, tickets);
-    case 11: return launch_x3<128, 16, 4, 1, 4>(p, slabs, splits, s, tickets);
-    case 12: return launch_x3<64, 128, 2, 2, 3>(p, slabs, splits, s, tickets);
-    case 13: return launch_x3<64, 64, 4, 1, 2>(p, slabs, splits, s, tickets);
-    case 14: return launch_x3<128, 64, 4, 1, 2>(p, slabs, splits, s, tickets);
-    case 15: return launch_x3<64, 128, 2, 2, 2>(p, slabs, splits, s, tickets);
-    case 16: return launch_x3<128, 32, 4, 1, 2>(p, slabs, splits, s, tickets);
-    case 17: return launch_x3<32, 64, 1, 4, 3>(p, slabs, splits, s, tickets);
-    case 18: return launch_x3<32, 128, 1, 4, 3>(p, slabs, splits, s, tickets);
-    case 19: return launch_x3<64, 64, 4, 1, 2, 2>(p, slabs, splits, s, tickets);
-    case 20: return launch_x3<64, 64, 4, 1, 3, 2>(p, slabs, splits, s, tickets);
-    case 21: return launch_x3<64, 128, 2, 2, 2, 2>(p, slabs, splits, s, tickets);
-    case 22: return launch_x3<256, 128, 2, 2, 2>(p, slabs, splits, s, tickets);
-    case 23: return launch_x3<256, 64, 4, 1, 2>(p, slabs, splits, s, tickets);
-    case 24: return launch_x3<64, 64, 2, 2, 2>(p, slabs, splits, s, tickets);
-    case 25: return launch_x3<128, 64, 2, 2, 2>(p, slabs, splits, s, tickets);
-    case 26: return launch_x3<128, 128, 4, 1, 2>(p, slabs, splits, s, tickets);
-    case 27: return launch_x3<64, 128, 4, 1, 2>(p, slabs, splits, s, tickets);
-    case 28: return launch_x3<128, 128, 4, 1, 2, 1, true>(p, slabs, splits, s, tickets);
-    case 29: return launch_x3<128, 64, 4, 1, 2, 1, true>(p, slabs, splits, s, tickets);
-    case 30: return launch_x3<64, 64, 4, 1, 2, 1, true>(p, slabs, splits, s, tickets);
-    case 31: return launch_x3<256, 64, 4, 1, 2, 1, true>(p, slabs, splits, s, tickets);
-    case 32: return launch_x3<128, 32, 4, 1, 2, 1, true>(p, slabs, splits, s, tickets);
-    case 33: return launch_x3<256, 128, 4, 1, 2, 1, true>(p, slabs, splits, s, tickets);
-    case 34: return launch_x3<64, 64, 4, 1, 2, 1, false, 4>(p, slabs, splits, s, tickets);
-    case 35: return launch_x3<128, 32, 4, 1, 2, 1, false, 4>(p, slabs, splits, s, tickets);
-    case 36: return launch_x3<64, 128, 2, 2, 2, 1, false, 3>(p, slabs, splits, s, tickets);
+    IGEMM_VARIANTS(LX3)
+    IGEMM_VARIANTS_X3_ONLY(LX3)
     default: return -3;
   }
+#undef LX3
 }
 
 extern "C" size_t cfp_pack_w_x3_elems(long long rows, int K) { return rows <= 0 || K <= 0 ? 0 : (size_t)rows * ((K + 31) / 32) * 64; }

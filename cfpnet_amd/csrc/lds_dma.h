@@ -15,3 +15,10 @@ __device__ __forceinline__ void glds16(const void* g, unsigned char* lds_wave_ba
 
 // counted wait: all but this wave's N youngest vector-memory operations (they complete in order) have landed
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+
+// ... before a stage of a STAGES-deep pipeline with LPS operations per stage is consumed: `ahead` (<= STAGES - 2) younger stages may stay in flight
+template <int STAGES, int LPS> __device__ __forceinline__ void wait_stage(int ahead) {
+  if (ahead >= 2) wait_vmcnt<(STAGES > 3 ? 2 : 1) * LPS>();
+  else if (ahead == 1) wait_vmcnt<LPS>();
+  else wait_vmcnt<0>();
+}

@@ -926,6 +926,90 @@ def test_pointwise_conv_per_image_weights(B, HW, Cin, Cout, dtype):
     close(out.torch().float().cpu().reshape(B, HW, Cout), ref, dtype, f"per-image weights {B}x{HW}x{Cin}->{Cout}")
 
 
+_PIW_TILES = (3, 70, 72, 40)      # B, rows per image, Cin, Cout: no tile height divides 70 rows (every tile meets the m_end guard and the
+                                   # per-image weight offset), K = 72 is a tail of the 64- and the 32-channel K-step, Cout = 40 of every BN
+
+
+@functools.lru_cache(maxsize=None)
+def _piw_tiles_problem(dtype):
+    B, HW, Cin, Cout = _PIW_TILES
+    x = q(rnd(B, HW, Cin, seed=1), dtype)
+    w = q(rnd(B, Cout, Cin, seed=2, scale=1.0 / math.sqrt(Cin)), dtype)
+    scale, shift = rnd(Cout, seed=3).abs() + 0.5, rnd(Cout, seed=4)
+    res = q(rnd(B, HW, Cout, seed=5), dtype)
+    ref = torch.einsum("bmk,bnk->bmn", x.double(), w.double()) * scale.double() + shift.double() + res.double()
+    return x, w, scale.to(DEV), shift.to(DEV), res, ref
+
+
+@pytest.mark.parametrize("dtype", HALF)
+def test_pointwise_conv_per_image_weights_every_gen2_tile(dtype):
+    """Per-image weights through every forced 16-bit tile 0-21: rows_per_batch ends inside a tile, K and Cout tails."""
+    B, HW, Cin, Cout = _PIW_TILES
+    x, w, scale, shift, res, ref = _piw_tiles_problem(dtype)
+    xa, wa, ra = to_act(x.reshape(B * HW, Cin), dtype), w.to(dtype).to(DEV).contiguous(), to_act(res.reshape(B * HW, Cout), dtype)
+    lib = hip.load()
+    try:
+        lib.cfp_debug_set(1, 1)
+        for variant in GEN2_VARIANTS:
+            lib.cfp_debug_set(0, variant)
+            out = ops.new_act(B * HW, Cout, dtype, DEV, zero=True)
+            ops.conv2d(xa, wa, scale, shift, out, B, 1, HW, 1, 1, 1, 0, 0, 1, HW, hip.ACT_NONE, ra, None, per_image_weights=True)
+            torch.cuda.synchronize()
+            close(out.torch().float().cpu().reshape(B, HW, Cout), ref.float(), dtype, f"per-image weights, gen2 v{variant}")
+    finally:
+        lib.cfp_debug_set(0, -1)
+        lib.cfp_debug_set(1, -1)
+
+
+def test_pointwise_conv_per_image_weights_every_x3_tile():
+    """... and through every forced f16x3 tile 0-36 (pre-split per-image operands)."""
+    B, HW, Cin, Cout = _PIW_TILES
+    x, w, scale, shift, res, ref = _piw_tiles_problem(torch.float32)
+    xa, ra = to_act(x.reshape(B * HW, Cin), torch.float32), to_act(res.reshape(B * HW, Cout), torch.float32)
+    wx = ops.pack_w_x3(w.reshape(B * Cout, Cin).to(DEV)).reshape(B, Cout, -1)
+    lib = hip.load()
+    try:
+        lib.cfp_debug_set(1, 1)
+        for variant in range(37):
+            lib.cfp_debug_set(0, 400 + variant)
+            out = ops.new_act(B * HW, Cout, torch.float32, DEV, zero=True)
+            ops.conv2d(xa, wx, scale, shift, out, B, 1, HW, 1, 1, 1, 0, 0, 1, HW, hip.ACT_NONE, ra, None, per_image_weights=True)
+            torch.cuda.synchronize()
+            _x3_close(out.torch().cpu().reshape(B, HW, Cout), ref, f"per-image weights, x3 v{variant}")
+    finally:
+        lib.cfp_debug_set(0, -1)
+        lib.cfp_debug_set(1, -1)
+
+
+@pytest.mark.parametrize("dtype", HALF)
+def test_pointwise_two_term_weights_every_gen2_tile(dtype):
+    """Two-term weights through every forced 16-bit tile 0-21 on the 210 x 72 -> 40 problem: the reference and the bound of
+    test_pointwise_two_term_weights (as good as the output store allows, better than the one-term layer through the same tile)."""
+    B, HW, Cin, Cout = _PIW_TILES
+    rows = B * HW
+    x = q(rnd(rows, Cin, seed=1), dtype)
+    w = rnd(Cout, Cin, seed=2, scale=1.0 / math.sqrt(Cin))
+    sc, sh = 0.5 + torch.rand(Cout, generator=torch.Generator().manual_seed(3)), rnd(Cout, seed=4, scale=0.2)
+    ref = (x.double() @ w.double().t()) * sc.double() + sh.double()
+    store = float((ref.float().to(dtype).double() - ref).abs().sum() / ref.abs().sum())     # what the output rounding alone costs
+    xa, w1, w2 = to_act(x, dtype), w.to(dtype).to(DEV).contiguous(), ops.pack_w2(w, dtype).to(DEV).contiguous()
+    lib = hip.load()
+    try:
+        lib.cfp_debug_set(1, 1)
+        for variant in GEN2_VARIANTS:
+            lib.cfp_debug_set(0, variant)
+            err = {}
+            for two, wp in ((False, w1), (True, w2)):
+                out = ops.new_act(rows, Cout, dtype, DEV)
+                ops.linear(xa, wp, sc.to(DEV), sh.to(DEV), out, rows)
+                err[two] = float((out.torch().float().cpu().double() - ref).abs().sum() / ref.abs().sum())
+            print(f"{dtype} v{variant}: rel-L1 one-term {err[False]:.2e}, two-term {err[True]:.2e}, output store alone {store:.2e}")
+            assert err[True] < 1.15 * store + 1e-6 and err[True] < err[False], variant
+    finally:
+        lib.cfp_debug_set(0, -1)
+        lib.cfp_debug_set(1, -1)
+
+
 ACT_REF = {hip.ACT_NONE: lambda t: t, hip.ACT_RELU: F.relu, hip.ACT_LRELU: lambda t: F.leaky_relu(t, 0.01), hip.ACT_SILU: F.silu,
            hip.ACT_GELU: F.gelu, hip.ACT_SIGMOID: torch.sigmoid}
 
