@@ -360,8 +360,11 @@ class _CapturedTrainStep:
             self.pred, self.edges, (B, h, w) = self.net.forward(self.tape, self.inp, offs_dev, zone_dev)
         self.shape = (B, 1, h, w)
         self.gpred = torch.zeros(B * h * w, 1, dtype=torch.float32, device=dev)
+        self.gedges = torch.zeros_like(self.edges)       # gradient of a loss on `bin_edges`; zero when no loss touches them
+        self._gedges_set, self._gpred_set = False, False
         with torch.cuda.graph(self.gb, pool=self.gf.pool()):
             self.pred.g = self.gpred
+            self.tape.acc(self.net.widths, _edges_grad_to_widths(self.gedges, model.min_val, model.max_val))
             self.tape.backward()
             g = self.net.grads()
             self.grads = [g.get(n) for n in self.names]
@@ -384,8 +387,13 @@ class _CapturedTrainStep:
         self.gf.replay()
         return self.edges.clone(), self.pred.t.reshape(self.shape).clone()
 
-    def backward(self, g_pred):
-        self.gpred.copy_(g_pred.reshape(-1, 1))
+    def backward(self, g_pred, g_edges=None):
+        for buf, g, flag in ((self.gpred, g_pred, "_gpred_set"), (self.gedges, g_edges, "_gedges_set")):
+            if g is not None:
+                buf.copy_(g.reshape(buf.shape))
+            elif getattr(self, flag):                   # left over from a step whose loss used this output
+                buf.zero_()
+            setattr(self, flag, g is not None)
         self.gb.replay()
         # a contiguous gradient could be adopted by autograd as `.grad` without a copy and would then alias this static buffer
         return tuple(None if g is None else (g.clone() if g.is_contiguous() else g) for g in self.grads)
@@ -414,7 +422,7 @@ class _TrainStep(torch.autograd.Function):
             ctx.cap = cap
             edges, pred = cap.forward(input_data, pos_offsets)
             ctx.generation = cap.generation
-            ctx.mark_non_differentiable(edges)
+            ctx.set_materialize_grads(False)
             return edges, pred
         ctx.cap = None
         sd = {k: v.detach() for k, v in model.state_dict(keep_vars=True).items()}
@@ -425,20 +433,36 @@ class _TrainStep(torch.autograd.Function):
         tape = net.new_tape()
         pred, edges, (B, h, w) = net.forward(tape, input_data, pos_offsets)
         ctx.net, ctx.tape, ctx.pred = net, tape, pred
-        ctx.mark_non_differentiable(edges)
+        ctx.min_max = (model.min_val, model.max_val)
+        ctx.set_materialize_grads(False)              # a loss on `pred` alone hands no edge gradient in: exactly the launches of before
         return edges, pred.t.reshape(B, 1, h, w)
 
     @staticmethod
-    def backward(ctx, _g_edges, g_pred):
+    def backward(ctx, g_edges, g_pred):
+        """`g_edges`: the gradient of a loss on the returned bin edges (train_ops.bins_chamfer), None when no loss touches them.  It
+        enters the tape at the normalised widths (`_edges_grad_to_widths`), before the tape's backward runs."""
         if ctx.cap is not None:
             if ctx.generation != ctx.cap.generation:
                 raise RuntimeError("cfpnet_amd: backward of a training-mode forward whose activations were overwritten by a later forward "
                                    "of the same captured step (two forwards before one backward); set model.train_graphs = False for that pattern")
-            return (None, None, None, None) + ctx.cap.backward(g_pred.to(torch.float32))
-        ctx.pred.g = g_pred.reshape(-1, 1).to(torch.float32).contiguous()
+            return (None, None, None, None) + ctx.cap.backward(None if g_pred is None else g_pred.to(torch.float32),
+                                                               None if g_edges is None else g_edges.to(torch.float32))
+        if g_pred is None:
+            ctx.pred.g = torch.zeros_like(ctx.pred.t, dtype=torch.float32)
+        else:
+            ctx.pred.g = g_pred.reshape(-1, 1).to(torch.float32).contiguous()
+        if g_edges is not None:
+            ctx.tape.acc(ctx.net.widths, _edges_grad_to_widths(g_edges.to(torch.float32), *ctx.min_max))
         ctx.tape.backward()
         grads = ctx.net.grads()
         return (None, None, None, None) + tuple(grads.get(n) for n in ctx.names)
+
+
+def _edges_grad_to_widths(g_edges: torch.Tensor, min_val: float, max_val: float) -> torch.Tensor:
+    """Adjoint of deltar.py:53-57's edges w.r.t. the normalised widths: e_0 = min_val, e_k = min_val + (max_val - min_val) sum_{i<k} wn_i,
+    so d/d wn_i = (max_val - min_val) sum_{k>i} g_e[k].  [B, P+1] -> [B, P].  For the gradient of a loss on the centres folded to the
+    edges (g_e[k] = 0.5 (g_c[k-1] + g_c[k])) this is cfp_bin_centers_bwd of that centre gradient."""
+    return ((max_val - min_val) * g_edges[:, 1:].flip(1).cumsum(1).flip(1)).contiguous()
 
 
 def _train_numerics(model):

@@ -80,6 +80,8 @@ SIGNATURES = {
     "cfp_silog_ws_bytes": (_sz, [_i, _i, _i]),
     "cfp_silog_loss_fwd": (_i, [_p, _i, _i, _p, _p, _i, _i, _i, _i, _p, _sz, _p, _p]),
     "cfp_silog_loss_bwd": (_i, [_p, _p, _f, _i, _i, _i, _i, _i, _i, _p, _p]),
+    "cfp_bins_chamfer_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "cfp_bins_chamfer": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _p, _sz, _p, _p, _p]),
     "cfp_adamw_step": (_i, [_p, _p, _p, _p, C.c_longlong, _f, _f, _f, _f, _f, _i, _p, _p]),
     "cfp_grad_clip_ws_bytes": (_sz, []),
     "cfp_grad_clip_factor": (_i, [_p, C.c_longlong, _f, _p, _sz, _p, _p]),

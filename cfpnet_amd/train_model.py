@@ -85,6 +85,9 @@ class TrainNet:
         self.se_fused = os.environ.get("CFP_SE_FUSED_TRAIN", "1") != "0"      # squeeze-excite gate + its backward as three kernels (csrc/se_train.hip)
         self.side_stream: Optional[torch.cuda.Stream] = None      # set by the trainer: parameter gradients beside the dY -> dX chain
         self._open_tape = None
+        self.centers, self.widths = None, None            # the last forward's bin centres and normalised widths (tape values)
+        self._chamfer = train_ops.BinsChamferLoss()       # keeps its workspace between steps
+        self.last_chamfer: Optional[torch.Tensor] = None  # device scalar of the last forward_backward(w_chamfer > 0)
         self.flipped: Dict[str, torch.Tensor] = {}        # bound mode: name -> flipped conv weight, refreshed by the trainer every step
         self.packed: Dict[str, torch.Tensor] = {}         # bound f16x3 mode: name -> pre-split forward operand, refreshed every step
         self.packed_t: Dict[str, torch.Tensor] = {}       # ... and the pre-split operand of the data gradient (flipped / transposed weights)
@@ -519,19 +522,24 @@ class TrainNet:
         y = t.add_const(t.act(y, hip.ACT_RELU), torch.full((self.n_bins,), 0.1, dtype=torch.float32, device=dev))     # norm == 'linear'
         wn = t.row_normalize(y)
         edges, centers = t.bin_centers(wn, self.min_val, self.max_val)
+        # tape values a loss on the bins accumulates into before the backward runs: w_chamfer at the centres, a gradient on `edges` at the widths
+        self.centers, self.widths = centers, wn
         logits = pw(ram, "conv_out.0", h0, w0)
         pred = t.softmax_expect(logits, centers, B, h0 * w0)
         return pred, edges, (B, h0, w0)
 
     def forward_backward(self, input_data: dict, target: torch.Tensor, loss_mask: Optional[torch.Tensor] = None, pos_offsets: Optional[dict] = None,
                          stop_before_encoder: bool = False, loss_sync=None, stop: Optional[str] = None, defer_param_grads: bool = False,
-                         zone_records: Optional[dict] = None):
+                         zone_records: Optional[dict] = None, w_chamfer: float = 0.0):
         """One forward in training mode + SILog + backward.  Returns (loss as a device scalar, pred [B,1,H/2,W/2], edges);
         gradients are in `self.grads()`, running statistics in `self.buf`.  `stop_before_encoder`: the backward stops where the
         RGB encoder's begins (every non-encoder parameter gradient is final) and `finish_backward()` runs the rest.
         `loss_sync` = (torch.distributed module, world size): the loss is the global-batch SILog over the ranks (SILogLoss.sync_moments).
         `stop`: any tape mark (BACKWARD_MARKS) instead of "encoder"; `finish_backward(stop=...)` continues to the next one.
-        `defer_param_grads`: weight / bias gradient kernels are queued on the tape; `run_deferred_param_grads()` issues them."""
+        `defer_param_grads`: weight / bias gradient kernels are queued on the tape; `run_deferred_param_grads()` issues them.
+        `w_chamfer` > 0: the objective is SILog + w_chamfer * bin-centre chamfer loss (train_ops.BinsChamferLoss on `edges`, the full
+        resolution target and the same mask); its gradient enters the tape at the bin centres.  The returned loss stays the SILog
+        scalar, the chamfer value is the device scalar `self.last_chamfer` (None when the weight is 0: no launch is added)."""
         dev = self.dev
         t = self.new_tape(side=self.side_stream)
         t.defer = defer_param_grads
@@ -545,6 +553,12 @@ class TrainNet:
             loss = crit.sync_moments(loss_sync[0])
             gl = float(loss_sync[1])                                            # the gradient average over the ranks divides by it again
         pred.g = crit.backward(gl).reshape(-1, 1).contiguous()
+        self.last_chamfer = None
+        if w_chamfer > 0.0:
+            # a per-rank mean over images averaged over equal-sized ranks is already the global mean: no world-size factor under loss_sync
+            self.last_chamfer = self._chamfer.forward(edges, target.to(dev, torch.float32), loss_mask.to(dev) if loss_mask is not None else None,
+                                                      grad_scale=float(w_chamfer))
+            t.acc(self.centers, self._chamfer.grad_centers)
         stop = stop or ("encoder" if stop_before_encoder else None)
         t.backward(stop=stop)
         self._open_tape = t if (stop is not None or defer_param_grads) else None

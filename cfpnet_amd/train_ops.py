@@ -82,6 +82,82 @@ class SILogLoss:
         return grad
 
 
+class BinsChamferLoss:
+    """Bin-centre chamfer loss (include/cfpnet_hip.h, cfp_bins_chamfer; the `w_chamfer` term of the AdaBins recipe, none in the
+    reference): call with (edges [B,P+1] f32, target [B,1,Ht,Wt] f32, mask bool|None; None: target >= 1e-3).  `forward` returns the
+    device scalar, `backward(grad_loss)` d loss / d centres [B,P] -- `cfp_bin_centers_bwd` carries it to the widths.  One call computes
+    both: `forward(..., grad_scale=s)` already leaves s * d loss / d centres in `grad_centers`, `backward` rescales that.  `per_image`
+    [B] holds the L_b.  The workspace is kept between calls."""
+
+    name = "BinsChamfer"
+
+    def __init__(self):
+        self._ws: Optional[torch.Tensor] = None
+        self._out: Optional[torch.Tensor] = None
+        self.grad_centers: Optional[torch.Tensor] = None
+        self._scale = 1.0
+
+    def forward(self, edges: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor] = None, grad_scale: float = 1.0):
+        assert edges.is_cuda and edges.dtype == torch.float32 and target.dtype == torch.float32 and edges.dim() == 2
+        B, P = edges.shape[0], edges.shape[1] - 1
+        Ht, Wt = target.shape[-2:]
+        assert target.numel() == B * Ht * Wt, (tuple(edges.shape), tuple(target.shape))
+        edges, target = edges.contiguous(), target.to(edges.device).contiguous()
+        m8 = None
+        if mask is not None:
+            m8 = mask.to(device=edges.device).reshape(B, 1, Ht, Wt).to(torch.uint8).contiguous()
+        need = int(hip.load().cfp_bins_chamfer_ws_bytes(B, Ht, Wt, P))
+        if self._ws is None or self._ws.numel() < max(need, 16) or self._ws.device != edges.device:
+            self._ws = torch.empty(max(need, 16), dtype=torch.uint8, device=edges.device)
+        self._out = torch.empty(1 + B, dtype=torch.float32, device=edges.device)
+        self.grad_centers = torch.empty(B, P, dtype=torch.float32, device=edges.device)
+        self._scale = float(grad_scale)
+        hip.call("cfp_bins_chamfer", edges.data_ptr(), target.data_ptr(), hip.ptr(m8), B, Ht, Wt, P, self._scale, self._ws.data_ptr(),
+                 self._ws.numel(), self._out.data_ptr(), self.grad_centers.data_ptr(), hip.current_stream())
+        return self._out[0]
+
+    __call__ = forward
+
+    @property
+    def per_image(self) -> torch.Tensor:
+        return self._out[1:]
+
+    def backward(self, grad_loss: float = 1.0) -> torch.Tensor:
+        if float(grad_loss) == self._scale:
+            return self.grad_centers
+        if self._scale == 0.0:
+            raise RuntimeError("BinsChamferLoss.forward ran with grad_scale 0: there is no gradient to rescale")
+        return self.grad_centers * (float(grad_loss) / self._scale)
+
+
+def centers_grad_to_edges(g_centers: torch.Tensor) -> torch.Tensor:
+    """Adjoint of c_p = 0.5 (e_p + e_{p+1}): g_e[k] = 0.5 (g_c[k-1] + g_c[k]), [B,P] -> [B,P+1]."""
+    ge = g_centers.new_zeros(g_centers.shape[0], g_centers.shape[1] + 1)
+    ge[:, :-1] += 0.5 * g_centers
+    ge[:, 1:] += 0.5 * g_centers
+    return ge
+
+
+class _BinsChamfer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, edges, target, mask):
+        crit = BinsChamferLoss()
+        loss = crit.forward(edges.detach().float(), target.detach().float(), mask)
+        ctx.save_for_backward(centers_grad_to_edges(crit.grad_centers))
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        (ge,) = ctx.saved_tensors
+        return ge * g, None, None
+
+
+def bins_chamfer(edges: torch.Tensor, target: torch.Tensor, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The chamfer loss as a torch loss, differentiable w.r.t. `edges` (the first value `model.train()(x)` returns):
+    `loss = silog(pred, ...) + 0.1 * bins_chamfer(bin_edges, depth, mask)`.  Value and gradient come from one cfp_bins_chamfer call."""
+    return _BinsChamfer.apply(edges, target, mask)
+
+
 class OneCycle:
     """torch.optim.lr_scheduler.OneCycleLR as train.py:90-94 configures it: cosine annealing, pct_start 0.3,
     two phases, momentum (AdamW beta1) cycled inversely between base_momentum and max_momentum.  Note the reference

@@ -27,8 +27,10 @@ class Trainer:
                  device="cuda:0", dist=None, world: int = 1, n_bins: int = 256, min_val: float = 1e-3, max_val: float = 10.0,
                  change_embedding: bool = True, dtype=torch.float32, no_skip_inside: bool = False, norm: str = "linear", kernel_layout: bool = True,
                  base_resolution=spec.BASE_RESOLUTION, overlap_param_grads: bool = False, comm: str = "overlap", sync_loss: bool = False,
-                 zone_offset_bound: int = 0, zone_layout=None):
-        """`zone_offset_bound` k > 0: per-sample zone-grid offsets in [-k, k] (`--train_zone_random_offset`).  The batch's zone
+                 zone_offset_bound: int = 0, zone_layout=None, w_chamfer: float = 0.0):
+        """`w_chamfer` F > 0: the objective of a step is SILog + F * bin-centre chamfer loss (TrainNet.forward_backward); `step` still
+        returns the SILog scalar, `last_chamfer` is the chamfer value.  0 (default) adds no launch.
+        `zone_offset_bound` k > 0: per-sample zone-grid offsets in [-k, k] (`--train_zone_random_offset`).  The batch's zone
         rectangle of each fusion scale is then a device record written by every `step` (TrainNet's dynamic-geometry form), so the
         captured step follows it; `zone_layout` = tof.zone_layout(...) (None: read from the first batch)."""
         self.dev = torch.device(device)
@@ -48,6 +50,9 @@ class Trainer:
         self._pending_opt = None         # optimizer state loaded before the first batch fixed the kernel layouts
         self._flip_jobs = None           # [(source buffer, flipped buffer, device descriptors, n, workgroups, dtype code)]
         self.dist, self.world = dist, world
+        self.w_chamfer = float(w_chamfer)
+        if not self.w_chamfer >= 0.0:
+            raise ValueError(f"w_chamfer must be >= 0, got {w_chamfer!r}")
         # sync_loss: the SILog loss over the GLOBAL batch (its three moments all-reduced), as the reference's nn.DataParallel loop
         # computes it; default is the per-rank loss of DistributedDataParallel-style training (SURVEY 8e documents the difference)
         self.sync_loss = bool(sync_loss) and dist is not None and world > 1
@@ -198,6 +203,12 @@ class Trainer:
             offs[name] = (oy, ox)
         return offs
 
+    @property
+    def last_chamfer(self) -> Optional[torch.Tensor]:
+        """The chamfer loss of the last step as a device scalar (None with w_chamfer == 0).  In a captured step it is the graph's own
+        output tensor: read it before the next step."""
+        return self.net.last_chamfer
+
     def _loss_sync(self):
         return (self.dist, self.world) if self.sync_loss else None
 
@@ -212,12 +223,12 @@ class Trainer:
                 self._refresh_weight_flips()
             loss, _, _ = self.net.forward_backward(input_data, target, target > self.min_val, pos_offsets=offs,
                                                    stop_before_encoder=stop_before_encoder, loss_sync=self._loss_sync(), stop=stop,
-                                                   defer_param_grads=defer, zone_records=self._zone_dev)
+                                                   defer_param_grads=defer, zone_records=self._zone_dev, w_chamfer=self.w_chamfer)
             if self._flip_jobs is None:
                 self._plan_weight_flips()
             return loss                                             # every gradient is already at its flat address
         loss, pred, _ = self.net.forward_backward(input_data, target, target > self.min_val, pos_offsets=offs, loss_sync=self._loss_sync(),
-                                                  zone_records=self._zone_dev)
+                                                  zone_records=self._zone_dev, w_chamfer=self.w_chamfer)
         self.flat.grad.zero_()
         for name, g in self.net.grads().items():
             self.flat.view(name, "grad").copy_(g)
@@ -426,11 +437,14 @@ class Trainer:
         if self.kernel_layout and self._to_torch is None:
             raise RuntimeError("optimizer state exists only after the first training step fixed the kernel layouts")
         return {"format": "cfpnet_amd.FlatAdamW/1", "kernel_layout": self._to_torch is not None, "step_count": self.opt.step_count,
-                "layout": self._layout_signature(), "exp_avg": self.opt.m.detach().cpu().clone(), "exp_avg_sq": self.opt.v.detach().cpu().clone()}
+                "w_chamfer": self.w_chamfer, "layout": self._layout_signature(), "exp_avg": self.opt.m.detach().cpu().clone(), "exp_avg_sq": self.opt.v.detach().cpu().clone()}
 
     def load_optimizer_state_dict(self, state: dict) -> None:
         if state.get("format") != "cfpnet_amd.FlatAdamW/1":
             raise ValueError("not a cfpnet_amd optimizer state (the reference's torch AdamW state is not restored by train.py:83-84 either)")
+        if float(state.get("w_chamfer", 0.0)) != self.w_chamfer:         # the moments belong to another objective
+            raise ValueError(f"optimizer state was saved by a run with w_chamfer={float(state.get('w_chamfer', 0.0))}; "
+                             f"this Trainer has w_chamfer={self.w_chamfer}")
         if state["kernel_layout"] and self._to_torch is None:
             if not self.kernel_layout:
                 raise ValueError("optimizer state was saved in kernel layout; this Trainer keeps the reference layout")

@@ -543,6 +543,22 @@ int cfp_silog_loss_fwd(const float* pred, int Hp, int Wp, const float* target, c
 int cfp_silog_loss_bwd(const void* ws, const float* stats, float grad_loss, int Hp, int Wp, int Ht, int Wt, int B,
                        int interpolate, float* grad_pred, cfp_stream_t stream);
 
+/* Bin-centre chamfer loss (the `w_chamfer` term of the AdaBins training recipe; none in the reference), value and gradient, f32.
+ * Per image b:  centres c_p = 0.5 (e_p + e_{p+1}), p = 0..P-1, from edges [B,P+1] (strictly increasing: the caller's duty, not checked);
+ * target points T_b = { target[b,y,x] : mask[b,y,x] != 0 } at the full target size (mask NULL: target >= 1e-3), N_b = |T_b|;
+ *   L_b = (1/P) sum_p min_{t in T_b} (c_p - t)^2 + (1/N_b) sum_{t in T_b} min_p (c_p - t)^2,      L = (1/B) sum_b L_b.
+ * An image with N_b = 0 contributes 0 to the loss and 0 to the gradient; the denominator stays B.  Ties: the lower centre index wins,
+ * and the lower target value wins.  loss [1+B] (device) = {L, L_0 .. L_{B-1}}; grad_centers [B,P] (may be NULL) = grad_scale * dL/dc,
+ * which cfp_bin_centers_bwd carries on to the widths.  One pass over the pixels (a binary search over the sorted centres per pixel, no
+ * N x P comparison), a finalising launch per image and a one-wave mean.  Deterministic like cfp_silog_loss_fwd: per-workgroup partials
+ * in ws (cfp_bins_chamfer_ws_bytes, 16-byte aligned) combined in index order, f64 sums in fixed-order trees, and the only atomics are
+ * integer ones in LDS (order-independent): min / max of the targets per interval, and the per-centre sum of d = t - c_nearest in fixed
+ * point with quantum 2^-40, |d| clamped to 2047 (depths are metres), moved to f64 every 4096 pixels of a workgroup, so no image size
+ * overflows it.  No host sync, no allocation, graph-capturable.  1 <= P <= 1024 and B*Ht*Wt < 2^31, otherwise CFP_ESHAPE. */
+size_t cfp_bins_chamfer_ws_bytes(int B, int Ht, int Wt, int P);
+int cfp_bins_chamfer(const float* edges, const float* target, const unsigned char* mask, int B, int Ht, int Wt, int P,
+                     float grad_scale, void* ws, size_t ws_bytes, float* loss, float* grad_centers, cfp_stream_t stream);
+
 /* torch.optim.AdamW step (train.py:82,131) over one contiguous segment of flat f32 buffers: `step` is the
  * 1-based step count of the group, beta1 may change per step (OneCycleLR cycles it, train.py:90-94).
  * grad_scale (device, may be NULL) multiplies the gradient first: the clip factor of cfp_grad_clip_factor. */

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Training with the reference's CLI and loop (`/root/reference/train.py:41-209`):
 
-    python train.py @configs/cfpnet_combine1.txt [--synthetic N] [--max_steps K] [--stop_after K] [--seed S] [--save weights/x.pt] [--dtype bf16|f16|f32|f32x3] [--eager] [--validate N]
+    python train.py @configs/cfpnet_combine1.txt [--synthetic N] [--max_steps K] [--stop_after K] [--seed S] [--save weights/x.pt] [--dtype bf16|f16|f32|f32x3] [--eager] [--validate N] [--w_chamfer F]
                     [--resume checkpoints/x.pt] [--weight_path weights/x.pt] [--backend nccl|gloo] [--local_gpu I]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py @configs/cfpnet_combine1.txt --synthetic 4096
 
@@ -21,6 +21,11 @@ metrics) runs at the end of every epoch whose step count is a multiple of `--val
 `<epoch>_<rmse>.pt` and `best.pt` next to `--save`, and once more at the end.
 bf16 activations with float32 master parameters by default (`--dtype`); the step is replayed as one HIP graph unless
 `--eager`.  There is no PyTorch autograd or fallback anywhere in the step.
+
+`--w_chamfer F` (not a reference flag; default 0 = off) makes the objective of a step SILog + F x the bin-centre chamfer loss between the
+adaptive bin centres and the valid depths of each image (`cfp_bins_chamfer`): the `w_chamfer` term of the AdaBins recipe,
+on the `bin_edges` the training forward returns.  The logged `loss` stays the SILog value, `chamfer=` is printed next to it, and the
+weight is stored with the optimizer state: `--resume` with another weight is refused.
 
 `--train_zone_random_offset K` jitters the ToF zone grid like dataloader.py:94-103: every step draws one offset per sample with
 `random.randint(-K, K)` (seeded by `--seed`), shifts that sample's grid by it in y and in x, simulates its histograms there and
@@ -184,6 +189,7 @@ def main(argv=None):
     save_path = _pop(argv, "--save", "", str)
     log_every = _pop(argv, "--log_every", 10, int)
     n_val = _pop(argv, "--validate", 0, int)
+    w_chamfer = _pop(argv, "--w_chamfer", 0.0, float)    # objective = SILog + F * bin-centre chamfer loss (not a reference flag: popped here)
     dtype = TRAIN_DTYPES[_pop(argv, "--dtype", "bf16")]
     backend = _pop(argv, "--backend", "nccl")        # "gloo": ranks may share one GPU (tests), buckets staged through the host
     local_gpu = _pop(argv, "--local_gpu", None, int)
@@ -246,7 +252,7 @@ def main(argv=None):
                  clip_grad_norm=None if args.disable_clip_grad else 0.1, device=dev, dist=dist, world=world, n_bins=int(args.n_bins),
                  min_val=float(args.min_depth), max_val=float(args.max_depth), change_embedding=bool(args.change_embedding), dtype=dtype, no_skip_inside=bool(getattr(args, "no_skip_inside", False)),
                  norm=str(args.norm), sync_loss=sync_loss, zone_offset_bound=zone_offset,
-                 zone_layout=zone_layout(args, H, W) if zone_offset > 0 else None)
+                 zone_layout=zone_layout(args, H, W) if zone_offset > 0 else None, w_chamfer=w_chamfer)
     if opt_state is not None:
         tr.load_optimizer_state_dict(opt_state)
     elif start_step > 0:
@@ -364,7 +370,8 @@ def main(argv=None):
             if rank == 0 and (step % log_every == 0 or step == 1 or step == total_steps):
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
-                print(f"epoch {epoch + 1} step {step}/{total_steps} loss {float(loss):.4f} lr {lr:.2e} beta1 {beta1:.3f} {seen / dt:.1f} samples/s", flush=True)
+                cham = f" chamfer={float(tr.last_chamfer):.4f}" if w_chamfer > 0 else ""
+                print(f"epoch {epoch + 1} step {step}/{total_steps} loss {float(loss):.4f}{cham} lr {lr:.2e} beta1 {beta1:.3f} {seen / dt:.1f} samples/s", flush=True)
         if rank == 0 and n_val > 0 and step % max(1, int(args.validate_every)) == 0 and step != last_validated:      # train.py:137: end of epoch
             validate(step, epoch)
         if stop_after and steps_here >= stop_after:
