@@ -11,16 +11,17 @@
 //   3. the run of consecutive non-zero bins with the largest sum survives (first on ties)
 //   4. n, mask = n > 0, mu and sigma over bin centres in float64 (ascending-bin order, no FMA contraction)
 //   5. S samples w0*(mu-3sigma) + w1*(mu+3sigma) in float64 rounded to float32 (zero for masked-out zones)
+// The bin of step 1 and steps 2-4 are the sensor model of tof_cluster.h, shared with zone_consistency.hip (the same model applied to
+// the prediction).
 //
 // Roofline: HBM-bound by construction -- 4 bytes read per depth pixel inside the zone grid, ~200 bytes written per
 // zone -- but at B=8 that is 6.4 MB, i.e. ~1.5 us of HBM time: the launch is latency bound (one pass over <= 16
 // pixels per thread, LDS atomics, a <= 250-bin scan).
 #include "common.h"
+#include "tof_cluster.h"
 
 namespace {
 
-constexpr int kTofThreads = 256;
-constexpr int kTofMaxBins = 1024;
 constexpr int kTofBatch = 8;         // pixels per thread in flight
 
 // Step 5 for one (zone, sample): both branches of sample_point_from_hist_parallel (dataloader.py:65-80) in float64, rounded to
@@ -58,11 +59,9 @@ __global__ __launch_bounds__(kTofThreads) void tof_hist_kernel(TofP p) {
   if (tid == 0) best = 0ull;
   __syncthreads();
 
-  // 1. histogram.  Lanes of a wave that hit the same bin are merged with a ballot so a flat zone (every pixel in
-  //    two or three bins) does not serialise 64-way on one LDS counter.
+  // 1. histogram (tof_cluster.h: the bin of histc; equal bins of a wave merged with a ballot before the LDS atomic)
   const float* img = p.depth + (long long)b * p.img_stride;
   const int npx = p.zone_px * p.zone_px;
-  const float fb = (float)p.bins;
   for (int c0 = 0; c0 < npx; c0 += kTofThreads * kTofBatch) {
     // all loads of the batch are issued before the first bin is computed: one HBM round trip per 8 pixels/thread
     float v[kTofBatch];
@@ -73,76 +72,21 @@ __global__ __launch_bounds__(kTofThreads) void tof_hist_kernel(TofP p) {
       v[u] = img[(long long)(sy + y) * p.W + (sx + x)];
     }
 #pragma unroll
-    for (int u = 0; u < kTofBatch; ++u) {
-      int bin = -1;
-      if (c0 + u * kTofThreads + tid < npx && v[u] >= 0.f && v[u] <= p.max_d) {
-        bin = (int)(((v[u] - 0.f) * fb) / (p.max_d - 0.f));
-        if (bin == p.bins) bin = p.bins - 1;
-      }
-      unsigned long long todo = __ballot(bin >= 0);
-      while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const int lb = __builtin_amdgcn_readlane(bin, leader);
-        const unsigned long long same = __ballot(bin == lb);
-        if ((tid & 63) == leader) atomicAdd(&cnt[lb], (int)__popcll(same));
-        todo &= ~same;
-      }
-    }
+    for (int u = 0; u < kTofBatch; ++u)
+      tof_hist_add(cnt, c0 + u * kTofThreads + tid < npx ? tof_bin(v[u], p.max_d, p.bins) : -1, tid & 63);
   }
   __syncthreads();
 
-  // 2. ambient floor
-  int hloc[kTofMaxBins / kTofThreads];
-#pragma unroll
-  for (int k = 0; k < kTofMaxBins / kTofThreads; ++k) {
-    const int i = tid + k * kTofThreads;
-    hloc[k] = (i < p.bins && i > 0) ? max(cnt[i] - p.floor_count, 0) : 0;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < kTofMaxBins / kTofThreads; ++k) {
-    const int i = tid + k * kTofThreads;
-    if (i < p.bins) cnt[i] = hloc[k];
-  }
-  __syncthreads();
-
-  // 3. every run start walks its run; key = (sum << 32) | ~start so the largest sum wins and, on ties, the lowest start
-#pragma unroll
-  for (int k = 0; k < kTofMaxBins / kTofThreads; ++k) {
-    const int i = tid + k * kTofThreads;
-    if (i < p.bins && hloc[k] > 0 && (i == 0 || cnt[i - 1] == 0)) {
-      unsigned long long s = 0;
-      for (int j = i; j < p.bins && cnt[j] > 0; ++j) s += (unsigned long long)cnt[j];
-      atomicMax(&best, (s << 32) | (unsigned long long)(0xffffffffu - (unsigned)i));
-    }
-  }
-  __syncthreads();
-  const unsigned long long key = best;
-  const int start = key ? (int)(0xffffffffu - (unsigned)(key & 0xffffffffull)) : p.bins;
-  int stop = start;
-  while (stop < p.bins && cnt[stop] > 0) ++stop;          // every thread: <= run length LDS reads
-
-  // 4. moments (one thread, ascending bins, float64)
+  // 2-3. ambient floor and the strongest run, 4. its moments (one thread): the sensor model of tof_cluster.h
+  const TofRun run = tof_cluster(cnt, &best, p.bins, p.floor_count, tid);
+  const int start = run.start, stop = run.stop;
   if (tid == 0) {
-    const long long n = (long long)(key >> 32);
-    const double nf = (double)((float)n + 1e-9f);           // the reference's `n + 1e-9` stays float32
-    double acc = 0.0;
-    for (int j = start; j < stop; ++j) {
-      const double c = ((double)(float)((double)(j + 1) * p.bin_width) + (double)j * p.bin_width) / 2.0;
-      acc += c * (double)cnt[j];
-    }
-    const double mu = acc / nf;
-    double var = 0.0;
-    for (int j = start; j < stop; ++j) {
-      const double c = ((double)(float)((double)(j + 1) * p.bin_width) + (double)j * p.bin_width) / 2.0;
-      const double d = c - mu;
-      var += (double)cnt[j] * (d * d);
-    }
-    const double sigma = sqrt(var / nf) + 1e-9;
+    double mu, sigma;
+    tof_moments(cnt, run, p.bin_width, mu, sigma);
     ms[0] = mu; ms[1] = sigma;
     const long long o = (long long)b * Z + z;
     p.fh[o * 2] = mu; p.fh[o * 2 + 1] = sigma;
-    p.mask[o] = n > 0 ? 1 : 0;
+    p.mask[o] = run.n > 0 ? 1 : 0;
     p.rect[o * 4 + 0] = (float)sy; p.rect[o * 4 + 1] = (float)sx;
     p.rect[o * 4 + 2] = (float)(sy + p.zone_px); p.rect[o * 4 + 3] = (float)(sx + p.zone_px);
   }
@@ -152,7 +96,7 @@ __global__ __launch_bounds__(kTofThreads) void tof_hist_kernel(TofP p) {
   const long long o = (long long)b * Z + z;
   if (tid < p.nsamp) {
     float v = 0.f;
-    if (key) {
+    if (run.n > 0) {
       v = tof_sample(ms[0], ms[1], p.w0[tid], p.w1 ? p.w1[tid] : 0.f, p.sample_mode);
     }
     p.pts[o * p.nsamp + tid] = v;

@@ -157,9 +157,13 @@ class EvalInputBuilder:
 
     `args.zone_type` (8x8 by default) = 6x6 / 4x4 / 2x2 keeps the central block of the simulated 8x8 grid, row-major, in `hist_data`,
     `rect_data` and `mask` (zjuL5.py:107-132); `patch_info` then comes from the kept rectangles.  The block is gathered on the
-    device from the full simulation, so it equals that simulation's entries bit for bit."""
+    device from the full simulation, so it equals that simulation's entries bit for bit.
+
+    `last_raw` holds the simulation's `fh` of the last batch, [B,Z,2] f64 (mu, sigma) gathered like the other three: the measurement
+    `metrics.zone_consistency` compares a prediction with.  It is not part of the returned dict."""
 
     def __init__(self, args, device="cuda:0"):
+        self.last_raw = None
         self.args = args
         self.device = torch.device(device)
         self.zone_type = str(getattr(args, "zone_type", "8x8") or "8x8")
@@ -191,7 +195,8 @@ class EvalInputBuilder:
         B, _, H, W = img.shape
         sim = self.sim.simulate(dep)
         if self._keep is not None:
-            sim = {k: sim[k].index_select(1, self._keep) for k in ("hist_data", "rect_data", "mask")}
+            sim = {k: sim[k].index_select(1, self._keep) for k in ("hist_data", "rect_data", "mask", "fh")}
+        self.last_raw = sim["fh"]                                # what a rig would measure: `metrics.zone_consistency`'s raw_data
         return {"rgb": img, "additional": {"hist_data": sim["hist_data"], "rect_data": sim["rect_data"], "mask": sim["mask"],
                                            "patch_info": self.patch_info(B, H, W)}}, dep
 

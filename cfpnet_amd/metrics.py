@@ -13,6 +13,9 @@ model (sparsification curves, AUSE, AURG; `cfp_unc_sparsification`, `csrc/unc_me
 
 `normal_metrics` / `RunningNormalAverage` rate the geometry: the angle between the surface normal of the prediction and that of the
 ground-truth depth, both formed as `pointcloud.unproject` forms them (`cfp_normal_metrics`, `csrc/normal_metrics.hip`).
+
+`zone_consistency` / `RunningZoneConsistency` need no ground truth: the ToF zones are re-simulated from the prediction with the sensor
+model of `tof.TofSimulator` and compared with the measured (mu, sigma) per zone (`cfp_tof_zone_consistency`, `csrc/zone_consistency.hip`).
 """
 from __future__ import annotations
 
@@ -21,7 +24,7 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
-from . import hip
+from . import hip, tof
 
 KEYS = ("a1", "a2", "a3", "abs_rel", "rmse", "log_10", "rmse_log", "silog", "sq_rel")   # the reference's dict order
 EVALUATE_ALL, VALIDATE = 0, 1
@@ -324,3 +327,83 @@ class RunningNormalAverage:
 
     def histogram(self):
         return [0] * NORMAL_BINS if self._hist is None else self._hist.cpu().tolist()
+
+
+ZONE_CONSISTENCY_NAMES = ("n_compared", "mae_mu", "rmse_mu", "rel_mu", "mae_sigma", "frac_1bin", "frac_window", "n_lost", "n_unmeasured",
+                          "n_measured")                # CFP_ZONE_* order
+ZONE_COLUMNS = ("mu_p", "sigma_p", "n_signal", "n_pix", "n_window", "state")
+ZONE_STATES = ("compared", "lost", "unmeasured", "neither")
+
+
+def zone_consistency(pred: torch.Tensor, raw_data: torch.Tensor, rect_data: torch.Tensor, mask: torch.Tensor, lo: float, hi: float,
+                     size=None, max_distance: float = 4.0, floor_count: int = tof.AMBIENT_FLOOR, dev_map: bool = False):
+    """The ToF zones re-simulated from the prediction against what the sensor measured (`cfp_tof_zone_consistency`, definition in
+    include/cfpnet_hip.h): the check that needs no ground truth.  pred [B,h,w] / [B,1,h,w] f32 on the device; raw_data [B,Z,2] the
+    measured (mu, sigma) per zone (a rig's `raw_data`, or the `fh` of `tof.TofSimulator.simulate`; converted to float64), rect_data
+    [B,Z,4] f32 (sy, sx, ey, ex) in pixels of the H x W grid and mask [B,Z] bool / uint8, all on the device; `size` = (H, W), twice the
+    prediction by default; `max_distance` the distance the measurement was made with (bins = int(max_distance / tof.BIN_WIDTH));
+    `floor_count` the ambient floor of the sensor model ->(summary [B,10] f64 in `ZONE_CONSISTENCY_NAMES` order, zone
+    [B,Z,6] f64 in `ZONE_COLUMNS` order), and with `dev_map` a third tensor [B,H,W] f32: the prediction minus the measured mu of the
+    first measured zone that contains the pixel, NaN outside.  No host synchronisation."""
+    from . import pointcloud
+    pred = pointcloud._pred3(pred)
+    for name, t, ok in (("raw_data", raw_data, (torch.float64, torch.float32)), ("rect_data", rect_data, (torch.float32,)),
+                        ("mask", mask, (torch.bool, torch.uint8))):
+        if not isinstance(t, torch.Tensor) or t.dtype not in ok or not t.is_cuda:
+            raise ValueError(f"{name} must be a {' / '.join(str(d).replace('torch.', '') for d in ok)} device tensor")
+    B, Hp, Wp = pred.shape
+    H, W = pointcloud._size(size, Hp, Wp)
+    if rect_data.dim() != 3 or rect_data.shape[0] != B or rect_data.shape[2] != 4 or rect_data.shape[1] < 1:
+        raise ValueError(f"rect_data must be [B,Z,4] with B = {B}, got {tuple(rect_data.shape)}")
+    Z = rect_data.shape[1]
+    if tuple(mask.shape) != (B, Z):
+        raise ValueError(f"mask must be [B,Z] = {(B, Z)}, got {tuple(mask.shape)}")
+    if tuple(raw_data.shape) != (B, Z, 2):
+        raise ValueError(f"raw_data must be [B,Z,2] = {(B, Z, 2)}, got {tuple(raw_data.shape)}")
+    if not float(lo) < float(hi):
+        raise ValueError(f"empty depth range [{lo}, {hi}]")
+    md = float(max_distance)
+    if not md > 0:
+        raise ValueError(f"max_distance must be positive, got {max_distance}")
+    bins = int(md / tof.BIN_WIDTH)
+    raw, rect, mk = raw_data.to(torch.float64).contiguous(), rect_data.contiguous(), mask.contiguous()
+    interp = int((Hp, Wp) != (H, W))                      # the rule of eval_metrics in EVALUATE_ALL order
+    summary = torch.empty(B, 10, dtype=torch.float64, device=pred.device)
+    zone = torch.empty(B, Z, 6, dtype=torch.float64, device=pred.device)
+    dmap = torch.empty(B, H, W, dtype=torch.float32, device=pred.device) if dev_map else None
+    hip.call("cfp_tof_zone_consistency", pred.data_ptr(), Hp, Wp, H, W, B, interp, float(lo), float(hi), rect.data_ptr(), mk.data_ptr(),
+             raw.data_ptr(), Z, md, bins, tof.BIN_WIDTH, int(floor_count), zone.data_ptr(), summary.data_ptr(), hip.ptr(dmap), hip.current_stream())
+    return (summary, zone, dmap) if dev_map else (summary, zone)
+
+
+class RunningZoneConsistency:
+    """Means of the zone-consistency summary over a data set: `update` takes the [B,10] rows of `zone_consistency` (and optionally the
+    [B,Z,6] zone tables) and keeps them on the device; `get_value` synchronises once and returns the plain means of the ten columns
+    over the images with n_compared > 0 (NaN entries, such as frac_window of an image without measured pixels, are left out of that
+    column's mean) plus "images", their number; `tables` is the list of per-image zone tables given, as nested lists."""
+
+    def __init__(self):
+        self._rows, self._zones = [], []
+
+    def update(self, rows: torch.Tensor, zone: Optional[torch.Tensor] = None) -> None:
+        if rows.dim() != 2 or rows.shape[1] != 10:
+            raise ValueError(f"rows must be [B,10], got {tuple(rows.shape)}")
+        self._rows.append(rows)
+        if zone is not None:
+            self._zones.append(zone)
+
+    def get_value(self) -> Dict[str, float]:
+        if not self._rows:
+            return {}
+        rows = [r for r in torch.cat(self._rows, 0).cpu().tolist() if r[0] > 0]      # the only host synchronisation
+        if not rows:
+            return {}
+        res = {}
+        for i, k in enumerate(ZONE_CONSISTENCY_NAMES):
+            v = [r[i] for r in rows if r[i] == r[i]]
+            res[k] = sum(v) / len(v) if v else float("nan")
+        res["images"] = len(rows)
+        return res
+
+    def tables(self):
+        return [t for z in self._zones for t in z.cpu().tolist()]

@@ -42,6 +42,14 @@ median_deg, rmse_deg and the shares below 11.25 / 22.5 / 30 degrees over the ima
 of those images; with `--save_dir D` given it writes `D/normals.json` with the names, the means and the 0.1-degree histogram summed over the
 images.  `--intrinsics` applies.  The other lines do not change.
 
+`--zone_consistency` asks whether the prediction agrees with what the sensor measured -- the check that needs no ground truth
+(`cfp_tof_zone_consistency`): the ToF zones are re-simulated from the prediction with the sensor model of the simulation and compared with
+the (mu, sigma) the model was fed from, per zone.  It prints one more line `ZoneConsistency: {...}` (after `Normals:` when that is present)
+with the means over the images with a compared zone, rounded to 4 decimals, and the number of those images; with `--save_dir D` given it
+writes `D/zone_consistency.json` with the names, the means and the zone table of every image.  It uses `--simu_max_distance`, the distance
+the measurement was made with: with `--random_simu_max_d` that distance is not known afterwards and the switch is an error.  The other lines
+do not change.
+
 `--save_pred`, `--save_gt`, `--save_rgb`, `--save_error_map` and `--save_for_demo` (the reference's picture switches) paint on the device
 (`cfpnet_amd/render.py`: `cfp_render_depth`, `cfp_render_zones`, `cfp_render_rgb`) and write, per evaluated image index i, into `--save_dir D`
 (default `tmp`): `D/pred_<i>.png` (colour) and `D/pred_<i>_mm.png` (16-bit millimetres of the clipped, enlarged prediction the metrics
@@ -113,6 +121,7 @@ def main(argv=None):
     points_normals = _pop(argv, "--points_normals", False, None)
     intrinsics = _pop(argv, "--intrinsics", None, _intrinsics)
     normal_metrics = _pop(argv, "--normal_metrics", False, None)
+    zone_consistency = _pop(argv, "--zone_consistency", False, None)
     if not save_points and (points_stride is not None or points_max_std is not None or points_normals or
                             (intrinsics is not None and not normal_metrics)):
         raise ValueError("--points_stride, --points_max_std, --points_normals and --intrinsics need --save_points"
@@ -139,6 +148,8 @@ def main(argv=None):
     area = metrics.REGIONS.index("fov_in") if area_in else metrics.REGIONS.index("fov_out") if area_out else None
     if range_edges and not want_regions:
         raise ValueError("--range_edges needs --region_metrics")
+    if zone_consistency and getattr(args, "random_simu_max_d", False):
+        raise ValueError("--zone_consistency re-simulates the zones with the distance the measurement was made with: not with --random_simu_max_d")
     geometry.central_zone_block(str(getattr(args, "zone_type", "8x8")))      # an unknown --zone_type is an error before anything is built
     device = torch.device("cuda:0")
     if n_syn > 0:
@@ -166,6 +177,7 @@ def main(argv=None):
     spars = metrics.RunningSparsification() if unc_metrics else None
     regions = metrics.RunningRegionAverage(range_edges) if want_regions else None
     normals_avg = metrics.RunningNormalAverage() if normal_metrics else None
+    zones_avg = metrics.RunningZoneConsistency() if zone_consistency else None
     if save_points:
         from cfpnet_amd import pointcloud
         os.makedirs(args.save_dir, exist_ok=True)
@@ -204,6 +216,11 @@ def main(argv=None):
                 avg.update(metrics.eval_metrics(pred, gt, float(args.min_depth), float(args.max_depth), mode=metrics.EVALUATE_ALL))
             if normal_metrics:
                 normals_avg.update(*metrics.normal_metrics(pred, gt, float(args.min_depth), float(args.max_depth), intrinsics, hist=True))
+            if zone_consistency:
+                add = inp["additional"]
+                zones_avg.update(*metrics.zone_consistency(pred, build.last_raw, add["rect_data"], add["mask"], float(args.min_depth),
+                                                           float(args.max_depth), size=gt.shape[-2:],
+                                                           max_distance=float(args.simu_max_distance)))
             if save_points:
                 pc = pointcloud.point_cloud(pred, intrinsics or pointcloud.ZJUL5_INTRINSICS, size=gt.shape[-2:], lo=float(args.min_depth),
                                             hi=float(args.max_depth), depth_range=(float(args.min_depth), float(args.max_depth)),
@@ -268,6 +285,16 @@ def main(argv=None):
             with open(os.path.join(args.save_dir, "normals.json"), "w") as f:
                 json.dump({"metrics": list(metrics.NORMAL_METRIC_NAMES), "means": [nv.get(k) for k in metrics.NORMAL_METRIC_NAMES],
                            "images": nv.get("images", 0), "bin_deg": 0.1, "histogram": normals_avg.histogram()}, f)
+    if zone_consistency:
+        zv = zones_avg.get_value()
+        print(f"ZoneConsistency: { {k: (v if k == 'images' else round(v, 4)) for k, v in zv.items()} }")
+        if save_spars:
+            import json
+            os.makedirs(args.save_dir, exist_ok=True)
+            with open(os.path.join(args.save_dir, "zone_consistency.json"), "w") as f:
+                json.dump({"metrics": list(metrics.ZONE_CONSISTENCY_NAMES), "means": [zv.get(k) for k in metrics.ZONE_CONSISTENCY_NAMES],
+                           "images": zv.get("images", 0), "max_distance": float(args.simu_max_distance),
+                           "zone_columns": list(metrics.ZONE_COLUMNS), "zones": zones_avg.tables()}, f)
     if save_points:
         print(f"points: {n_points / max(n_img, 1):.1f} kept per image on average, written to {args.save_dir}/points_<index>.ply", file=sys.stderr)
     if pics:

@@ -755,6 +755,53 @@ int cfp_normal_metrics(const float* pred, int Hp, int Wp, const float* gt, int H
                        const float* K /* device, [B][4]: fx fy cx cy */, void* ws, size_t ws_bytes, double* out /* [B][7] */,
                        int* hist /* [B][1800] or NULL */, float* angle_map /* [B][H][W] or NULL */, cfp_stream_t stream);
 
+/* Zone consistency: the ToF zones re-simulated from the PREDICTION and compared with what the sensor measured, per image, without leaving
+ * the device -- the quality number that needs no ground truth.  On a rig the measurement is the sensor itself: per zone a rectangle, a
+ * validity bit and the (mu, sigma) of its strongest return (the reference's `raw_data`, src/dataloader/zjuL5.py:106,148).  A ground-truth
+ * map is perfectly consistent with its own cfp_tof_hist_sim: fed back with that call's rect, mask and fh it gives mu_p, sigma_p equal to
+ * fh bit for bit and errors of exactly 0.
+ *   Inputs  pred [B,Hp,Wp] f32; H, W, interpolate, lo < hi as cfp_eval_metrics in mode 0; rect [B,Z,4] f32 (sy, sx, ey, ex), mask [B,Z]
+ *           u8 and raw [B,Z,2] f64 (the measured mu_m, sigma_m), read per image; max_distance, bins, bin_width, floor_count as
+ *           cfp_tof_hist_sim, with the distance the measurement was made with.  All pointers are device pointers.
+ *   Depth   d(y, x) is the float32 value cfp_eval_metrics evaluates at that pixel in mode 0: clip to [lo, hi] at model resolution, then
+ *           the align-corners bilinear blend; interpolate = 0 requires equal sizes.  One implementation (csrc/metrics_pred.h): bit for bit.
+ *   Zone    pixel (y, x) of the H x W grid belongs to zone z iff sy <= (float)y < ey && sx <= (float)x < ex, compared in float: the
+ *           membership rule of cfp_eval_metrics_regions.  Rectangles may be non-square, of any size, overlapping (a pixel then counts in
+ *           each) and partly or wholly off the image: only in-image pixels count.  An empty rectangle or a NaN coordinate gives an empty zone.
+ *   Sensor  the model of cfp_tof_hist_sim applied to the zone's d, one implementation (csrc/tof_cluster.h): float32 histogram with
+ *           bin = (int)(((d - 0.f) * (float)bins) / (max_distance - 0.f)), d == max_distance folded into the last bin, values outside
+ *           [0, max_distance] and NaN ignored; bin 0 cleared and floor_count subtracted, clamped at 0; the strongest run of consecutive
+ *           non-zero bins kept, lowest start winning ties; n, mu, sigma in float64 over the bin centres
+ *           ((double)(float)((j+1)*bin_width) + j*bin_width)/2 in ascending bin order with the divisor (double)((float)n + 1e-9f) and
+ *           sigma = sqrt(var/nf) + 1e-9.  No return (n = 0) gives mu = 0 and sigma = 1e-9.
+ *   Window  in float64 from the measured inputs: w = 3*sigma_m if 3*sigma_m > bin_width else bin_width (so a NaN sigma_m gives bin_width);
+ *           a pixel is inside iff mu_m - w <= (double)d <= mu_m + w.
+ *   zone [B][Z][6] f64 = {mu_p, sigma_p, n_signal, n_pix, n_window, state}: mu_p, sigma_p and n_signal = n of the sensor model; n_pix the
+ *           in-image pixels of the rectangle; n_window the ones inside the window, 0 when mask == 0; state
+ *             0 compared     mask != 0 and n_signal > 0
+ *             1 lost         mask != 0 and the prediction has no return
+ *             2 unmeasured   mask == 0 and the prediction has a return (not an error: a dropped zone looks like this)
+ *             3 neither
+ *   summary [B][10] f64 = {n_compared, mae_mu, rmse_mu, rel_mu, mae_sigma, frac_1bin, frac_window, n_lost, n_unmeasured, n_measured}
+ *           (CFP_ZONE_*).  Over the set C of compared zones: mae_mu = mean |mu_p - mu_m|, rmse_mu = sqrt(mean (mu_p - mu_m)^2),
+ *           rel_mu = mean |mu_p - mu_m| / mu_m, mae_sigma = mean |sigma_p - sigma_m|, frac_1bin = the share with |mu_p - mu_m| <= bin_width;
+ *           the five are NaN when n_compared == 0.  frac_window = sum n_window / sum n_pix over the zones with mask != 0, NaN if that
+ *           pixel sum is 0.  n_lost, n_unmeasured count states 1 and 2; n_measured the zones with mask != 0.
+ *   dev_map [B][H][W] f32 or NULL (skipped): d - (float)mu_m of the lowest-index zone with mask != 0 that contains the pixel, NaN where
+ *           there is none.  zone and summary are bit-identical with and without it.
+ * Three launches on `stream` -- one workgroup per (image, zone), one per image over the zone table in a fixed summation order, one lane per
+ * pixel for the map -- with no workspace, no host synchronisation, no global atomics and no floating-point atomics (integer LDS atomics
+ * only): two calls on the same tensors give identical bits.  CFP_ESHAPE for B*Z >= 2^31 or an image of 2^31 pixels or more. */
+enum { CFP_ZONE_N_COMPARED = 0, CFP_ZONE_MAE_MU, CFP_ZONE_RMSE_MU, CFP_ZONE_REL_MU, CFP_ZONE_MAE_SIGMA, CFP_ZONE_FRAC_1BIN,
+       CFP_ZONE_FRAC_WINDOW, CFP_ZONE_N_LOST, CFP_ZONE_N_UNMEASURED, CFP_ZONE_N_MEASURED };
+enum { CFP_ZONE_COMPARED = 0, CFP_ZONE_LOST, CFP_ZONE_UNMEASURED, CFP_ZONE_NEITHER };
+int cfp_tof_zone_consistency(const float* pred, int Hp, int Wp, int H, int W, int B, int interpolate, float lo, float hi,
+                             const float* rect /* [B][Z][4] sy sx ey ex */, const unsigned char* mask /* [B][Z] */,
+                             const double* raw /* [B][Z][2] measured mu, sigma */, int Z,
+                             float max_distance, int bins, double bin_width, int floor_count,
+                             double* zone /* [B][Z][6] */, double* summary /* [B][10] */,
+                             float* dev_map /* [B][H][W] or NULL */, cfp_stream_t stream);
+
 /* Pictures on the device: what the reference's `colorize` (src/utils/utils.py:44-64) paints on the host after moving the prediction
  * there, defined on the value the metrics evaluate.  Three entry points, one launch each; no workspace, no atomics, no host
  * synchronisation, capturable in a graph.  Every float32 operation below is rounded once (no fused multiply-add).
