@@ -164,6 +164,7 @@ class EvalInputBuilder:
 
     def __init__(self, args, device="cuda:0"):
         self.last_raw = None
+        self.last_counts = None
         self.args = args
         self.device = torch.device(device)
         self.zone_type = str(getattr(args, "zone_type", "8x8") or "8x8")
@@ -188,7 +189,10 @@ class EvalInputBuilder:
             self._pinfo[key] = info
         return self._pinfo[key]
 
-    def __call__(self, image: torch.Tensor, depth: torch.Tensor) -> Dict:
+    def __call__(self, image: torch.Tensor, depth: torch.Tensor, degrade: Optional[Dict] = None) -> Dict:
+        """`degrade` = dict(drop=, sigma=, prob=, mean=, seed=, step=) (every key optional, 0 by default) puts the kept zones through
+        `TofSimulator.degrade` before the model sees them: the robustness protocol of `evaluate_all.py --robust_*`.  `last_counts` then
+        holds that call's [B,3] counts (None otherwise); `last_raw` stays the undegraded measurement."""
         dev = self.device
         img = image.to(dev, non_blocking=True)
         dep = depth.to(dev, dtype=torch.float32, non_blocking=True)
@@ -197,6 +201,15 @@ class EvalInputBuilder:
         if self._keep is not None:
             sim = {k: sim[k].index_select(1, self._keep) for k in ("hist_data", "rect_data", "mask", "fh")}
         self.last_raw = sim["fh"]                                # what a rig would measure: `metrics.zone_consistency`'s raw_data
+        self.last_counts = None
+        if degrade is not None:
+            unknown = set(degrade) - {"drop", "sigma", "prob", "mean", "seed", "step"}
+            if unknown:
+                raise ValueError(f"degrade: unknown keys {sorted(unknown)}")
+            sim = self.sim.degrade(sim, drop=float(degrade.get("drop", 0.0)),
+                                   noise=(float(degrade.get("prob", 0.0)), float(degrade.get("mean", 0.0)), float(degrade.get("sigma", 0.0))),
+                                   seed=int(degrade.get("seed", 0)), step=int(degrade.get("step", 0)))
+            self.last_counts = sim["counts"]
         return {"rgb": img, "additional": {"hist_data": sim["hist_data"], "rect_data": sim["rect_data"], "mask": sim["mask"],
                                            "patch_info": self.patch_info(B, H, W)}}, dep
 

@@ -87,6 +87,7 @@ SIGNATURES = {
     "cfp_grad_clip_factor": (_i, [_p, C.c_longlong, _f, _p, _sz, _p, _p]),
     "cfp_tof_hist_sim": (_i, [_p, C.c_longlong, _i, _i, _i, _i, _i, _i, _i, _p, _i, _f, _i, C.c_double, _i, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p]),
     "cfp_tof_sample_points": (_i, [_p, _p, _p, _p, C.c_longlong, _i, _i, _p, _p]),
+    "cfp_tof_degrade": (_i, [_p, _p, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, C.c_ulonglong, C.c_uint, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
     "cfp_eval_metrics_ws_bytes": (_sz, [_i]),
     "cfp_eval_metrics": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _i, _f, _f, _p, _sz, _p, _p]),
     "cfp_unc_sparsification_ws_bytes": (_sz, [_i, _i, _i, _i]),

@@ -5,6 +5,8 @@ Reference interface: `src/utils/dataloader.py` -- `get_hist_parallel(rgb, dep, c
 (`src/dataloader/nyu.py:154,179`).  Same names, argument meaning and return values here, but the arrays are device
 tensors and the work is the HIP kernel behind `cfp_tof_hist_sim` / `cfp_tof_sample_points` (`csrc/tof_sim.hip`).
 `TofSimulator.simulate` is the batched form (one launch for B depth maps) that a device-side input pipeline uses.
+`TofSimulator.degrade` is what the loader does to that measurement when training (`nyu.py:155-163`: random zone dropout, range noise),
+as one launch of `cfp_tof_degrade` (`csrc/tof_degrade.hip`) with counter-based draws and no host round trip.
 
 There is no CPU implementation in this package: without the HIP library the calls raise.
 """
@@ -125,6 +127,45 @@ class TofSimulator:
         hip.call("cfp_tof_sample_points", fh.data_ptr(), mk.data_ptr(), self.w0.data_ptr(), hip.ptr(self.w1), nz, self.nsamp,
                  self.sample_mode, pts.data_ptr(), hip.current_stream())
         return pts
+
+    def degrade(self, sim_out: Dict[str, torch.Tensor], drop: float = 0.0, noise: Tuple[float, float, float] = (0.0, 0.0, 0.0),
+                seed: int = 0, step: int = 0, out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+        """Random zone dropout and Gaussian range noise on what `simulate` returned, in one launch (`cfp_tof_degrade`; nyu.py:155-163 then
+        :179): `drop` of each image's valid zones, drawn with replacement, lose their validity; then every zone that is still valid gets,
+        with probability noise[0], mu += noise[1] + noise[2] * N(0, 1); then the samples of the result.  The draws are Philox4x32-10 of
+        (`seed`, `step`, image index): the same arguments give the same result, whatever the batch size.
+
+        -> dict(mask [B,Z] bool, hist_data [B,Z,S] f32, fh [B,Z,2] f64, counts [B,3] i32 = valid before / distinct zones dropped / zones
+        noised), plus `rect_data` (and `hist`) of `sim_out` passed through.  `sim_out` is left as it is.  Nothing is copied to the host
+        and nothing waits for the device."""
+        fh, mask = sim_out["fh"], sim_out["mask"]
+        if not (torch.is_tensor(fh) and fh.is_cuda and fh.dtype == torch.float64 and fh.dim() == 3 and fh.shape[2] == 2):
+            raise ValueError("fh must be a float64 device tensor [B,Z,2]")
+        if not (torch.is_tensor(mask) and mask.is_cuda and mask.dtype == torch.bool and tuple(mask.shape) == tuple(fh.shape[:2])):
+            raise ValueError("mask must be a bool device tensor [B,Z] matching fh")
+        if fh.device != self.w0.device or mask.device != fh.device:
+            raise ValueError("fh and mask must be on the simulator's device")
+        prob, mean, sigma = (float(v) for v in noise)
+        fh, mask = fh.contiguous(), mask.contiguous()
+        B, Z = mask.shape
+        dev = fh.device
+        if out is None:
+            out = {"mask": torch.empty(B, Z, dtype=torch.bool, device=dev), "hist_data": torch.empty(B, Z, self.nsamp, dtype=torch.float32, device=dev),
+                   "fh": torch.empty(B, Z, 2, dtype=torch.float64, device=dev), "counts": torch.empty(B, 3, dtype=torch.int32, device=dev)}
+        else:
+            want = {"mask": (torch.bool, (B, Z)), "hist_data": (torch.float32, (B, Z, self.nsamp)), "fh": (torch.float64, (B, Z, 2)),
+                    "counts": (torch.int32, (B, 3))}
+            for k, (dt, shape) in want.items():
+                t = out.get(k)
+                if not (torch.is_tensor(t) and t.device == dev and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()):
+                    raise ValueError(f"out['{k}'] must be a contiguous {dt} tensor {list(shape)} on {dev}")
+        hip.call("cfp_tof_degrade", fh.data_ptr(), mask.data_ptr(), B, Z, float(drop), prob, mean, sigma, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                 int(step) & 0xFFFFFFFF, self.w0.data_ptr(), hip.ptr(self.w1), self.nsamp, self.sample_mode, out["mask"].data_ptr(),
+                 out["fh"].data_ptr(), out["hist_data"].data_ptr(), out["counts"].data_ptr(), hip.current_stream())
+        for k in ("rect_data", "hist"):
+            if k in sim_out:
+                out[k] = sim_out[k]
+        return out
 
 
 _sims: Dict[Tuple, TofSimulator] = {}

@@ -50,6 +50,14 @@ writes `D/zone_consistency.json` with the names, the means and the zone table of
 the measurement was made with: with `--random_simu_max_d` that distance is not known afterwards and the switch is an error.  The other lines
 do not change.
 
+`--robust_drop a,b,...` and `--robust_sigma a,b,...` build a robustness table: for each listed value the same images go through the model
+once more with that one degradation of the ToF input applied on the device (`cfp_tof_degrade`) -- a fraction of every image's
+valid zones dropped at random (with replacement, like `--drop_hist` in training), or Gaussian noise of that standard deviation in metres
+added to the mu of every valid zone.  The draws are keyed by `--robust_seed` (117010053 by default) and the index of the batch.  One more
+line, `Robustness: {"drop": {"0.25": {...}}, "sigma": {...}}` (JSON; the nine metrics rounded to 3 decimals), is printed last on stdout, and
+`<save_dir>/robustness.json` holds the same with the mean counts per image of valid zones, zones dropped and zones noised.  A listed value of
+0 reproduces the `Metrics:` line.  The other lines do not change.
+
 `--save_pred`, `--save_gt`, `--save_rgb`, `--save_error_map` and `--save_for_demo` (the reference's picture switches) paint on the device
 (`cfpnet_amd/render.py`: `cfp_render_depth`, `cfp_render_zones`, `cfp_render_rgb`) and write, per evaluated image index i, into `--save_dir D`
 (default `tmp`): `D/pred_<i>.png` (colour) and `D/pred_<i>_mm.png` (16-bit millimetres of the clipped, enlarged prediction the metrics
@@ -99,6 +107,14 @@ def _vis_range(v):
     return r
 
 
+def _robust_values(v):
+    r = tuple(float(x) for x in v.split(",") if x.strip())
+    if not r or any(not x >= 0.0 for x in r) or len({f"{x:g}" for x in r}) != len(r):
+        raise ValueError(f"--robust_drop / --robust_sigma take distinct non-negative values a,b,..., got '{v}'")
+    return r
+
+
+ROBUST_SEED = 117010053        # default of --robust_seed: the number the reference seeds everything with (train.py:218)
 PICTURE_SWITCHES = ("save_pred", "save_gt", "save_rgb", "save_error_map", "save_for_demo")
 
 
@@ -122,6 +138,13 @@ def main(argv=None):
     intrinsics = _pop(argv, "--intrinsics", None, _intrinsics)
     normal_metrics = _pop(argv, "--normal_metrics", False, None)
     zone_consistency = _pop(argv, "--zone_consistency", False, None)
+    robust = {"drop": _pop(argv, "--robust_drop", (), _robust_values), "sigma": _pop(argv, "--robust_sigma", (), _robust_values)}
+    robust_seed = _pop(argv, "--robust_seed", None, int)
+    if robust_seed is not None and not (robust["drop"] or robust["sigma"]):
+        raise ValueError("--robust_seed needs --robust_drop or --robust_sigma")
+    if any(not 0.0 <= v <= 1.0 for v in robust["drop"]):
+        raise ValueError("--robust_drop takes fractions in [0, 1]")
+    robust_seed = ROBUST_SEED if robust_seed is None else robust_seed
     if not save_points and (points_stride is not None or points_max_std is not None or points_normals or
                             (intrinsics is not None and not normal_metrics)):
         raise ValueError("--points_stride, --points_max_std, --points_normals and --intrinsics need --save_points"
@@ -189,6 +212,9 @@ def main(argv=None):
         vmin, vmax = vis_range or (float(args.min_depth), float(args.max_depth))
         n_pics = 0
     want_std = save_points and points_max_std is not None
+    robust_runs = [(kind, v, metrics.RunningAverageDict()) for kind in ("drop", "sigma") for v in robust[kind]]
+    robust_counts = {(kind, v): torch.zeros(3, dtype=torch.int64, device=device) for kind, v, _ in robust_runs}
+    n_batch = 0
     n_img, t0 = 0, time.perf_counter()
     with torch.no_grad():
         for img, dep, names in data.batches(samples, bs):
@@ -250,7 +276,20 @@ def main(argv=None):
                     for b, a in enumerate(t.cpu().numpy()):
                         render.write_png(os.path.join(args.save_dir, pattern.format(n_img + b)), a)
                         n_pics += 1
+            for kind, value, r_avg in robust_runs:           # the same images again, one degradation each; step = index of the batch
+                deg = dict(drop=value, seed=robust_seed, step=n_batch) if kind == "drop" else \
+                    dict(sigma=value, prob=1.0, mean=0.0, seed=robust_seed, step=n_batch)
+                r_inp, _ = build(img, dep, degrade=deg)
+                _, r_pred, _, _ = model(r_inp)
+                if area is not None:
+                    r_add = r_inp["additional"]
+                    r_avg.update(metrics.region_metrics(r_pred, gt, float(args.min_depth), float(args.max_depth), r_add["rect_data"], r_add["mask"],
+                                                        range_edges, mode=metrics.EVALUATE_ALL)[:, area, 0])
+                else:
+                    r_avg.update(metrics.eval_metrics(r_pred, gt, float(args.min_depth), float(args.max_depth), mode=metrics.EVALUATE_ALL))
+                robust_counts[kind, value] = robust_counts[kind, value] + build.last_counts.sum(0)
             n_img += img.shape[0]
+            n_batch += 1
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     res = {k: round(v, 3) for k, v in avg.get_value().items()}
@@ -295,6 +334,17 @@ def main(argv=None):
                 json.dump({"metrics": list(metrics.ZONE_CONSISTENCY_NAMES), "means": [zv.get(k) for k in metrics.ZONE_CONSISTENCY_NAMES],
                            "images": zv.get("images", 0), "max_distance": float(args.simu_max_distance),
                            "zone_columns": list(metrics.ZONE_COLUMNS), "zones": zones_avg.tables()}, f)
+    if robust_runs:
+        import json
+        line = {"drop": {}, "sigma": {}}
+        full = {"seed": robust_seed, "images": n_img, "metrics": list(metrics.KEYS), "counts": ["valid", "dropped", "noised"], "drop": {}, "sigma": {}}
+        for kind, v, r_avg in robust_runs:
+            line[kind][f"{v:g}"] = {k: round(x, 3) for k, x in r_avg.get_value().items()}
+            full[kind][f"{v:g}"] = {"metrics": line[kind][f"{v:g}"], "counts": [c / max(n_img, 1) for c in robust_counts[kind, v].cpu().tolist()]}
+        print("Robustness: " + json.dumps(line))
+        os.makedirs(args.save_dir, exist_ok=True)
+        with open(os.path.join(args.save_dir, "robustness.json"), "w") as f:
+            json.dump(full, f)
     if save_points:
         print(f"points: {n_points / max(n_img, 1):.1f} kept per image on average, written to {args.save_dir}/points_<index>.ply", file=sys.stderr)
     if pics:

@@ -603,6 +603,31 @@ int cfp_tof_hist_sim(const float* depth, long long img_stride, int B, int H, int
  * and may be NULL.  pts is 0 where !mask[z]. */
 int cfp_tof_sample_points(const double* fh, const unsigned char* mask, const float* w0, const float* w1, long long nzones,
                           int nsamp, int sample_mode, float* pts, cfp_stream_t stream);
+/* ToF degradation between cfp_tof_hist_sim and the model: random zone dropout (src/dataloader/nyu.py:155-158) and Gaussian range
+ * noise (what nyu.py:159-163 intended; the reference adds it to a copy), then the samples of the result.  One launch per batch, one
+ * workgroup per image, nothing returns to the host.
+ *   fh [B,Z,2] f64 (mu, sigma) and mask [B,Z] u8 as cfp_tof_hist_sim writes them; w0, w1, nsamp, sample_mode as
+ *   cfp_tof_sample_points takes them.  All pointers are device pointers.
+ *   Random numbers  Philox4x32-10 with key (seed & 0xffffffff, seed >> 32) and counter (i, b, step, stream): b the image, stream 0
+ *            the dropout with i the draw index, stream 1 the noise with i the zone index.  An image's result depends on (seed, step,
+ *            b) and its own inputs only, not on B or on the launch geometry.
+ *   Dropout  V = the valid zones of image b in ascending order, n = |V|, k = (int)(n * drop) with the product in f64.  For j < k
+ *            zone V[(word0(j) * n) >> 32] (64-bit product, word0 the first word of counter (j, b, step, 0)) loses its validity:
+ *            draws with replacement, as rng.choice(idx, k) of the reference, so duplicates are expected and at most k zones are
+ *            dropped.  The multiply-shift has a bias below n / 2^32.
+ *   Noise    after the dropout, on the zones that are still valid: with the words w of counter (z, b, step, 1) zone z is hit when
+ *            w0 * 2^-32 < noise_prob, and then mu += noise_mean + noise_sigma * sqrt(-2 ln((w1 + 1) * 2^-32)) * cos(2 pi * w2 * 2^-32)
+ *            (Box-Muller) in f64.  sigma is untouched and mu is not clamped.
+ *   Samples  pts[b, z, :] as cfp_tof_sample_points gives them for the resulting (mu, sigma); a zone that is not valid in mask_out
+ *            gets an all-zero row (dropout first, then sampling: nyu.py:155-158 before :179).
+ * Outputs: mask_out [B,Z] u8; fh_out [B,Z,2] f64 (may be NULL when noise_prob == 0); pts [B,Z,nsamp] f32; counts [B,3] i32 (may be
+ * NULL) = {valid before, distinct zones dropped, zones that received noise}.  With drop = 0 and noise_prob = 0 the outputs equal
+ * mask, fh and cfp_tof_sample_points(fh, mask) bit for bit.
+ * Limits: 1 <= Z <= 256 (16 x 16 is the largest grid in use), B * Z < 2^31, 0 <= drop <= 1, 0 <= noise_prob <= 1, noise_sigma >= 0;
+ * anything else is CFP_EINVAL / CFP_ESHAPE before any launch. */
+int cfp_tof_degrade(const double* fh, const unsigned char* mask, int B, int Z, double drop, double noise_prob, double noise_mean,
+                    double noise_sigma, unsigned long long seed, unsigned int step, const float* w0, const float* w1, int nsamp,
+                    int sample_mode, unsigned char* mask_out, double* fh_out, float* pts, int* counts, cfp_stream_t stream);
 
 /* Depth-evaluation metrics per image without leaving the device: compute_errors (src/utils/metrics.py:4-24 =
  * evaluate_all.py:15-35) fused with the protocol around it.

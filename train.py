@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Training with the reference's CLI and loop (`/root/reference/train.py:41-209`):
 
-    python train.py @configs/cfpnet_combine1.txt [--synthetic N] [--max_steps K] [--stop_after K] [--seed S] [--save weights/x.pt] [--dtype bf16|f16|f32|f32x3] [--eager] [--validate N] [--w_chamfer F]
+    python train.py @configs/cfpnet_combine1.txt [--synthetic N] [--max_steps K] [--stop_after K] [--seed S] [--save weights/x.pt] [--dtype bf16|f16|f32|f32x3] [--eager] [--validate N] [--w_chamfer F] [--tof_rng host|device]
                     [--resume checkpoints/x.pt] [--weight_path weights/x.pt] [--backend nccl|gloo] [--local_gpu I]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py @configs/cfpnet_combine1.txt --synthetic 4096
 
@@ -26,6 +26,12 @@ bf16 activations with float32 master parameters by default (`--dtype`); the step
 adaptive bin centres and the valid depths of each image (`cfp_bins_chamfer`): the `w_chamfer` term of the AdaBins recipe,
 on the `bin_edges` the training forward returns.  The logged `loss` stays the SILog value, `chamfer=` is printed next to it, and the
 weight is stored with the optimizer state: `--resume` with another weight is refused.
+
+`--tof_rng host|device` (not a reference flag; default host) says where the zone dropout of `--drop_hist` draws.  `host` is `drop_zones`
+below: the mask comes to the host, numpy draws, the mask goes back -- the one device-to-host wait of the loop.  `device` is one launch of
+`cfp_tof_degrade` (`TofSimulator.degrade`) with Philox draws keyed by (`--seed` or 4242) + rank and the global step, so nothing
+waits for the device and a resumed run repeats the uninterrupted one with no generator state to restore; the two modes draw different
+zones.  In `device` mode `--noise_prob`, `--noise_mean` and `--noise_sigma` take effect as nyu.py:159-163 intended.
 
 `--train_zone_random_offset K` jitters the ToF zone grid like dataloader.py:94-103: every step draws one offset per sample with
 `random.randint(-K, K)` (seeded by `--seed`), shifts that sample's grid by it in y and in x, simulates its histograms there and
@@ -190,6 +196,9 @@ def main(argv=None):
     log_every = _pop(argv, "--log_every", 10, int)
     n_val = _pop(argv, "--validate", 0, int)
     w_chamfer = _pop(argv, "--w_chamfer", 0.0, float)    # objective = SILog + F * bin-centre chamfer loss (not a reference flag: popped here)
+    tof_rng = _pop(argv, "--tof_rng", "host")            # where the zone dropout / range noise draw: numpy on the host, or `cfp_tof_degrade` (not a reference flag)
+    if tof_rng not in ("host", "device"):
+        raise ValueError(f"--tof_rng takes host or device, got '{tof_rng}'")
     dtype = TRAIN_DTYPES[_pop(argv, "--dtype", "bf16")]
     backend = _pop(argv, "--backend", "nccl")        # "gloo": ranks may share one GPU (tests), buckets staged through the host
     local_gpu = _pop(argv, "--local_gpu", None, int)
@@ -212,8 +221,15 @@ def main(argv=None):
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
     zone_offset = int(getattr(args, "train_zone_random_offset", 0) or 0)
-    if float(getattr(args, "noise_prob", 0.0) or 0.0) > 1e-3 and rank == 0:
-        print("note: --noise_prob has no effect in the reference either (nyu.py:159-163 adds the noise to a copy); nothing is added here", flush=True)
+    noise = tuple(float(getattr(args, k, 0.0) or 0.0) for k in ("noise_prob", "noise_mean", "noise_sigma"))
+    if noise[0] > 1e-3 and rank == 0:
+        if tof_rng == "device":
+            print("note: --tof_rng device applies --noise_prob / --noise_mean / --noise_sigma to mu as nyu.py:159-163 intended (the reference adds the noise to a copy)", flush=True)
+        else:
+            print("note: --noise_prob has no effect in the reference either (nyu.py:159-163 adds the noise to a copy); nothing is added here", flush=True)
+    if noise[0] <= 1e-3:                                 # nyu.py:159: the reference's threshold
+        noise = (0.0, 0.0, 0.0)
+    tof_seed = (seed if seed is not None else 4242) + rank       # --tof_rng device: with the global step, all the state its draws have
 
     H, W = int(args.input_height), int(args.input_width)
     per_rank = max(1, int(args.bs) // world)
@@ -358,7 +374,11 @@ def main(argv=None):
                 step_info = _torch_patch_info(geometry.offsets_patch_info(zoffs, (zn, zp), (H, W), zone_cache))
             s = sim.simulate(depd, offsets=torch.tensor(zoffs, dtype=torch.int32).to(dev) if zoffs is not None else None)
             mask, hist_data = s["mask"], s["hist_data"]
-            if drop > 1e-3:
+            if tof_rng == "device":                           # nyu.py:155-163 in one launch, no copy to the host; nothing to do launches nothing
+                if drop > 1e-3 or noise[0] > 0.0:
+                    d = sim.degrade(s, drop=drop if drop > 1e-3 else 0.0, noise=noise, seed=tof_seed, step=step)
+                    mask, hist_data = d["mask"], d["hist_data"]
+            elif drop > 1e-3:
                 mask, hist_data = drop_zones(sim, s, drop, rng)
             inp = {"rgb": img, "additional": {"hist_data": hist_data, "rect_data": s["rect_data"], "mask": mask, "patch_info": step_info}}
             if not eager and tr._graph is None:
