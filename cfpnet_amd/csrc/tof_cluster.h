@@ -27,6 +27,16 @@ __device__ __forceinline__ int tof_bin(float v, float max_d, int bins) {
   return bin;
 }
 
+// The pixels of a zone along one axis: the integers i of [0, n) with a <= (float)i < b are [lo, hi).  n <= 2^24, so (float)i is exact and
+// the float rule is a rule on ceil().  A NaN bound gives the empty range.  (The membership rule of the zone consistency and the zone loss.)
+__device__ __forceinline__ void zc_span(float a, float b, int n, int& lo, int& hi) {
+  lo = hi = 0;
+  if (a != a || b != b) return;
+  lo = !(a > 0.f) ? 0 : (a >= (float)n ? n : (int)ceilf(a));
+  hi = !(b > 0.f) ? 0 : (b >= (float)n ? n : (int)ceilf(b));
+  if (hi < lo) hi = lo;
+}
+
 // Every lane of the wave calls this with its pixel's bin (-1: nothing to add).  Lanes that hit the same bin are merged with a ballot so
 // a flat zone (every pixel in two or three bins) does not serialise 64-way on one LDS counter.
 __device__ __forceinline__ void tof_hist_add(int* cnt, int bin, int lane) {

@@ -37,16 +37,6 @@ struct ZoneP {
   double* zone; double* summary; float* dev_map;
 };
 
-// The integers i of [0, n) with a <= (float)i < b: [lo, hi).  n <= 2^24, so (float)i is exact and the float rule is a rule on ceil().
-// A NaN bound gives the empty range.
-__device__ __forceinline__ void zc_span(float a, float b, int n, int& lo, int& hi) {
-  lo = hi = 0;
-  if (a != a || b != b) return;
-  lo = !(a > 0.f) ? 0 : (a >= (float)n ? n : (int)ceilf(a));
-  hi = !(b > 0.f) ? 0 : (b >= (float)n ? n : (int)ceilf(b));
-  if (hi < lo) hi = lo;
-}
-
 __global__ __launch_bounds__(kTofThreads) void zone_consistency_kernel(ZoneP p) {
   __shared__ int cnt[kTofMaxBins];
   __shared__ unsigned long long best;

@@ -100,7 +100,9 @@ SIGNATURES = {
     "cfp_normal_metrics_ws_bytes": (_sz, [_i, _i, _i]),
     "cfp_normal_metrics": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _f, _f, _p, _p, _sz, _p, _p, _p, _p]),
     "cfp_tof_zone_consistency": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _p, _i, _f, _i, C.c_double, _i, _p, _p, _p, _p]),
-    "cfp_render_depth": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _f, _f, _i, _f, _f, _p, _p, _ll, _i, _p, _f, _p]),
+    "cfp_tof_zone_loss_ws_bytes": (_sz, [_i, _i, _i]),
+    "cfp_tof_zone_loss": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _p, _i, _f, _i, C.c_double, _i, C.c_double, _f, _i, _p, _sz, _p, _p, _p, _p]),
+    "cfp_render_depth":(_i, [_p, _i, _i, _p, _i, _i, _i, _i, _f, _f, _i, _f, _f, _p, _p, _ll, _i, _p, _f, _p]),
     "cfp_render_zones": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _p, _i, _p, _ll, _i, _p]),
     "cfp_render_rgb": (_i, [_p, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _i, _i, _p, _ll, _i, _p]),
     "cfp_conv2d_wgrad_ws_bytes": (_sz, [_i, _i, _i]),

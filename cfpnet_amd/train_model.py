@@ -88,6 +88,8 @@ class TrainNet:
         self.centers, self.widths = None, None            # the last forward's bin centres and normalised widths (tape values)
         self._chamfer = train_ops.BinsChamferLoss()       # keeps its workspace between steps
         self.last_chamfer: Optional[torch.Tensor] = None  # device scalar of the last forward_backward(w_chamfer > 0)
+        self._zone = train_ops.ZoneLoss()                 # keeps its workspace and outputs between steps
+        self.last_zone: Optional[torch.Tensor] = None     # device scalar of the last forward_backward(w_zone > 0)
         self.flipped: Dict[str, torch.Tensor] = {}        # bound mode: name -> flipped conv weight, refreshed by the trainer every step
         self.packed: Dict[str, torch.Tensor] = {}         # bound f16x3 mode: name -> pre-split forward operand, refreshed every step
         self.packed_t: Dict[str, torch.Tensor] = {}       # ... and the pre-split operand of the data gradient (flipped / transposed weights)
@@ -530,7 +532,8 @@ class TrainNet:
 
     def forward_backward(self, input_data: dict, target: torch.Tensor, loss_mask: Optional[torch.Tensor] = None, pos_offsets: Optional[dict] = None,
                          stop_before_encoder: bool = False, loss_sync=None, stop: Optional[str] = None, defer_param_grads: bool = False,
-                         zone_records: Optional[dict] = None, w_chamfer: float = 0.0):
+                         zone_records: Optional[dict] = None, w_chamfer: float = 0.0, w_zone: float = 0.0, zone_target: Optional[dict] = None,
+                         silog: bool = True):
         """One forward in training mode + SILog + backward.  Returns (loss as a device scalar, pred [B,1,H/2,W/2], edges);
         gradients are in `self.grads()`, running statistics in `self.buf`.  `stop_before_encoder`: the backward stops where the
         RGB encoder's begins (every non-encoder parameter gradient is final) and `finish_backward()` runs the rest.
@@ -539,20 +542,42 @@ class TrainNet:
         `defer_param_grads`: weight / bias gradient kernels are queued on the tape; `run_deferred_param_grads()` issues them.
         `w_chamfer` > 0: the objective is SILog + w_chamfer * bin-centre chamfer loss (train_ops.BinsChamferLoss on `edges`, the full
         resolution target and the same mask); its gradient enters the tape at the bin centres.  The returned loss stays the SILog
-        scalar, the chamfer value is the device scalar `self.last_chamfer` (None when the weight is 0: no launch is added)."""
+        scalar, the chamfer value is the device scalar `self.last_chamfer` (None when the weight is 0: no launch is added).
+        `w_zone` > 0: w_zone * zone-consistency loss is added to the objective (train_ops.ZoneLoss on `pred` clipped to [min_val, max_val],
+        on the target's grid): `zone_target` = dict(raw_data [B,Z,2], rect_data [B,Z,4], mask [B,Z], max_distance) is what the sensor
+        measured.  Its gradient is accumulated into the prediction's by the same call, `self.last_zone` is the device scalar (None when
+        the weight is 0: no launch is added).  A per-rank mean over images needs no world-size factor, as for the chamfer term.
+        `silog` False: SILog is not launched (a batch without valid ground truth makes it NaN); the objective is w_zone * L alone and
+        the returned loss is that scalar."""
+        if not silog and not w_zone > 0.0:
+            raise ValueError("silog=False leaves no objective: it needs w_zone > 0")
+        if w_zone > 0.0 and zone_target is None:
+            raise ValueError("w_zone > 0 needs zone_target = dict(raw_data, rect_data, mask, max_distance)")
         dev = self.dev
         t = self.new_tape(side=self.side_stream)
         t.defer = defer_param_grads
         pred, edges, (B, h0, w0) = self.forward(t, input_data, pos_offsets, zone_records)
         # SILog (loss.py:9-19) on the half-resolution prediction against the full-resolution target
-        crit = train_ops.SILogLoss()
         pred4 = pred.t.reshape(B, 1, h0, w0)
-        loss = crit.forward(pred4, target.to(dev, torch.float32), loss_mask.to(dev) if loss_mask is not None else None, interpolate=True)
-        gl = 1.0
-        if loss_sync is not None:
-            loss = crit.sync_moments(loss_sync[0])
-            gl = float(loss_sync[1])                                            # the gradient average over the ranks divides by it again
-        pred.g = crit.backward(gl).reshape(-1, 1).contiguous()
+        loss = None
+        if silog:
+            crit = train_ops.SILogLoss()
+            loss = crit.forward(pred4, target.to(dev, torch.float32), loss_mask.to(dev) if loss_mask is not None else None, interpolate=True)
+            gl = 1.0
+            if loss_sync is not None:
+                loss = crit.sync_moments(loss_sync[0])
+                gl = float(loss_sync[1])                                        # the gradient average over the ranks divides by it again
+            pred.g = crit.backward(gl).reshape(-1, 1).contiguous()
+        self.last_zone = None
+        if w_zone > 0.0:
+            zt = zone_target
+            self.last_zone = self._zone.forward(pred4, zt["raw_data"].to(dev), zt["rect_data"].to(dev, torch.float32), zt["mask"].to(dev),
+                                                self.min_val, self.max_val, size=tuple(target.shape[-2:]),
+                                                max_distance=float(zt.get("max_distance", 4.0)), grad_scale=float(w_zone),
+                                                grad_out=pred.g if silog else None)
+            if not silog:
+                pred.g = self._zone.grad_pred.reshape(-1, 1)
+                loss = self.last_zone * float(w_zone)
         self.last_chamfer = None
         if w_chamfer > 0.0:
             # a per-rank mean over images averaged over equal-sized ranks is already the global mean: no world-size factor under loss_sync

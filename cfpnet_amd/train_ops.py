@@ -13,7 +13,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import ctypes
 import torch
 
-from . import hip
+from . import hip, tof
 
 
 class SILogLoss:
@@ -156,6 +156,117 @@ def bins_chamfer(edges: torch.Tensor, target: torch.Tensor, mask: Optional[torch
     """The chamfer loss as a torch loss, differentiable w.r.t. `edges` (the first value `model.train()(x)` returns):
     `loss = silog(pred, ...) + 0.1 * bins_chamfer(bin_edges, depth, mask)`.  Value and gradient come from one cfp_bins_chamfer call."""
     return _BinsChamfer.apply(edges, target, mask)
+
+
+ZONE_LOSS_COLUMNS = ("m_z", "n_z", "r_z", "rho_z", "run_start", "run_stop", "state", "coef")     # `ZoneLoss.zone` [B,Z,8]
+
+
+class ZoneLoss:
+    """Zone-consistency loss (include/cfpnet_hip.h, cfp_tof_zone_loss; none in the reference): the ToF zones re-simulated from the
+    prediction with the sensor model of `metrics.zone_consistency`, their weighted mean depth against the measured mu through a dead zone
+    of half a bin and a Huber penalty -- the training signal that needs no ground truth.  Call with (pred [B,h,w] / [B,1,h,w] f32,
+    raw_data [B,Z,2] the measured (mu, sigma) (a rig's `raw_data` or `TofSimulator.simulate`'s `fh`; sigma is not used), rect_data
+    [B,Z,4] f32, mask [B,Z] bool / uint8, lo, hi), all on the device; `size` = (H, W) of the grid the rectangles are given on, twice the
+    prediction by default; `max_distance` the one distance the measurement was made with; `delta` the Huber threshold (None:
+    tof.BIN_WIDTH).  `forward` returns the device scalar L; `per_image` [B] holds the L_b, `zone` [B,Z,8] f64 the table in
+    `ZONE_LOSS_COLUMNS` order and `grad_pred` [B,h,w] `grad_scale` * dL/dpred.  With `grad_out` (a contiguous f32 tensor of B*h*w
+    elements) the gradient is ADDED to it instead and `grad_pred` is that tensor.  One call computes value and gradient; `backward`
+    rescales.  The workspace and the outputs are kept between calls of the same shape.  No host synchronisation."""
+
+    name = "ZoneLoss"
+
+    def __init__(self):
+        self._ws: Optional[torch.Tensor] = None
+        self._out: Optional[torch.Tensor] = None
+        self.zone: Optional[torch.Tensor] = None
+        self.grad_pred: Optional[torch.Tensor] = None
+        self._own_grad: Optional[torch.Tensor] = None
+        self._scale = 1.0
+
+    def forward(self, pred: torch.Tensor, raw_data: torch.Tensor, rect_data: torch.Tensor, mask: torch.Tensor, lo: float, hi: float,
+                size=None, max_distance: float = 4.0, floor_count: int = tof.AMBIENT_FLOOR, delta: Optional[float] = None,
+                grad_scale: float = 1.0, grad_out: Optional[torch.Tensor] = None):
+        if pred.dim() == 4 and pred.shape[1] == 1:
+            pred = pred[:, 0]
+        if pred.dim() != 3 or pred.dtype != torch.float32 or not pred.is_cuda:
+            raise ValueError("pred must be a float32 device tensor [B,h,w] or [B,1,h,w]")
+        pred = pred.contiguous()
+        for name, t, ok in (("raw_data", raw_data, (torch.float64, torch.float32)), ("rect_data", rect_data, (torch.float32,)),
+                            ("mask", mask, (torch.bool, torch.uint8))):
+            if not isinstance(t, torch.Tensor) or t.dtype not in ok or not t.is_cuda:
+                raise ValueError(f"{name} must be a {' / '.join(str(d).replace('torch.', '') for d in ok)} device tensor")
+        B, Hp, Wp = pred.shape
+        H, W = (2 * Hp, 2 * Wp) if size is None else (int(size[0]), int(size[1]))
+        if rect_data.dim() != 3 or rect_data.shape[0] != B or rect_data.shape[2] != 4 or rect_data.shape[1] < 1:
+            raise ValueError(f"rect_data must be [B,Z,4] with B = {B}, got {tuple(rect_data.shape)}")
+        Z = rect_data.shape[1]
+        if tuple(mask.shape) != (B, Z) or tuple(raw_data.shape) != (B, Z, 2):
+            raise ValueError(f"mask must be [B,Z] = {(B, Z)} and raw_data [B,Z,2], got {tuple(mask.shape)} and {tuple(raw_data.shape)}")
+        md = float(max_distance)
+        if not md > 0:
+            raise ValueError(f"max_distance must be positive, got {max_distance}")
+        bins = int(md / tof.BIN_WIDTH)
+        delta = tof.BIN_WIDTH if delta is None else float(delta)
+        raw, rect, mk = raw_data.to(torch.float64).contiguous(), rect_data.contiguous(), mask.contiguous()
+        dev = pred.device
+        need = max(int(hip.load().cfp_tof_zone_loss_ws_bytes(B, Z, bins)), 16)
+        if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        if self._out is None or self._out.numel() != 1 + B or self._out.device != dev:
+            self._out = torch.empty(1 + B, dtype=torch.float32, device=dev)
+        if self.zone is None or tuple(self.zone.shape) != (B, Z, 8) or self.zone.device != dev:
+            self.zone = torch.empty(B, Z, 8, dtype=torch.float64, device=dev)
+        if grad_out is not None:
+            if grad_out.dtype != torch.float32 or grad_out.numel() != B * Hp * Wp or not grad_out.is_contiguous() or grad_out.device != dev:
+                raise ValueError("grad_out must be a contiguous float32 device tensor with one element per pixel of pred")
+            grad, acc = grad_out, 1
+        else:
+            if self._own_grad is None or tuple(self._own_grad.shape) != (B, Hp, Wp) or self._own_grad.device != dev:
+                self._own_grad = torch.empty(B, Hp, Wp, dtype=torch.float32, device=dev)
+            grad, acc = self._own_grad, 0
+        self.grad_pred, self._scale = grad, float(grad_scale)
+        hip.call("cfp_tof_zone_loss", pred.data_ptr(), Hp, Wp, H, W, B, int((Hp, Wp) != (H, W)), float(lo), float(hi), rect.data_ptr(),
+                 mk.data_ptr(), raw.data_ptr(), Z, md, bins, tof.BIN_WIDTH, int(floor_count), delta, self._scale, acc, self._ws.data_ptr(),
+                 self._ws.numel(), self.zone.data_ptr(), self._out.data_ptr(), hip.ptr(grad), hip.current_stream())
+        return self._out[0]
+
+    __call__ = forward
+
+    @property
+    def per_image(self) -> torch.Tensor:
+        return self._out[1:]
+
+    def backward(self, grad_loss: float = 1.0) -> torch.Tensor:
+        if self.grad_pred is None or self.grad_pred is not self._own_grad:
+            raise RuntimeError("ZoneLoss.backward rescales the gradient of a forward that wrote its own grad_pred (no grad_out)")
+        if float(grad_loss) == self._scale:
+            return self.grad_pred
+        if self._scale == 0.0:
+            raise RuntimeError("ZoneLoss.forward ran with grad_scale 0: there is no gradient to rescale")
+        return self.grad_pred * (float(grad_loss) / self._scale)
+
+
+class _ZoneLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, raw_data, rect_data, mask, lo, hi, size, max_distance, floor_count, delta):
+        crit = ZoneLoss()
+        loss = crit.forward(pred.detach().float(), raw_data, rect_data, mask, lo, hi, size=size, max_distance=max_distance,
+                            floor_count=floor_count, delta=delta)
+        ctx.save_for_backward(crit.grad_pred.reshape(pred.shape))
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        (gp,) = ctx.saved_tensors
+        return (gp * g,) + (None,) * 9
+
+
+def zone_loss(pred: torch.Tensor, raw_data: torch.Tensor, rect_data: torch.Tensor, mask: torch.Tensor, lo: float, hi: float, size=None,
+              max_distance: float = 4.0, floor_count: int = tof.AMBIENT_FLOOR, delta: Optional[float] = None) -> torch.Tensor:
+    """The zone-consistency loss as a torch loss, differentiable w.r.t. `pred` (the second value `model.train()(x)` returns):
+    `loss = silog(pred, ...) + w * zone_loss(pred, raw_data, rect_data, mask, 1e-3, 10.0)`.  Value and gradient come from one
+    cfp_tof_zone_loss call; the run and the weights of each zone are held constant in the gradient."""
+    return _ZoneLossFn.apply(pred, raw_data, rect_data, mask, lo, hi, size, max_distance, floor_count, delta)
 
 
 class OneCycle:

@@ -27,9 +27,15 @@ class Trainer:
                  device="cuda:0", dist=None, world: int = 1, n_bins: int = 256, min_val: float = 1e-3, max_val: float = 10.0,
                  change_embedding: bool = True, dtype=torch.float32, no_skip_inside: bool = False, norm: str = "linear", kernel_layout: bool = True,
                  base_resolution=spec.BASE_RESOLUTION, overlap_param_grads: bool = False, comm: str = "overlap", sync_loss: bool = False,
-                 zone_offset_bound: int = 0, zone_layout=None, w_chamfer: float = 0.0):
+                 zone_offset_bound: int = 0, zone_layout=None, w_chamfer: float = 0.0, w_zone: float = 0.0, zone_only: bool = False,
+                 zone_max_distance: float = 4.0):
         """`w_chamfer` F > 0: the objective of a step is SILog + F * bin-centre chamfer loss (TrainNet.forward_backward); `step` still
         returns the SILog scalar, `last_chamfer` is the chamfer value.  0 (default) adds no launch.
+        `w_zone` F > 0: F * zone-consistency loss is added (TrainNet.forward_backward, train_ops.ZoneLoss): the prediction must reproduce
+        the ToF measurement it was given.  The measurement is read from the batch: `input_data["additional"]["raw_data"]` [B,Z,2] (the
+        measured mu, sigma), `rect_data` and `zone_mask` (default: `mask`); `zone_max_distance` is the one distance it was made with.
+        `last_zone` is the value.  `zone_only`: SILog is not launched (scenes without dense ground truth), the objective is F * L alone
+        and `step` returns that scalar.  0 (default) adds no launch.
         `zone_offset_bound` k > 0: per-sample zone-grid offsets in [-k, k] (`--train_zone_random_offset`).  The batch's zone
         rectangle of each fusion scale is then a device record written by every `step` (TrainNet's dynamic-geometry form), so the
         captured step follows it; `zone_layout` = tof.zone_layout(...) (None: read from the first batch)."""
@@ -53,6 +59,14 @@ class Trainer:
         self.w_chamfer = float(w_chamfer)
         if not self.w_chamfer >= 0.0:
             raise ValueError(f"w_chamfer must be >= 0, got {w_chamfer!r}")
+        self.w_zone, self.zone_only, self.zone_max_distance = float(w_zone), bool(zone_only), float(zone_max_distance)
+        if not self.w_zone >= 0.0:
+            raise ValueError(f"w_zone must be >= 0, got {w_zone!r}")
+        if self.zone_only and not self.w_zone > 0.0:
+            raise ValueError("zone_only leaves no objective without w_zone > 0")
+        if self.zone_only and sync_loss:
+            raise ValueError("zone_only launches no SILog: there is nothing for sync_loss to synchronise")
+        self._szt = None                  # captured step: the static buffers of the zone target
         # sync_loss: the SILog loss over the GLOBAL batch (its three moments all-reduced), as the reference's nn.DataParallel loop
         # computes it; default is the per-rank loss of DistributedDataParallel-style training (SURVEY 8e documents the difference)
         self.sync_loss = bool(sync_loss) and dist is not None and world > 1
@@ -209,8 +223,26 @@ class Trainer:
         output tensor: read it before the next step."""
         return self.net.last_chamfer
 
+    @property
+    def last_zone(self) -> Optional[torch.Tensor]:
+        """The zone-consistency loss of the last step as a device scalar (None with w_zone == 0).  In a captured step it is the graph's
+        own output tensor: read it before the next step."""
+        return self.net.last_zone
+
     def _loss_sync(self):
         return (self.dist, self.world) if self.sync_loss else None
+
+    def _zone_kw(self, input_data: dict) -> dict:
+        """The zone term's arguments of TrainNet.forward_backward; empty with w_zone == 0, so that call is the one without them."""
+        if not self.w_zone > 0.0:
+            return {}
+        add = input_data["additional"]
+        if add.get("raw_data") is None or add.get("rect_data") is None:
+            raise ValueError("w_zone > 0 needs input_data['additional']['raw_data'] [B,Z,2] (the measured mu, sigma) and 'rect_data' [B,Z,4]")
+        zm = add.get("zone_mask")
+        target = {"raw_data": add["raw_data"], "rect_data": add["rect_data"], "mask": zm if zm is not None else add["mask"],
+                  "max_distance": self.zone_max_distance}
+        return {"w_zone": self.w_zone, "zone_target": target, "silog": not self.zone_only}
 
     def _grads_to_flat(self, input_data, target, offs, stop_before_encoder: bool = False, stop: Optional[str] = None, defer: bool = False):
         if self.kernel_layout and self._to_torch is None:
@@ -223,12 +255,13 @@ class Trainer:
                 self._refresh_weight_flips()
             loss, _, _ = self.net.forward_backward(input_data, target, target > self.min_val, pos_offsets=offs,
                                                    stop_before_encoder=stop_before_encoder, loss_sync=self._loss_sync(), stop=stop,
-                                                   defer_param_grads=defer, zone_records=self._zone_dev, w_chamfer=self.w_chamfer)
+                                                   defer_param_grads=defer, zone_records=self._zone_dev, w_chamfer=self.w_chamfer,
+                                                   **self._zone_kw(input_data))
             if self._flip_jobs is None:
                 self._plan_weight_flips()
             return loss                                             # every gradient is already at its flat address
         loss, pred, _ = self.net.forward_backward(input_data, target, target > self.min_val, pos_offsets=offs, loss_sync=self._loss_sync(),
-                                                  zone_records=self._zone_dev, w_chamfer=self.w_chamfer)
+                                                  zone_records=self._zone_dev, w_chamfer=self.w_chamfer, **self._zone_kw(input_data))
         self.flat.grad.zero_()
         for name, g in self.net.grads().items():
             self.flat.view(name, "grad").copy_(g)
@@ -271,6 +304,13 @@ class Trainer:
                                     "mask": add["mask"].to(dev).contiguous().clone(), "rect_data": add.get("rect_data"),
                                     "patch_info": add["patch_info"]}}
         self._starget = target.to(dev, torch.float32).contiguous().clone()
+        if self.w_zone > 0.0:
+            # what the sensor measured: static buffers that every `step` refreshes (the rectangles move with the zone offsets)
+            zk = self._zone_kw(input_data)["zone_target"]
+            self._szt = {"raw_data": zk["raw_data"].to(dev, torch.float64).contiguous().clone(),
+                         "rect_data": zk["rect_data"].to(dev, torch.float32).contiguous().clone(),
+                         "zone_mask": zk["mask"].to(dev).contiguous().clone()}
+            self._sin["additional"].update(self._szt)
         if self._szone is not None:
             self._write_zone(input_data)
         self._soffs = torch.zeros(3, 2, dtype=torch.int32, device=dev)
@@ -384,6 +424,11 @@ class Trainer:
             self._sin["additional"]["hist_data"].copy_(add["hist_data"], non_blocking=True)
             self._sin["additional"]["mask"].copy_(add["mask"], non_blocking=True)
             self._starget.copy_(target, non_blocking=True)
+            if self._szt is not None:
+                zk = self._zone_kw(input_data)["zone_target"]
+                self._szt["raw_data"].copy_(zk["raw_data"], non_blocking=True)
+                self._szt["rect_data"].copy_(zk["rect_data"], non_blocking=True)
+                self._szt["zone_mask"].copy_(zk["mask"], non_blocking=True)
             self._soffs.copy_(torch.tensor([offs[n] for n in ("cross_atten3", "cross_atten2", "cross_atten1")], dtype=torch.int32), non_blocking=True)
             loss = self._sloss
             if self._segments is not None:
@@ -437,7 +482,7 @@ class Trainer:
         if self.kernel_layout and self._to_torch is None:
             raise RuntimeError("optimizer state exists only after the first training step fixed the kernel layouts")
         return {"format": "cfpnet_amd.FlatAdamW/1", "kernel_layout": self._to_torch is not None, "step_count": self.opt.step_count,
-                "w_chamfer": self.w_chamfer, "layout": self._layout_signature(), "exp_avg": self.opt.m.detach().cpu().clone(), "exp_avg_sq": self.opt.v.detach().cpu().clone()}
+                "w_chamfer": self.w_chamfer, "w_zone": self.w_zone, "zone_only": self.zone_only, "layout": self._layout_signature(), "exp_avg": self.opt.m.detach().cpu().clone(), "exp_avg_sq": self.opt.v.detach().cpu().clone()}
 
     def load_optimizer_state_dict(self, state: dict) -> None:
         if state.get("format") != "cfpnet_amd.FlatAdamW/1":
@@ -445,6 +490,11 @@ class Trainer:
         if float(state.get("w_chamfer", 0.0)) != self.w_chamfer:         # the moments belong to another objective
             raise ValueError(f"optimizer state was saved by a run with w_chamfer={float(state.get('w_chamfer', 0.0))}; "
                              f"this Trainer has w_chamfer={self.w_chamfer}")
+        mine = (float(getattr(self, "w_zone", 0.0)), bool(getattr(self, "zone_only", False)))
+        theirs = (float(state.get("w_zone", 0.0)), bool(state.get("zone_only", False)))
+        if theirs != mine:
+            raise ValueError(f"optimizer state was saved by a run with w_zone={theirs[0]}, zone_only={theirs[1]}; "
+                             f"this Trainer has w_zone={mine[0]}, zone_only={mine[1]}")
         if state["kernel_layout"] and self._to_torch is None:
             if not self.kernel_layout:
                 raise ValueError("optimizer state was saved in kernel layout; this Trainer keeps the reference layout")

@@ -827,6 +827,52 @@ int cfp_tof_zone_consistency(const float* pred, int Hp, int Wp, int H, int W, in
                              double* zone /* [B][Z][6] */, double* summary /* [B][10] */,
                              float* dev_map /* [B][H][W] or NULL */, cfp_stream_t stream);
 
+/* Zone-consistency loss: cfp_tof_zone_consistency turned into a training objective with a gradient on the prediction, on the device --
+ * the term that needs no ground truth (`train.py --w_zone`).  Everything up to the strongest run is the metric's, bit for bit, from the
+ * same code (csrc/metrics_pred.h, csrc/tof_cluster.h); the arguments up to floor_count are the metric's.
+ *   Depth     d_i is the depth at pixel i of the H x W grid: the float32 value of cfp_tof_zone_consistency (mode 0 with (lo, hi): the taps
+ *             clipped at model resolution, then the align-corners blend in float32).
+ *   Pixels    the pixels of zone z are those of the metric: sy <= (float)y < ey && sx <= (float)x < ex, in-image pixels only.
+ *   Counts    cnt_j is the zone's histogram of bin(d_i) (the metric's float32 bin); c'_j the histogram after the floor (bin 0 cleared,
+ *             floor_count subtracted, clamped at 0); [a, b) the strongest run of consecutive non-zero c'_j, lowest start winning ties;
+ *             n_z = sum_{j in [a,b)} c'_j.
+ *   Weights   omega_j = c'_j / cnt_j for j in [a, b), 0 elsewhere.
+ *   Zone mean m_z = (1/n_z) sum_{i in zone} omega_{bin(d_i)} * d_i, accumulated in float64 over the float32 d_i; 0 when n_z = 0.  The
+ *             sensor model's mu weights the bin centres by the floored counts, so m_z uses the same weights: |m_z - mu_z| <= bin_width/2
+ *             for any floor, which the unweighted mean of the run's pixels does not keep.
+ *   Compared  a zone is compared when mask != 0, n_z > 0 and the measured mu_m (raw[b][z][0]) is finite; n_b is their number in image b.
+ *             The sigma column of raw is not used.
+ *   Residual  r_z = m_z - mu_m.
+ *   Dead zone e_z = max(|r_z| - bin_width/2, 0): the sensor cannot tell depths apart inside its bin.
+ *   Penalty   Huber: rho_z = e_z^2 / (2 delta) if e_z <= delta, else e_z - delta/2; delta > 0 and finite (CFP_EINVAL otherwise).
+ *   Loss      L_b = (1/n_b) sum_{compared z} rho_z, and n_b = 0 contributes 0;  L = (1/B) sum_b L_b.
+ *   Gradient  with the run and the weights held constant:
+ *               dL/dd_i = sum_{z contains i, compared} grad_scale * min(e_z/delta, 1) * sgn(r_z) * omega_{bin(d_i)} / (B * n_b * n_z),
+ *             carried to pred through the transpose of the blend, times [lo <= pred_t <= hi] per tap t: the derivative of the clip,
+ *             closed interval, as torch.clamp.  A NaN d_i has no bin and no gradient; a tap outside the clip interval gets 0, NaN and
+ *             Inf included: the gradient this call produces is finite wherever the inputs are not, and L is finite.
+ *   ws        cfp_tof_zone_loss_ws_bytes(B, Z, bins) bytes (0 for arguments the call refuses), 16-byte aligned: omega_j / n_z per
+ *             (image, zone, bin).  CFP_EINVAL when null, misaligned or too small.
+ *   zone [B][Z][8] f64 = {m_z, n_z, r_z, rho_z, run_start, run_stop, state, coef}: run_start = a, run_stop = b (both = bins when
+ *             n_z = 0); state as cfp_tof_zone_consistency (CFP_ZONE_COMPARED ... from mask and n_z alone: a zone with state 0 and a
+ *             non-finite mu_m is not compared); r_z is NaN, rho_z and coef are 0 for a zone that is not compared;
+ *             coef = grad_scale * min(e_z/delta, 1) * sgn(r_z) / (B * n_b) = d(grad_scale * L)/dm_z.
+ *   out [1+B] f32 = L, then the L_b (L is the float64 mean of the float32 L_b).
+ *   grad_pred [B][Hp][Wp] f32 or NULL (value only: out and zone are the same bits).  accumulate = 0 writes every element, accumulate = 1
+ *             adds to what is there (one float32 addition per element), so a step needs no add launch after the SILog backward.
+ * Three launches on `stream` (two without grad_pred): one workgroup per (image, zone); one workgroup over the zone table in a fixed
+ * order; a gather over the pred grid, one lane per pixel, in which overlapping zones sum in index order in float64.  No host
+ * synchronisation, no global atomics and no floating-point atomics (integer LDS atomics only): two calls on the same tensors give
+ * identical bits.  CFP_ESHAPE for bins outside 1..1024, B*Z >= 2^31 or an image of 2^31 pixels or more. */
+size_t cfp_tof_zone_loss_ws_bytes(int B, int Z, int bins);
+int cfp_tof_zone_loss(const float* pred, int Hp, int Wp, int H, int W, int B, int interpolate, float lo, float hi,
+                      const float* rect /* [B][Z][4] sy sx ey ex */, const unsigned char* mask /* [B][Z] */,
+                      const double* raw /* [B][Z][2] measured mu, sigma */, int Z,
+                      float max_distance, int bins, double bin_width, int floor_count,
+                      double delta, float grad_scale, int accumulate, void* ws, size_t ws_bytes,
+                      double* zone /* [B][Z][8] */, float* out /* [1+B] */, float* grad_pred /* [B][Hp][Wp] or NULL */,
+                      cfp_stream_t stream);
+
 /* Pictures on the device: what the reference's `colorize` (src/utils/utils.py:44-64) paints on the host after moving the prediction
  * there, defined on the value the metrics evaluate.  Three entry points, one launch each; no workspace, no atomics, no host
  * synchronisation, capturable in a graph.  Every float32 operation below is rounded once (no fused multiply-add).

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Training with the reference's CLI and loop (`/root/reference/train.py:41-209`):
 
-    python train.py @configs/cfpnet_combine1.txt [--synthetic N] [--max_steps K] [--stop_after K] [--seed S] [--save weights/x.pt] [--dtype bf16|f16|f32|f32x3] [--eager] [--validate N] [--w_chamfer F] [--tof_rng host|device]
+    python train.py @configs/cfpnet_combine1.txt [--synthetic N] [--max_steps K] [--stop_after K] [--seed S] [--save weights/x.pt] [--dtype bf16|f16|f32|f32x3] [--eager] [--validate N] [--w_chamfer F] [--w_zone F [--zone_only]] [--tof_rng host|device]
                     [--resume checkpoints/x.pt] [--weight_path weights/x.pt] [--backend nccl|gloo] [--local_gpu I]
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 train.py @configs/cfpnet_combine1.txt --synthetic 4096
 
@@ -26,6 +26,14 @@ bf16 activations with float32 master parameters by default (`--dtype`); the step
 adaptive bin centres and the valid depths of each image (`cfp_bins_chamfer`): the `w_chamfer` term of the AdaBins recipe,
 on the `bin_edges` the training forward returns.  The logged `loss` stays the SILog value, `chamfer=` is printed next to it, and the
 weight is stored with the optimizer state: `--resume` with another weight is refused.
+
+`--w_zone F` (not a reference flag; default 0 = off) adds F x the zone-consistency loss to the objective (`cfp_tof_zone_loss`):
+the ToF zones are re-simulated from the prediction with the sensor model and their mean depth must reproduce the measured mu, up to half
+a bin.  The target is what the sensor measured -- `sim.simulate`'s `fh`, `mask` and `rect_data`, taken BEFORE `--drop_hist` / `--noise_*`
+and `--tof_rng`: dropout and noise augment the model's input, so a withheld zone still supervises.  `zone=` is printed next to the loss
+and the weight is stored with the optimizer state.  `--zone_only` leaves SILog out (scenes without dense ground truth): the objective
+and the logged `loss` are F x the zone term alone.  The term re-simulates with the one distance the measurement was made with, so
+`--w_zone` with `--random_simu_max_d` is an error, as `evaluate_all.py --zone_consistency` is.  The sigma of the measurement is not used.
 
 `--tof_rng host|device` (not a reference flag; default host) says where the zone dropout of `--drop_hist` draws.  `host` is `drop_zones`
 below: the mask comes to the host, numpy draws, the mask goes back -- the one device-to-host wait of the loop.  `device` is one launch of
@@ -196,6 +204,8 @@ def main(argv=None):
     log_every = _pop(argv, "--log_every", 10, int)
     n_val = _pop(argv, "--validate", 0, int)
     w_chamfer = _pop(argv, "--w_chamfer", 0.0, float)    # objective = SILog + F * bin-centre chamfer loss (not a reference flag: popped here)
+    w_zone = _pop(argv, "--w_zone", 0.0, float)          # objective += F * zone-consistency loss (not a reference flag: popped here)
+    zone_only = "--zone_only" in argv                    # ... and SILog left out: no dense ground truth needed
     tof_rng = _pop(argv, "--tof_rng", "host")            # where the zone dropout / range noise draw: numpy on the host, or `cfp_tof_degrade` (not a reference flag)
     if tof_rng not in ("host", "device"):
         raise ValueError(f"--tof_rng takes host or device, got '{tof_rng}'")
@@ -205,9 +215,13 @@ def main(argv=None):
     eager = "--eager" in argv
     no_augment = "--no_augment" in argv
     sync_loss = "--sync_loss" in argv                # global-batch SILog (three moments all-reduced), the reference's DataParallel semantics
-    argv = [a for a in argv if a not in ("--eager", "--no_augment", "--sync_loss")]
+    argv = [a for a in argv if a not in ("--eager", "--no_augment", "--sync_loss", "--zone_only")]
     args = config.parse_args(argv) if argv else config.defaults()
     args.mode = "train"
+    if w_zone > 0 and getattr(args, "random_simu_max_d", False):
+        raise ValueError("--w_zone re-simulates the zones with the distance the measurement was made with: not with --random_simu_max_d")
+    if zone_only and not w_zone > 0:
+        raise ValueError("--zone_only needs --w_zone F > 0")
 
     rank, world, local = int(os.environ.get("RANK", 0)), int(os.environ.get("WORLD_SIZE", 1)), int(os.environ.get("LOCAL_RANK", 0))
     dist = None
@@ -268,7 +282,8 @@ def main(argv=None):
                  clip_grad_norm=None if args.disable_clip_grad else 0.1, device=dev, dist=dist, world=world, n_bins=int(args.n_bins),
                  min_val=float(args.min_depth), max_val=float(args.max_depth), change_embedding=bool(args.change_embedding), dtype=dtype, no_skip_inside=bool(getattr(args, "no_skip_inside", False)),
                  norm=str(args.norm), sync_loss=sync_loss, zone_offset_bound=zone_offset,
-                 zone_layout=zone_layout(args, H, W) if zone_offset > 0 else None, w_chamfer=w_chamfer)
+                 zone_layout=zone_layout(args, H, W) if zone_offset > 0 else None, w_chamfer=w_chamfer, w_zone=w_zone, zone_only=zone_only,
+                 zone_max_distance=float(getattr(args, "simu_max_distance", 4.0) or 4.0))
     if opt_state is not None:
         tr.load_optimizer_state_dict(opt_state)
     elif start_step > 0:
@@ -381,6 +396,8 @@ def main(argv=None):
             elif drop > 1e-3:
                 mask, hist_data = drop_zones(sim, s, drop, rng)
             inp = {"rgb": img, "additional": {"hist_data": hist_data, "rect_data": s["rect_data"], "mask": mask, "patch_info": step_info}}
+            if w_zone > 0:                                    # the zone term's target: the measurement before dropout and noise
+                inp["additional"].update(raw_data=s["fh"], zone_mask=s["mask"])
             if not eager and tr._graph is None:
                 tr.capture(inp, depd)                         # the whole step as one HIP graph from here on
             loss, lr, beta1 = tr.step(inp, depd, zone_offsets=zoffs)
@@ -391,7 +408,8 @@ def main(argv=None):
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
                 cham = f" chamfer={float(tr.last_chamfer):.4f}" if w_chamfer > 0 else ""
-                print(f"epoch {epoch + 1} step {step}/{total_steps} loss {float(loss):.4f}{cham} lr {lr:.2e} beta1 {beta1:.3f} {seen / dt:.1f} samples/s", flush=True)
+                zl = f" zone={float(tr.last_zone):.5f}" if w_zone > 0 else ""
+                print(f"epoch {epoch + 1} step {step}/{total_steps} loss {float(loss):.4f}{cham}{zl} lr {lr:.2e} beta1 {beta1:.3f} {seen / dt:.1f} samples/s", flush=True)
         if rank == 0 and n_val > 0 and step % max(1, int(args.validate_every)) == 0 and step != last_validated:      # train.py:137: end of epoch
             validate(step, epoch)
         if stop_after and steps_here >= stop_after:
