@@ -113,11 +113,8 @@ extern "C" int cfp_eval_metrics(const float* pred, int Hp, int Wp, const float* 
   CFP_REQUIRE(lo < hi, CFP_EINVAL, "cfp_eval_metrics: empty depth range");
   CFP_REQUIRE(ws_bytes >= cfp_eval_metrics_ws_bytes(B), CFP_EINVAL, "cfp_eval_metrics: workspace too small");
   CFP_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0, CFP_EINVAL, "cfp_eval_metrics: workspace must be 8-byte aligned");
-  MetP p;
-  p.pred = pred; p.gt = gt; p.partial = reinterpret_cast<double*>(ws); p.out = out;
-  p.B = B; p.Hp = Hp; p.Wp = Wp; p.H = H; p.W = W; p.interpolate = interpolate; p.mode = mode; p.lo = lo; p.hi = hi;
-  p.sy = H > 1 ? (float)(Hp - 1) / (float)(H - 1) : 0.f;
-  p.sx = W > 1 ? (float)(Wp - 1) / (float)(W - 1) : 0.f;
+  MetP p = met_params(pred, gt, Hp, Wp, H, W, B, interpolate, mode, lo, hi);
+  p.partial = reinterpret_cast<double*>(ws); p.out = out;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(metrics_kernel, dim3(kMetBlocks, B), dim3(256), 0, s, p);
   hipLaunchKernelGGL(metrics_finalize_kernel, dim3(B), dim3(64), 0, s, p.partial, out);

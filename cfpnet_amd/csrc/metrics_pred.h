@@ -12,6 +12,18 @@ struct MetP {
   float lo, hi, sy, sx;
 };
 
+// The block of a B x Hp x Wp prediction seen on the H x W grid, with the align-corners scales every kernel here uses; `partial` and `out`
+// are null: the caller that uses them sets them afterwards.
+inline MetP met_params(const float* pred, const float* gt, int Hp, int Wp, int H, int W, int B, int interpolate, int mode, float lo,
+                       float hi) {
+  MetP p;
+  p.pred = pred; p.gt = gt; p.partial = nullptr; p.out = nullptr;
+  p.B = B; p.Hp = Hp; p.Wp = Wp; p.H = H; p.W = W; p.interpolate = interpolate; p.mode = mode; p.lo = lo; p.hi = hi;
+  p.sy = H > 1 ? (float)(Hp - 1) / (float)(H - 1) : 0.f;
+  p.sx = W > 1 ? (float)(Wp - 1) / (float)(W - 1) : 0.f;
+  return p;
+}
+
 __device__ __forceinline__ float clipf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }   // NaN passes, like np.clip
 
 __device__ __forceinline__ float met_pred(const MetP& p, const float* __restrict__ pb, int i) {

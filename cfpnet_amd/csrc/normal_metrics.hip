@@ -242,11 +242,7 @@ extern "C" int cfp_normal_metrics(const float* pred, int Hp, int Wp, const float
   CFP_REQUIRE(ws_bytes >= cfp_normal_metrics_ws_bytes(B, H, W), CFP_EINVAL, "cfp_normal_metrics: workspace too small");
   CFP_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0, CFP_EINVAL, "cfp_normal_metrics: workspace must be 8-byte aligned");
   NormP p;
-  MetP& m = p.m;
-  m.pred = pred; m.gt = gt; m.partial = nullptr; m.out = nullptr;
-  m.B = B; m.Hp = Hp; m.Wp = Wp; m.H = H; m.W = W; m.interpolate = interpolate; m.mode = 0; m.lo = lo; m.hi = hi;
-  m.sy = H > 1 ? (float)(Hp - 1) / (float)(H - 1) : 0.f;
-  m.sx = W > 1 ? (float)(Wp - 1) / (float)(W - 1) : 0.f;
+  p.m = met_params(pred, gt, Hp, Wp, H, W, B, interpolate, 0, lo, hi);
   p.K = K;
   p.partial = reinterpret_cast<double*>(ws);
   p.cells = reinterpret_cast<int*>(static_cast<char*>(ws) + nm_partial_bytes(B, H, W));

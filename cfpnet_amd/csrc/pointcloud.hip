@@ -234,11 +234,7 @@ extern "C" int cfp_depth_unproject(const float* pred, int Hp, int Wp, int H, int
   CFP_REQUIRE(interpolate || (Hp == H && Wp == W), CFP_ESHAPE, "cfp_depth_unproject: sizes differ and interpolate is off");
   CFP_REQUIRE(lo < hi, CFP_EINVAL, "cfp_depth_unproject: empty depth range");
   UnprojP p;
-  MetP& m = p.m;
-  m.pred = pred; m.gt = nullptr; m.partial = nullptr; m.out = nullptr;
-  m.B = B; m.Hp = Hp; m.Wp = Wp; m.H = H; m.W = W; m.interpolate = interpolate; m.mode = 0; m.lo = lo; m.hi = hi;
-  m.sy = H > 1 ? (float)(Hp - 1) / (float)(H - 1) : 0.f;
-  m.sx = W > 1 ? (float)(Wp - 1) / (float)(W - 1) : 0.f;
+  p.m = met_params(pred, nullptr, Hp, Wp, H, W, B, interpolate, 0, lo, hi);
   p.K = K; p.points = points; p.normals = normals;
   p.tiles_x = cdiv(W, kTileW); p.tiles_y = cdiv(H, kTileH);
   p.tiles = (long long)B * p.tiles_x * p.tiles_y;
@@ -282,12 +278,7 @@ extern "C" int cfp_points_compact(const float* points, const float* normals, int
   CFP_REQUIRE(ws_bytes >= cfp_points_compact_ws_bytes(B, H, W, stride), CFP_EINVAL, "cfp_points_compact: workspace too small");
   CFP_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7) == 0, CFP_EINVAL, "cfp_points_compact: workspace must be 8-byte aligned");
   CompP p;
-  MetP& u = p.u;
-  u.pred = unc; u.gt = nullptr; u.partial = nullptr; u.out = nullptr;
-  u.B = B; u.Hp = unc ? Hu : H; u.Wp = unc ? Wu : W; u.H = H; u.W = W; u.mode = 0; u.lo = 0.f; u.hi = 0.f;
-  u.interpolate = unc && (Hu != H || Wu != W) ? 1 : 0;
-  u.sy = H > 1 ? (float)(u.Hp - 1) / (float)(H - 1) : 0.f;
-  u.sx = W > 1 ? (float)(u.Wp - 1) / (float)(W - 1) : 0.f;
+  p.u = met_params(unc, nullptr, unc ? Hu : H, unc ? Wu : W, H, W, B, unc && (Hu != H || Wu != W) ? 1 : 0, 0, 0.f, 0.f);
   p.points = points; p.normals = normals; p.unc_stride = unc_stride; p.has_unc = unc ? 1 : 0;
   p.Wc = (W + stride - 1) / stride;
   p.N = (int)comp_candidates(H, W, stride);

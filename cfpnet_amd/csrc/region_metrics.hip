@@ -288,10 +288,8 @@ extern "C" int cfp_eval_metrics_regions(const float* pred, int Hp, int Wp, const
     p.edges[e] = v;
   }
   MetP& m = p.m;
-  m.pred = pred; m.gt = gt; m.partial = reinterpret_cast<double*>(ws); m.out = out;
-  m.B = B; m.Hp = Hp; m.Wp = Wp; m.H = H; m.W = W; m.interpolate = interpolate; m.mode = mode; m.lo = lo; m.hi = hi;
-  m.sy = H > 1 ? (float)(Hp - 1) / (float)(H - 1) : 0.f;
-  m.sx = W > 1 ? (float)(Wp - 1) / (float)(W - 1) : 0.f;
+  m = met_params(pred, gt, Hp, Wp, H, W, B, interpolate, mode, lo, hi);
+  m.partial = reinterpret_cast<double*>(ws); m.out = out;
   p.rect = rect; p.mask = mask; p.Z = Z; p.n_edges = n_edges;
   const int R = n_edges + 1, Q = n_edges == 0 ? 1 : n_edges + 2;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);

@@ -299,12 +299,8 @@ extern "C" int cfp_render_depth(const float* pred, int Hp, int Wp, const float* 
     CFP_REQUIRE(std::isfinite(u16_scale) && u16_scale > 0.f, CFP_EINVAL, "cfp_render_depth: u16_scale must be finite and positive");
   }
   DepthP p;
-  MetP& m = p.m;
-  m.pred = use_pred ? pred : nullptr; m.gt = use_gt ? gt : nullptr; m.partial = nullptr; m.out = nullptr;
-  m.B = B; m.Hp = use_pred ? Hp : H; m.Wp = use_pred ? Wp : W; m.H = H; m.W = W; m.interpolate = use_pred ? interpolate : 0; m.mode = 0;
-  m.lo = lo; m.hi = hi;
-  m.sy = H > 1 ? (float)(m.Hp - 1) / (float)(H - 1) : 0.f;
-  m.sx = W > 1 ? (float)(m.Wp - 1) / (float)(W - 1) : 0.f;
+  p.m = met_params(use_pred ? pred : nullptr, use_gt ? gt : nullptr, use_pred ? Hp : H, use_pred ? Wp : W, H, W, B,
+                   use_pred ? interpolate : 0, 0, lo, hi);
   p.what = what; p.Q = cdiv(W, 4);
   p.vmin = vmin; p.vmax = vmax; p.u16_scale = u16_scale; p.lut = lut;
   p.o = make_out(out, image_stride, pitch);

@@ -419,10 +419,7 @@ extern "C" int cfp_unc_sparsification(const float* pred, const float* unc, int H
     attr = true;
   }
   SpKeyP q;
-  q.m.pred = pred; q.m.gt = gt; q.m.partial = nullptr; q.m.out = nullptr;
-  q.m.B = B; q.m.Hp = Hp; q.m.Wp = Wp; q.m.H = H; q.m.W = W; q.m.interpolate = interpolate; q.m.mode = mode; q.m.lo = lo; q.m.hi = hi;
-  q.m.sy = H > 1 ? (float)(Hp - 1) / (float)(H - 1) : 0.f;
-  q.m.sx = W > 1 ? (float)(Wp - 1) / (float)(W - 1) : 0.f;
+  q.m = met_params(pred, gt, Hp, Wp, H, W, B, interpolate, mode, lo, hi);
   q.unc = unc; q.keys = reinterpret_cast<unsigned*>(ws);
   const SpLayout l = spars_layout(B, H, W, steps);
   unsigned char* base = reinterpret_cast<unsigned char*>(ws);

@@ -2,8 +2,9 @@
 // mu, as a training objective with a gradient on the prediction -- the term that needs no ground truth.  The definition is in
 // include/cfpnet_hip.h.
 //
-//   Everything up to the strongest run is the metric's (zone_consistency.hip), bit for bit: met_pred of metrics_pred.h in mode 0, the
-//   pixels of zc_span, the histogram, the floor and the run of tof_cluster.h.
+//   Everything up to the strongest run is the metric's (zone_consistency.hip), bit for bit, because it is the same code: the argument
+//   checks, the walk over a zone's pixels (met_pred of metrics_pred.h in mode 0 on the pixels of zc_span) and the zone staging of a tile
+//   are zone_core.h; the histogram, the floor and the run are tof_cluster.h.
 //
 // Zone kernel.  One workgroup of 256 lanes per (image, zone).  First sweep: the histogram, as the metric builds it.  The raw counts are
 // copied beside it in LDS before tof_cluster floors them, so that omega_j = c'_j / cnt_j exists for the bins of the run.  Second sweep over the
@@ -13,30 +14,20 @@
 // Image kernel.  ONE workgroup; wave w takes images w, w + 4, ...: lane t takes zones t, t + 64, ... in ascending order, a butterfly, then
 // lane 0 has n_b and L_b.  A second pass writes r_z, rho_z and coef_z = s * min(e_z / delta, 1) * sgn(r_z) / (B * n_b).  After a barrier
 // thread 0 sums the L_b in index order: L needs no atomic and no further launch.
-// Backward kernel (skipped when grad_pred is null).  A gather over the pred grid, one lane per pixel of an 8 x 32 tile.  The image's zones
-// go through LDS in chunks of 256 and only those with coef != 0 that can touch the tile's footprint are kept, in index order, so Z is not
-// bounded by LDS.  A lane walks the pixels of the H x W grid whose bilinear footprint holds its pred pixel (as silog_bwd_kernel does), forms
-// each one's depth and bin once it lies in a kept zone, and adds  w_y * w_x * coef_z * omega_bin / n_z  in float64; one rounding to float32
-// at the end, times the derivative of the clip.
+// Backward kernel (skipped when grad_pred is null).  A gather over the pred grid, one lane per pixel of an 8 x 32 tile.  Only the zones
+// with coef != 0 that can touch the tile's footprint are staged (ZoneStage).  A lane walks the pixels of the H x W grid whose bilinear
+// footprint holds its pred pixel (as silog_bwd_kernel does), forms each one's depth and bin once it lies in a kept zone, and adds
+// w_y * w_x * coef_z * omega_bin / n_z  in float64; one rounding to float32 at the end, times the derivative of the clip.
 // No global atomics, no floating-point atomics (integer LDS atomics only): two calls on the same tensors give identical bits.
-#include "common.h"
-#include "metrics_pred.h"
-#include "tof_cluster.h"
+#include "zone_core.h"
 
 #include <algorithm>
 
 namespace {
 
-constexpr int kZlBatch = 8;                           // pixels per lane in flight
 constexpr int kZlZone = 8;                            // {m_z, n_z, r_z, rho_z, run_start, run_stop, state, coef}
-constexpr int kZlChunk = 256;                         // zones looked at per pass of the backward kernel
-constexpr int kZlTileH = 8, kZlTileW = 32;           // its tile of the pred grid: one pixel per lane
-static_assert(kZlTileH * kZlTileW == kZlChunk && kZlChunk == 256, "one lane per pixel of the tile and per zone of the chunk, four waves");
 
-struct ZoneLossP {
-  MetP m;                                             // pred, Hp, Wp, H, W, interpolate, mode 0, lo, hi, sy, sx
-  const float* rect; const unsigned char* mask; const double* raw; int Z;
-  float max_d; int bins; double bin_width; int floor_count;
+struct ZoneLossP : ZoneArgs {
   double delta; float grad_scale; int accumulate;
   double* table;                                      // workspace [B][Z][bins]: omega_j / n_z
   double* zone; float* out; float* grad_pred;
@@ -47,36 +38,16 @@ __global__ __launch_bounds__(kTofThreads) void zone_loss_zone_kernel(ZoneLossP p
   __shared__ int rawc[kTofMaxBins];
   __shared__ unsigned long long best;
   __shared__ double sAcc[kTofThreads / 64];
-  const MetP& m = p.m;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int b = blockIdx.x / p.Z, z = blockIdx.x - b * p.Z;
   const long long o = (long long)b * p.Z + z;
-  const float* pb = m.pred + (long long)b * m.Hp * m.Wp;
 
   for (int i = tid; i < p.bins; i += kTofThreads) cnt[i] = 0;
   if (tid == 0) best = 0ull;
   __syncthreads();
 
-  int y0, y1, x0, x1;
-  zc_span(p.rect[o * 4 + 0], p.rect[o * 4 + 2], m.H, y0, y1);
-  zc_span(p.rect[o * 4 + 1], p.rect[o * 4 + 3], m.W, x0, x1);
-  const int rw = x1 - x0;
-  const int npx = (y1 - y0) * rw;                     // the in-image pixels of the zone; < 2^31 with H * W
-
-  for (int c0 = 0; c0 < npx; c0 += kTofThreads * kZlBatch) {
-    float v[kZlBatch];
-#pragma unroll
-    for (int u = 0; u < kZlBatch; ++u) {
-      const int i = min(c0 + u * kTofThreads + tid, npx - 1);
-      const int y = i / rw, x = i - y * rw;
-      v[u] = met_pred(m, pb, (y0 + y) * m.W + (x0 + x));
-    }
-#pragma unroll
-    for (int u = 0; u < kZlBatch; ++u) {
-      const bool in = c0 + u * kTofThreads + tid < npx;
-      tof_hist_add(cnt, in ? tof_bin(v[u], p.max_d, p.bins) : -1, lane);
-    }
-  }
+  const ZoneSweep sweep(p, b, z);
+  sweep.walk(p.m, [&](float v, bool in) { tof_hist_add(cnt, in ? tof_bin(v, p.max_d, p.bins) : -1, lane); });
   __syncthreads();
   for (int i = tid; i < p.bins; i += kTofThreads) rawc[i] = cnt[i];       // the bins this lane reads first in tof_cluster
 
@@ -85,20 +56,10 @@ __global__ __launch_bounds__(kTofThreads) void zone_loss_zone_kernel(ZoneLossP p
   // second sweep: sum omega_bin(d) * d over the pixels whose bin lies in the run
   double acc = 0.0;
   if (run.n > 0) {
-    for (int c0 = 0; c0 < npx; c0 += kTofThreads * kZlBatch) {
-      float v[kZlBatch];
-#pragma unroll
-      for (int u = 0; u < kZlBatch; ++u) {
-        const int i = min(c0 + u * kTofThreads + tid, npx - 1);
-        const int y = i / rw, x = i - y * rw;
-        v[u] = met_pred(m, pb, (y0 + y) * m.W + (x0 + x));
-      }
-#pragma unroll
-      for (int u = 0; u < kZlBatch; ++u) {
-        const int bin = c0 + u * kTofThreads + tid < npx ? tof_bin(v[u], p.max_d, p.bins) : -1;
-        if (bin >= run.start && bin < run.stop) acc += ((double)cnt[bin] / (double)rawc[bin]) * (double)v[u];
-      }
-    }
+    sweep.walk(p.m, [&](float v, bool in) {
+      const int bin = in ? tof_bin(v, p.max_d, p.bins) : -1;
+      if (bin >= run.start && bin < run.stop) acc += ((double)cnt[bin] / (double)rawc[bin]) * (double)v;
+    });
   }
 #pragma unroll
   for (int s = 32; s > 0; s >>= 1) acc += __shfl_xor(acc, s);
@@ -179,17 +140,16 @@ __device__ __forceinline__ void zl_footprint(float s, int a, int b, int n, int& 
   hi = s > 0.f ? min(n - 1, (int)floorf(((float)b + 1.f) / s) + 1) : n - 1;
 }
 
-__global__ __launch_bounds__(kZlChunk) void zone_loss_bwd_kernel(ZoneLossP p, int tiles_x) {
-  __shared__ float sRect[kZlChunk][4];
-  __shared__ double sCoef[kZlChunk];
-  __shared__ int sIdx[kZlChunk];
-  __shared__ int sKept[kZlChunk / 64];
+__global__ __launch_bounds__(kZoneChunk) void zone_loss_bwd_kernel(ZoneLossP p, int tiles_x) {
+  __shared__ ZoneStage st;
+  __shared__ double sCoef[kZoneChunk];
+  __shared__ int sIdx[kZoneChunk];
   const MetP& m = p.m;
-  const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+  const int t = threadIdx.x;
   const int tyi = blockIdx.x / tiles_x, txi = blockIdx.x - tyi * tiles_x;
-  const int ty0 = tyi * kZlTileH, tx0 = txi * kZlTileW;
-  const int ty1 = min(ty0 + kZlTileH, m.Hp) - 1, tx1 = min(tx0 + kZlTileW, m.Wp) - 1;      // the last pixel of the tile inside pred
-  const int y = ty0 + t / kZlTileW, x = tx0 + t % kZlTileW;
+  const int ty0 = tyi * kZoneTileH, tx0 = txi * kZoneTileW;
+  const int ty1 = min(ty0 + kZoneTileH, m.Hp) - 1, tx1 = min(tx0 + kZoneTileW, m.Wp) - 1;  // the last pixel of the tile inside pred
+  const int y = ty0 + t / kZoneTileW, x = tx0 + t % kZoneTileW;
   const bool live = y < m.Hp && x < m.Wp;
   // the pixels of the H x W grid that can hold a pixel of the tile / this lane's pixel in their footprint
   int TY0 = ty0, TY1 = ty1, TX0 = tx0, TX1 = tx1, Y0 = y, Y1 = y, X0 = x, X1 = x;
@@ -197,29 +157,24 @@ __global__ __launch_bounds__(kZlChunk) void zone_loss_bwd_kernel(ZoneLossP p, in
     zl_footprint(m.sy, ty0, ty1, m.H, TY0, TY1); zl_footprint(m.sx, tx0, tx1, m.W, TX0, TX1);
     zl_footprint(m.sy, y, y, m.H, Y0, Y1); zl_footprint(m.sx, x, x, m.W, X0, X1);
   }
-  const float ylo = (float)TY0, yhi = (float)TY1, xlo = (float)TX0, xhi = (float)TX1;
+  const ZoneTile tile = {(float)TY0, (float)TY1, (float)TX0, (float)TX1};
   for (int b = blockIdx.y; b < m.B; b += gridDim.y) {
     const float* pb = m.pred + (long long)b * m.Hp * m.Wp;
     double acc = 0.0;
-    for (int z0 = 0; z0 < p.Z; z0 += kZlChunk) {
+    for (int z0 = 0; z0 < p.Z; z0 += kZoneChunk) {
       const int z = z0 + t;
       bool keep = false;
-      float r0 = 0.f, r1 = 0.f, r2 = 0.f, r3 = 0.f;
+      float r[4] = {0.f, 0.f, 0.f, 0.f};
       double coef = 0.0;
       if (z < p.Z) {
         const long long o = (long long)b * p.Z + z;
-        r0 = p.rect[o * 4 + 0]; r1 = p.rect[o * 4 + 1]; r2 = p.rect[o * 4 + 2]; r3 = p.rect[o * 4 + 3];
+        r[0] = p.rect[o * 4 + 0]; r[1] = p.rect[o * 4 + 1]; r[2] = p.rect[o * 4 + 2]; r[3] = p.rect[o * 4 + 3];
         coef = p.zone[o * kZlZone + 7];
-        keep = coef != 0.0 && r0 <= yhi && ylo < r2 && r1 <= xhi && xlo < r3;      // a NaN coordinate: never kept
+        keep = coef != 0.0 && tile.touches(r);
       }
-      const unsigned long long kept = __ballot(keep);
-      __syncthreads();                                // the chunk before is read
-      if (lane == 0) sKept[wave] = (int)__popcll(kept);
-      __syncthreads();
-      int pos = (int)__popcll(kept & ((1ull << lane) - 1ull));
-      for (int k = 0; k < wave; ++k) pos += sKept[k];
-      const int nz = (sKept[0] + sKept[1]) + (sKept[2] + sKept[3]);
-      if (keep) { sRect[pos][0] = r0; sRect[pos][1] = r1; sRect[pos][2] = r2; sRect[pos][3] = r3; sCoef[pos] = coef; sIdx[pos] = z; }
+      int pos;
+      const int nz = st.stage(r, keep, pos);
+      if (keep) { sCoef[pos] = coef; sIdx[pos] = z; }
       __syncthreads();
       if (!live || nz == 0) continue;                 // nz is the same in every lane; a lane off the image takes part in the barriers only
       for (int Y = Y0; Y <= Y1; ++Y) {
@@ -249,7 +204,7 @@ __global__ __launch_bounds__(kZlChunk) void zone_loss_bwd_kernel(ZoneLossP p, in
           int bin = -2;                               // -2: the depth of (Y, X) is not formed yet
           double g = 0.0;
           for (int k = 0; k < nz; ++k) {
-            if (sRect[k][0] <= fY && fY < sRect[k][2] && sRect[k][1] <= fX && fX < sRect[k][3]) {
+            if (st.holds(k, fY, fX)) {
               if (bin == -2) bin = tof_bin(met_pred(m, pb, Y * m.W + X), p.max_d, p.bins);
               if (bin < 0) break;                     // a NaN or out-of-range depth has no bin and no gradient
               g += sCoef[k] * p.table[((long long)b * p.Z + sIdx[k]) * p.bins + bin];
@@ -280,34 +235,22 @@ extern "C" int cfp_tof_zone_loss(const float* pred, int Hp, int Wp, int H, int W
                                  double bin_width, int floor_count, double delta, float grad_scale, int accumulate, void* ws,
                                  size_t ws_bytes, double* zone, float* out, float* grad_pred, cfp_stream_t stream) {
   CFP_REQUIRE(pred && rect && mask && raw && ws && zone && out, CFP_EINVAL, "cfp_tof_zone_loss: null pointer");
-  CFP_REQUIRE(B > 0 && Hp > 0 && Wp > 0 && H > 0 && W > 0 && Z > 0, CFP_ESHAPE, "cfp_tof_zone_loss: non-positive dimension");
-  CFP_REQUIRE((long long)H * W < (1ll << 31) && (long long)Hp * Wp < (1ll << 31) && H <= (1 << 24) && W <= (1 << 24), CFP_ESHAPE,
-              "cfp_tof_zone_loss: image too large");
-  CFP_REQUIRE(interpolate || (Hp == H && Wp == W), CFP_ESHAPE, "cfp_tof_zone_loss: sizes differ and interpolate is off");
-  CFP_REQUIRE(lo < hi, CFP_EINVAL, "cfp_tof_zone_loss: empty depth range");
-  CFP_REQUIRE(bins > 0 && bins <= kTofMaxBins, CFP_ESHAPE, "cfp_tof_zone_loss: bins must be in 1..1024");
-  CFP_REQUIRE(max_distance > 0.f && bin_width > 0.0 && floor_count >= 0, CFP_EINVAL, "cfp_tof_zone_loss: bad histogram parameters");
+  ZoneLossP p;
+  if (const int rc = zone_args(p, "cfp_tof_zone_loss", pred, Hp, Wp, H, W, B, interpolate, lo, hi, rect, mask, raw, Z, max_distance, bins,
+                               bin_width, floor_count)) return rc;
   CFP_REQUIRE(delta > 0.0 && delta - delta == 0.0, CFP_EINVAL, "cfp_tof_zone_loss: delta must be positive and finite");
   CFP_REQUIRE(accumulate == 0 || accumulate == 1, CFP_EINVAL, "cfp_tof_zone_loss: accumulate must be 0 or 1");
   CFP_REQUIRE((long long)B * Z < (1ll << 31), CFP_ESHAPE, "cfp_tof_zone_loss: too many zones");
   CFP_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 16 == 0, CFP_EINVAL, "cfp_tof_zone_loss: workspace must be 16-byte aligned");
   CFP_REQUIRE(ws_bytes >= cfp_tof_zone_loss_ws_bytes(B, Z, bins), CFP_EINVAL, "cfp_tof_zone_loss: workspace too small");
-  ZoneLossP p;
-  MetP& m = p.m;
-  m.pred = pred; m.gt = nullptr; m.partial = nullptr; m.out = nullptr;
-  m.B = B; m.Hp = Hp; m.Wp = Wp; m.H = H; m.W = W; m.interpolate = interpolate; m.mode = 0; m.lo = lo; m.hi = hi;
-  m.sy = H > 1 ? (float)(Hp - 1) / (float)(H - 1) : 0.f;
-  m.sx = W > 1 ? (float)(Wp - 1) / (float)(W - 1) : 0.f;
-  p.rect = rect; p.mask = mask; p.raw = raw; p.Z = Z;
-  p.max_d = max_distance; p.bins = bins; p.bin_width = bin_width; p.floor_count = floor_count;
   p.delta = delta; p.grad_scale = grad_scale; p.accumulate = accumulate;
   p.table = reinterpret_cast<double*>(ws); p.zone = zone; p.out = out; p.grad_pred = grad_pred;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   hipLaunchKernelGGL(zone_loss_zone_kernel, dim3(B * Z), dim3(kTofThreads), 0, s, p);
   hipLaunchKernelGGL(zone_loss_image_kernel, dim3(1), dim3(256), 0, s, p);
   if (grad_pred) {
-    const int tiles_x = cdiv(Wp, kZlTileW);
-    hipLaunchKernelGGL(zone_loss_bwd_kernel, dim3(tiles_x * cdiv(Hp, kZlTileH), std::min(B, 65535)), dim3(kZlChunk), 0, s, p, tiles_x);
+    const int tiles_x = cdiv(Wp, kZoneTileW);
+    hipLaunchKernelGGL(zone_loss_bwd_kernel, dim3(tiles_x * cdiv(Hp, kZoneTileH), std::min(B, 65535)), dim3(kZoneChunk), 0, s, p, tiles_x);
   }
   return cfp_check_launch("cfp_tof_zone_loss");
 }

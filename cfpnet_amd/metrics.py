@@ -345,29 +345,7 @@ def zone_consistency(pred: torch.Tensor, raw_data: torch.Tensor, rect_data: torc
     `floor_count` the ambient floor of the sensor model ->(summary [B,10] f64 in `ZONE_CONSISTENCY_NAMES` order, zone
     [B,Z,6] f64 in `ZONE_COLUMNS` order), and with `dev_map` a third tensor [B,H,W] f32: the prediction minus the measured mu of the
     first measured zone that contains the pixel, NaN outside.  No host synchronisation."""
-    from . import pointcloud
-    pred = pointcloud._pred3(pred)
-    for name, t, ok in (("raw_data", raw_data, (torch.float64, torch.float32)), ("rect_data", rect_data, (torch.float32,)),
-                        ("mask", mask, (torch.bool, torch.uint8))):
-        if not isinstance(t, torch.Tensor) or t.dtype not in ok or not t.is_cuda:
-            raise ValueError(f"{name} must be a {' / '.join(str(d).replace('torch.', '') for d in ok)} device tensor")
-    B, Hp, Wp = pred.shape
-    H, W = pointcloud._size(size, Hp, Wp)
-    if rect_data.dim() != 3 or rect_data.shape[0] != B or rect_data.shape[2] != 4 or rect_data.shape[1] < 1:
-        raise ValueError(f"rect_data must be [B,Z,4] with B = {B}, got {tuple(rect_data.shape)}")
-    Z = rect_data.shape[1]
-    if tuple(mask.shape) != (B, Z):
-        raise ValueError(f"mask must be [B,Z] = {(B, Z)}, got {tuple(mask.shape)}")
-    if tuple(raw_data.shape) != (B, Z, 2):
-        raise ValueError(f"raw_data must be [B,Z,2] = {(B, Z, 2)}, got {tuple(raw_data.shape)}")
-    if not float(lo) < float(hi):
-        raise ValueError(f"empty depth range [{lo}, {hi}]")
-    md = float(max_distance)
-    if not md > 0:
-        raise ValueError(f"max_distance must be positive, got {max_distance}")
-    bins = int(md / tof.BIN_WIDTH)
-    raw, rect, mk = raw_data.to(torch.float64).contiguous(), rect_data.contiguous(), mask.contiguous()
-    interp = int((Hp, Wp) != (H, W))                      # the rule of eval_metrics in EVALUATE_ALL order
+    pred, raw, rect, mk, B, Hp, Wp, H, W, Z, md, bins, interp = tof.zone_inputs(pred, raw_data, rect_data, mask, lo, hi, size, max_distance)
     summary = torch.empty(B, 10, dtype=torch.float64, device=pred.device)
     zone = torch.empty(B, Z, 6, dtype=torch.float64, device=pred.device)
     dmap = torch.empty(B, H, W, dtype=torch.float32, device=pred.device) if dev_map else None

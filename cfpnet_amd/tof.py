@@ -23,6 +23,36 @@ BIN_WIDTH = 0.04      # dataloader.py:93,104
 AMBIENT_FLOOR = 20    # dataloader.py:109
 
 
+def zone_inputs(pred, raw_data, rect_data, mask, lo, hi, size, max_distance):
+    """What `metrics.zone_consistency` and `train_ops.ZoneLoss` re-simulate the zones from, checked once for both: pred [B,h,w] /
+    [B,1,h,w] f32, raw_data [B,Z,2] f64 / f32, rect_data [B,Z,4] f32 and mask [B,Z] bool / uint8 on the device, `size` = (H, W) or None
+    for twice the prediction -> (pred [B,Hp,Wp], raw f64, rect, mask, all contiguous, B, Hp, Wp, H, W, Z, max_distance, bins,
+    interpolate): the arguments of `cfp_tof_zone_consistency` / `cfp_tof_zone_loss` up to `bins`."""
+    from . import pointcloud
+    pred = pointcloud._pred3(pred)
+    for name, t, ok in (("raw_data", raw_data, (torch.float64, torch.float32)), ("rect_data", rect_data, (torch.float32,)),
+                        ("mask", mask, (torch.bool, torch.uint8))):
+        if not isinstance(t, torch.Tensor) or t.dtype not in ok or not t.is_cuda:
+            raise ValueError(f"{name} must be a {' / '.join(str(d).replace('torch.', '') for d in ok)} device tensor")
+    B, Hp, Wp = pred.shape
+    H, W = pointcloud._size(size, Hp, Wp)
+    if rect_data.dim() != 3 or rect_data.shape[0] != B or rect_data.shape[2] != 4 or rect_data.shape[1] < 1:
+        raise ValueError(f"rect_data must be [B,Z,4] with B = {B}, got {tuple(rect_data.shape)}")
+    Z = rect_data.shape[1]
+    if tuple(mask.shape) != (B, Z):
+        raise ValueError(f"mask must be [B,Z] = {(B, Z)}, got {tuple(mask.shape)}")
+    if tuple(raw_data.shape) != (B, Z, 2):
+        raise ValueError(f"raw_data must be [B,Z,2] = {(B, Z, 2)}, got {tuple(raw_data.shape)}")
+    if not float(lo) < float(hi):
+        raise ValueError(f"empty depth range [{lo}, {hi}]")
+    md = float(max_distance)
+    if not md > 0:
+        raise ValueError(f"max_distance must be positive, got {max_distance}")
+    interp = int((Hp, Wp) != (H, W))                      # the rule of eval_metrics in EVALUATE_ALL order
+    return (pred, raw_data.to(torch.float64).contiguous(), rect_data.contiguous(), mask.contiguous(), B, Hp, Wp, H, W, Z, md,
+            int(md / BIN_WIDTH), interp)
+
+
 def _cfg(config, name, default):
     return getattr(config, name, default)
 

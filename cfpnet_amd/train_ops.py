@@ -186,28 +186,9 @@ class ZoneLoss:
     def forward(self, pred: torch.Tensor, raw_data: torch.Tensor, rect_data: torch.Tensor, mask: torch.Tensor, lo: float, hi: float,
                 size=None, max_distance: float = 4.0, floor_count: int = tof.AMBIENT_FLOOR, delta: Optional[float] = None,
                 grad_scale: float = 1.0, grad_out: Optional[torch.Tensor] = None):
-        if pred.dim() == 4 and pred.shape[1] == 1:
-            pred = pred[:, 0]
-        if pred.dim() != 3 or pred.dtype != torch.float32 or not pred.is_cuda:
-            raise ValueError("pred must be a float32 device tensor [B,h,w] or [B,1,h,w]")
-        pred = pred.contiguous()
-        for name, t, ok in (("raw_data", raw_data, (torch.float64, torch.float32)), ("rect_data", rect_data, (torch.float32,)),
-                            ("mask", mask, (torch.bool, torch.uint8))):
-            if not isinstance(t, torch.Tensor) or t.dtype not in ok or not t.is_cuda:
-                raise ValueError(f"{name} must be a {' / '.join(str(d).replace('torch.', '') for d in ok)} device tensor")
-        B, Hp, Wp = pred.shape
-        H, W = (2 * Hp, 2 * Wp) if size is None else (int(size[0]), int(size[1]))
-        if rect_data.dim() != 3 or rect_data.shape[0] != B or rect_data.shape[2] != 4 or rect_data.shape[1] < 1:
-            raise ValueError(f"rect_data must be [B,Z,4] with B = {B}, got {tuple(rect_data.shape)}")
-        Z = rect_data.shape[1]
-        if tuple(mask.shape) != (B, Z) or tuple(raw_data.shape) != (B, Z, 2):
-            raise ValueError(f"mask must be [B,Z] = {(B, Z)} and raw_data [B,Z,2], got {tuple(mask.shape)} and {tuple(raw_data.shape)}")
-        md = float(max_distance)
-        if not md > 0:
-            raise ValueError(f"max_distance must be positive, got {max_distance}")
-        bins = int(md / tof.BIN_WIDTH)
+        pred, raw, rect, mk, B, Hp, Wp, H, W, Z, md, bins, interp = tof.zone_inputs(pred, raw_data, rect_data, mask, lo, hi, size,
+                                                                                    max_distance)
         delta = tof.BIN_WIDTH if delta is None else float(delta)
-        raw, rect, mk = raw_data.to(torch.float64).contiguous(), rect_data.contiguous(), mask.contiguous()
         dev = pred.device
         need = max(int(hip.load().cfp_tof_zone_loss_ws_bytes(B, Z, bins)), 16)
         if self._ws is None or self._ws.numel() < need or self._ws.device != dev:
@@ -225,7 +206,7 @@ class ZoneLoss:
                 self._own_grad = torch.empty(B, Hp, Wp, dtype=torch.float32, device=dev)
             grad, acc = self._own_grad, 0
         self.grad_pred, self._scale = grad, float(grad_scale)
-        hip.call("cfp_tof_zone_loss", pred.data_ptr(), Hp, Wp, H, W, B, int((Hp, Wp) != (H, W)), float(lo), float(hi), rect.data_ptr(),
+        hip.call("cfp_tof_zone_loss", pred.data_ptr(), Hp, Wp, H, W, B, interp, float(lo), float(hi), rect.data_ptr(),
                  mk.data_ptr(), raw.data_ptr(), Z, md, bins, tof.BIN_WIDTH, int(floor_count), delta, self._scale, acc, self._ws.data_ptr(),
                  self._ws.numel(), self.zone.data_ptr(), self._out.data_ptr(), hip.ptr(grad), hip.current_stream())
         return self._out[0]

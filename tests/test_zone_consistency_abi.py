@@ -8,10 +8,10 @@ import numpy as np
 import pytest
 
 import zone_consistency_ref as R
+from zone_abi_cases import EINVAL, check_shared_refusals
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "cfpnet_amd", "csrc")
-EINVAL, ESHAPE = -1, -2
 
 
 @pytest.fixture(scope="module")
@@ -39,8 +39,10 @@ def test_symbol_header_and_makefile(lib):
     assert len(hip.SIGNATURES["cfp_tof_zone_consistency"][1]) == 21
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert " zone_consistency.hip " in mk
-    deps = {l.split(":")[1].strip(): l.split(":")[0].split() for l in mk.splitlines() if l.endswith((": metrics_pred.h", ": tof_cluster.h"))}
+    deps = {l.split(":")[1].strip(): l.split(":")[0].split() for l in mk.splitlines()
+            if l.endswith((": metrics_pred.h", ": tof_cluster.h", ": zone_core.h"))}
     assert "zone_consistency.o" in deps["metrics_pred.h"] and sorted(deps["tof_cluster.h"]) == ["tof_sim.o", "zone_consistency.o"]
+    assert sorted(deps["zone_core.h"]) == ["zone_consistency.o", "zone_loss.o"]
     assert metrics.ZONE_CONSISTENCY_NAMES == R.NAMES and tof.BIN_WIDTH == R.BIN_WIDTH
 
 
@@ -48,14 +50,17 @@ def test_the_sensor_model_is_included_not_restated():
     sim = open(os.path.join(CSRC, "tof_sim.hip")).read()
     new = open(os.path.join(CSRC, "zone_consistency.hip")).read()
     head = open(os.path.join(CSRC, "tof_cluster.h")).read()
+    core = open(os.path.join(CSRC, "zone_core.h")).read()      # what the metric shares with the loss; the metric reaches both headers through it
+    assert '#include "tof_cluster.h"' in sim and '#include "zone_core.h"' in new and '#include "tof_cluster.h"' in core
     for src in (sim, new):
-        assert '#include "tof_cluster.h"' in src
         for call in ("tof_bin(", "tof_hist_add(", "tof_cluster(", "tof_moments("):
             assert call in src, call
+    for src in (sim, new, core):
         for restated in ("1e-9f", "atomicMax(", "__ffsll(", "max_d - 0.f", "sqrt(var"):        # each lives in the header alone
             assert restated not in src and restated in head, restated
-    assert '#include "metrics_pred.h"' in new and "met_pred(" in new and "clipf(" not in new          # the depth is included, not restated
-    adds = [l for l in new.splitlines() + head.splitlines() if "atomicAdd(" in l]
+    assert '#include "metrics_pred.h"' in core and "met_pred(" in new and "met_pred(" in core and "zc_span(" in core
+    assert "clipf(" not in new and "clipf(" not in core                                                # the depth is included, not restated
+    adds = [l for l in new.splitlines() + core.splitlines() + head.splitlines() if "atomicAdd(" in l]
     assert len(adds) == 2
     for line in adds:                                     # integer LDS counters only: no global and no floating-point atomic
         assert "&sWindow" in line or "&cnt[" in line, line
@@ -75,30 +80,7 @@ def test_entry_point_refuses_bad_arguments_with_a_message(lib):
     for name in ("pred", "rect", "mask", "raw", "zone", "summary"):
         rc, msg = call(**{name: 0})
         assert rc == EINVAL and "cfp_tof_zone_consistency: null pointer" in msg, (name, rc, msg)
-    for kw in (dict(b=0), dict(h=0), dict(w=-1), dict(hp=0), dict(wp=-3), dict(z=0), dict(z=-2)):
-        rc, msg = call(**kw)
-        assert rc == ESHAPE and "non-positive" in msg, (kw, rc, msg)
-    for kw in (dict(h=70000, w=70000, interp=1), dict(hp=70000, wp=70000, interp=1)):
-        rc, msg = call(**kw)
-        assert rc == ESHAPE and "too large" in msg, (kw, rc, msg)
-    for kw in (dict(hp=4, wp=4), dict(hp=8, wp=4), dict(h=16, w=16)):
-        rc, msg = call(**kw)
-        assert rc == ESHAPE and "sizes differ" in msg, (kw, rc, msg)
-    for lo, hi in ((2.0, 1.0), (1.0, 1.0), (float("nan"), 1.0), (0.0, float("nan"))):
-        rc, msg = call(lo=lo, hi=hi)
-        assert rc == EINVAL and "empty depth range" in msg, (lo, hi, rc, msg)
-    for bins in (0, -1, 1025):
-        rc, msg = call(bins=bins)
-        assert rc == ESHAPE and "bins must be in 1..1024" in msg, (bins, rc, msg)
-    for kw in (dict(md=0.0), dict(md=-1.0), dict(md=float("nan")), dict(bw=0.0), dict(bw=float("nan")), dict(floor=-1)):
-        rc, msg = call(**kw)
-        assert rc == EINVAL and "bad histogram parameters" in msg, (kw, rc, msg)
-    rc, msg = call(b=1 << 16, z=1 << 15)
-    assert rc == ESHAPE and "too many zones" in msg
-    # the order of the kinds: a null pointer before a dimension before the sizes before the range before the histogram before B * Z
-    assert "null pointer" in call(pred=0, b=0)[1] and "non-positive" in call(b=0, hp=4)[1] and "sizes differ" in call(hp=4, lo=2.0, hi=1.0)[1]
-    assert "empty depth range" in call(lo=2.0, hi=1.0, bins=0)[1] and "bins must be" in call(bins=0, md=0.0)[1]
-    assert "bad histogram" in call(md=0.0, b=1 << 16, z=1 << 15)[1]
+    check_shared_refusals("cfp_tof_zone_consistency", call)       # dimensions, sizes, range, bins, histogram, B * Z, and their order
     with pytest.raises(RuntimeError, match="cfp_tof_zone_consistency failed"):
         hip.call("cfp_tof_zone_consistency", P, 4, 4, 8, 8, 1, 0, 1e-3, 10.0, P, P, P, 4, 4.0, 100, 0.04, 20, P, P, 0, 0)
 
@@ -110,8 +92,9 @@ def test_python_api_refuses_before_anything_runs():
     assert list(sig.parameters) == ["pred", "raw_data", "rect_data", "mask", "lo", "hi", "size", "max_distance", "floor_count", "dev_map"]
     assert sig.parameters["size"].default is None and sig.parameters["max_distance"].default == 4.0
     assert sig.parameters["floor_count"].default == tof.AMBIENT_FLOOR == 20 and sig.parameters["dev_map"].default is False
-    src = inspect.getsource(metrics.zone_consistency)
-    assert "int(md / tof.BIN_WIDTH)" in src and "raw_data.to(torch.float64)" in src
+    src = inspect.getsource(tof.zone_inputs)               # the checks and conversions the metric shares with the loss
+    assert "tof.zone_inputs(" in inspect.getsource(metrics.zone_consistency) and "tof.BIN_WIDTH" in inspect.getsource(metrics.zone_consistency)
+    assert "int(md / BIN_WIDTH)" in src and "raw_data.to(torch.float64)" in src
     host = torch.ones(1, 4, 6)
     for bad in (host, host.double(), np.ones((1, 4, 6), np.float32)):
         with pytest.raises(ValueError, match="float32 device tensor"):

@@ -8,10 +8,10 @@ import pytest
 import torch
 
 import zone_loss_ref as R
+from zone_abi_cases import EINVAL, ESHAPE, check_shared_refusals
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "cfpnet_amd", "csrc")
-EINVAL, ESHAPE = -1, -2
 
 
 @pytest.fixture(scope="module")
@@ -53,13 +53,19 @@ def test_symbol_binding_makefile_and_shared_code(lib):
     assert len(hip.SIGNATURES["cfp_tof_zone_loss"][1]) == 26
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert " zone_loss.hip " in mk and re.search(r"^zone_loss\.o:.*tof_cluster\.h", mk, flags=re.M) and re.search(r"^zone_loss\.o:.*metrics_pred\.h", mk, flags=re.M)
+    assert re.search(r"^zone_consistency\.o zone_loss\.o: zone_core\.h$", mk, flags=re.M)
     src = open(os.path.join(CSRC, "zone_loss.hip")).read()
-    assert '#include "metrics_pred.h"' in src and '#include "tof_cluster.h"' in src
-    for call in ("met_pred(", "tof_bin(", "tof_hist_add(", "tof_cluster(", "zc_span("):               # the metric's bits: included, not restated
+    core = open(os.path.join(CSRC, "zone_core.h")).read()   # what it shares with the metric; both headers reach it through the core
+    assert '#include "zone_core.h"' in src and '#include "metrics_pred.h"' in core and '#include "tof_cluster.h"' in core
+    for call in ("met_pred(", "tof_bin(", "tof_hist_add(", "tof_cluster(", "ZoneSweep sweep(", "zone_args("):   # the metric's bits: included, not restated
         assert call in src, call
+    metric = open(os.path.join(CSRC, "zone_consistency.hip")).read()
+    for shared in ("zc_span(", "npx - 1", "__ballot(keep)", "non-positive dimension", "met_params("):   # the sweep, the staging and the checks: once
+        assert shared in core and shared not in src and shared not in metric, shared
     for restated in ("clipf(", "atomicMax(", "__ffsll(", "max_d - 0.f", "ceilf(a)"):
-        assert restated not in src, restated
-    assert "atomicAdd(" not in src and "atomicExch(" not in src and "atomicCAS(" not in src          # its only atomics are tof_cluster.h's, on LDS integers
+        assert restated not in src and restated not in core, restated
+    for atomic in ("atomicAdd(", "atomicExch(", "atomicCAS("):                                        # its only atomics are tof_cluster.h's, on LDS integers
+        assert atomic not in src and atomic not in core, atomic
     assert train_ops.ZONE_LOSS_COLUMNS == R.COLUMNS and tof.BIN_WIDTH == R.BIN_WIDTH
     assert lib.cfp_tof_zone_loss_ws_bytes(2, 9, 100) == 2 * 9 * 100 * 8
 
@@ -80,25 +86,12 @@ def test_entry_point_refuses_bad_arguments_with_a_message(lib):
     for name in ("pred", "rect", "mask", "raw", "ws", "zone", "out"):
         rc, msg = call(**{name: 0})
         assert rc == EINVAL and "cfp_tof_zone_loss: null pointer" in msg, (name, rc, msg)
-    for kw in (dict(b=0), dict(h=0), dict(w=-1), dict(hp=0), dict(wp=-3), dict(z=0), dict(z=-2)):
-        rc, msg = call(**kw)
-        assert rc == ESHAPE and "non-positive" in msg, (kw, rc, msg)
-    for kw in (dict(h=70000, w=70000, interp=1), dict(hp=70000, wp=70000, interp=1)):
-        rc, msg = call(**kw)
-        assert rc == ESHAPE and "too large" in msg, (kw, rc, msg)
-    for kw in (dict(hp=4, wp=4), dict(hp=8, wp=4), dict(h=16, w=16)):
-        rc, msg = call(**kw)
-        assert rc == ESHAPE and "interpolate is off" in msg, (kw, rc, msg)
-    for kw in (dict(lo=10.0, hi=10.0), dict(lo=5.0, hi=1.0), dict(lo=float("nan"))):
-        rc, msg = call(**kw)
-        assert rc == EINVAL and "empty depth range" in msg, (kw, rc, msg)
+    check_shared_refusals("cfp_tof_zone_loss", call)      # dimensions, sizes, range, bins, histogram, B * Z, and their order
     for bins in (0, -1, 1025):
-        rc, msg = call(bins=bins)
-        assert rc == ESHAPE and "1..1024" in msg, (bins, rc, msg)
         assert lib.cfp_tof_zone_loss_ws_bytes(1, 4, bins) == 0
-    for kw in (dict(md=0.0), dict(md=float("nan")), dict(bw=0.0), dict(floor=-1)):
-        rc, msg = call(**kw)
-        assert rc == EINVAL and "bad histogram parameters" in msg, (kw, rc, msg)
+    # its own two come after the histogram parameters and before B * Z
+    assert "delta must be" in call(delta=0.0, acc=2)[1] and "bad histogram" in call(md=0.0, delta=0.0)[1]
+    assert "accumulate" in call(acc=2, b=1 << 16, z=1 << 15)[1]
     for delta in (0.0, -0.04, float("nan"), float("inf")):
         rc, msg = call(delta=delta)
         assert rc == EINVAL and "delta must be positive" in msg, (delta, rc, msg)
