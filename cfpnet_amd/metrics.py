@@ -16,6 +16,8 @@ ground-truth depth, both formed as `pointcloud.unproject` forms them (`cfp_norma
 
 `zone_consistency` / `RunningZoneConsistency` need no ground truth: the ToF zones are re-simulated from the prediction with the sensor
 model of `tof.TofSimulator` and compared with the measured (mu, sigma) per zone (`cfp_tof_zone_consistency`, `csrc/zone_consistency.hip`).
+
+`temporal_consistency` compares two consecutive predictions after the first is warped into the second's view (`cfpnet_amd/temporal.py`).
 """
 from __future__ import annotations
 
@@ -385,3 +387,22 @@ class RunningZoneConsistency:
 
     def tables(self):
         return [t for z in self._zones for t in z.cpu().tolist()]
+
+
+TEMPORAL_CONSISTENCY_NAMES = ("mean_abs", "rmse", "coverage")
+
+
+def temporal_consistency(prev: torch.Tensor, cur: torch.Tensor, intrinsics, pose, lo: float, hi: float, size=None) -> torch.Tensor:
+    """How well two consecutive predictions agree once the first is carried into the second's view: `prev`, `cur` [B,h,w] /
+    [B,1,h,w] f32 on the device, `intrinsics` and `size` as in `pointcloud.unproject`, `pose` = [R|t] from the previous camera frame to
+    the current one (None: the camera did not move) -> [B,3] f64 in `TEMPORAL_CONSISTENCY_NAMES` order: the mean |difference| and the
+    RMSE in metres over the pixels of the H x W grid where the warped `prev` and `cur` are both known, and the share of the grid the
+    warped `prev` covers.  A thin wrapper over `temporal.reproject` and `temporal.fuse` (its `stats` and `counts`); NaN for an image
+    without a common pixel.  No host synchronisation."""
+    from . import temporal
+    warped, _ = temporal.reproject(prev, intrinsics, pose, size=size, lo=lo, hi=hi, splat=1)
+    B, H, W = warped.shape
+    one = torch.ones(B, 1, 1, dtype=torch.float32, device=warped.device)      # the gate and the variances play no part in `stats`
+    _, _, counts, stats = temporal.fuse(cur, one, warped, torch.zeros_like(warped), lo=lo, hi=hi)
+    n = (counts[:, 1] + counts[:, 2]).to(torch.float64)                       # fused + rejected: both known
+    return torch.stack([stats[:, 0] / n, torch.sqrt(stats[:, 1] / n), counts[:, 0].to(torch.float64) / float(H * W)], 1)

@@ -58,6 +58,12 @@ line, `Robustness: {"drop": {"0.25": {...}}, "sigma": {...}}` (JSON; the nine me
 `<save_dir>/robustness.json` holds the same with the mean counts per image of valid zones, zones dropped and zones noised.  A listed value of
 0 reproduces the `Metrics:` line.  The other lines do not change.
 
+`--robust_frames N` (N >= 2, with `--robust_drop` or `--robust_sigma`) asks how much of a degradation fusing N frames recovers: every
+degraded run is repeated with N - 1 further draws of the same degradation (frame 0 is the draw above, frame f is keyed by the index of the
+batch + f * 2^20), the N predictions and their standard-deviation planes go through a `temporal.TemporalFilter` with the identity pose
+(`cfp_depth_reproject`, `cfp_depth_fuse`) and the fused frame is evaluated like a prediction.  The `Robustness:` line and
+`robustness.json` gain one key, `"fused": {"frames": N, "drop": {...}, "sigma": {...}}`; without the switch nothing changes.
+
 `--save_pred`, `--save_gt`, `--save_rgb`, `--save_error_map` and `--save_for_demo` (the reference's picture switches) paint on the device
 (`cfpnet_amd/render.py`: `cfp_render_depth`, `cfp_render_zones`, `cfp_render_rgb`) and write, per evaluated image index i, into `--save_dir D`
 (default `tmp`): `D/pred_<i>.png` (colour) and `D/pred_<i>_mm.png` (16-bit millimetres of the clipped, enlarged prediction the metrics
@@ -145,6 +151,11 @@ def main(argv=None):
     if any(not 0.0 <= v <= 1.0 for v in robust["drop"]):
         raise ValueError("--robust_drop takes fractions in [0, 1]")
     robust_seed = ROBUST_SEED if robust_seed is None else robust_seed
+    robust_frames = _pop(argv, "--robust_frames", None, int)
+    if robust_frames is not None and robust_frames < 2:
+        raise ValueError(f"--robust_frames takes N >= 2, got {robust_frames}")
+    if robust_frames is not None and not (robust["drop"] or robust["sigma"]):
+        raise ValueError("--robust_frames needs --robust_drop or --robust_sigma")
     if not save_points and (points_stride is not None or points_max_std is not None or points_normals or
                             (intrinsics is not None and not normal_metrics)):
         raise ValueError("--points_stride, --points_max_std, --points_normals and --intrinsics need --save_points"
@@ -214,6 +225,10 @@ def main(argv=None):
     want_std = save_points and points_max_std is not None
     robust_runs = [(kind, v, metrics.RunningAverageDict()) for kind in ("drop", "sigma") for v in robust[kind]]
     robust_counts = {(kind, v): torch.zeros(3, dtype=torch.int64, device=device) for kind, v, _ in robust_runs}
+    if robust_frames:
+        from cfpnet_amd import pointcloud as _pc, temporal
+        fused_avg = {(kind, v): metrics.RunningAverageDict() for kind, v, _ in robust_runs}
+        fuser = None
     n_batch = 0
     n_img, t0 = 0, time.perf_counter()
     with torch.no_grad():
@@ -280,7 +295,10 @@ def main(argv=None):
                 deg = dict(drop=value, seed=robust_seed, step=n_batch) if kind == "drop" else \
                     dict(sigma=value, prob=1.0, mean=0.0, seed=robust_seed, step=n_batch)
                 r_inp, _ = build(img, dep, degrade=deg)
-                _, r_pred, _, _ = model(r_inp)
+                if robust_frames:
+                    _, r_pred, _, r_unc = model(r_inp, return_uncertainty=True)
+                else:
+                    _, r_pred, _, _ = model(r_inp)
                 if area is not None:
                     r_add = r_inp["additional"]
                     r_avg.update(metrics.region_metrics(r_pred, gt, float(args.min_depth), float(args.max_depth), r_add["rect_data"], r_add["mask"],
@@ -288,6 +306,23 @@ def main(argv=None):
                 else:
                     r_avg.update(metrics.eval_metrics(r_pred, gt, float(args.min_depth), float(args.max_depth), mode=metrics.EVALUATE_ALL))
                 robust_counts[kind, value] = robust_counts[kind, value] + build.last_counts.sum(0)
+                if robust_frames:                            # further draws of the same degradation, fused with the identity pose
+                    if fuser is None:
+                        fuser = temporal.TemporalFilter(intrinsics or _pc.ZJUL5_INTRINSICS, size=gt.shape[-2:], lo=float(args.min_depth),
+                                                        hi=float(args.max_depth))
+                    fuser.reset()
+                    f_pred, _ = fuser.update(r_pred, r_unc)
+                    for f in range(1, robust_frames):
+                        f_inp, _ = build(img, dep, degrade=dict(deg, step=n_batch + f * 2 ** 20))
+                        _, n_pred, _, n_unc = model(f_inp, return_uncertainty=True)
+                        f_pred, _ = fuser.update(n_pred, n_unc)
+                    if area is not None:
+                        fused_avg[kind, value].update(metrics.region_metrics(f_pred, gt, float(args.min_depth), float(args.max_depth),
+                                                                             r_add["rect_data"], r_add["mask"], range_edges,
+                                                                             mode=metrics.EVALUATE_ALL)[:, area, 0])
+                    else:
+                        fused_avg[kind, value].update(metrics.eval_metrics(f_pred, gt, float(args.min_depth), float(args.max_depth),
+                                                                           mode=metrics.EVALUATE_ALL))
             n_img += img.shape[0]
             n_batch += 1
     torch.cuda.synchronize()
@@ -341,6 +376,11 @@ def main(argv=None):
         for kind, v, r_avg in robust_runs:
             line[kind][f"{v:g}"] = {k: round(x, 3) for k, x in r_avg.get_value().items()}
             full[kind][f"{v:g}"] = {"metrics": line[kind][f"{v:g}"], "counts": [c / max(n_img, 1) for c in robust_counts[kind, v].cpu().tolist()]}
+        if robust_frames:
+            line["fused"] = {"frames": robust_frames, "drop": {}, "sigma": {}}
+            for kind, v, _ in robust_runs:
+                line["fused"][kind][f"{v:g}"] = {k: round(x, 3) for k, x in fused_avg[kind, v].get_value().items()}
+            full["fused"] = line["fused"]
         print("Robustness: " + json.dumps(line))
         os.makedirs(args.save_dir, exist_ok=True)
         with open(os.path.join(args.save_dir, "robustness.json"), "w") as f:

@@ -745,6 +745,63 @@ int cfp_points_compact(const float* points, const float* normals, int H, int W, 
                        float* out_points /* [B][cap][3] */, float* out_normals /* [B][cap][3] or NULL */,
                        int* out_index /* [B][cap] */, int* counts /* [B] */, void* ws, size_t ws_bytes, cfp_stream_t stream);
 
+/* Forward warp of the prediction into another view, with a z-buffer, without leaving the device: the previous frame's depth carried into
+ * the current camera (temporal fusion), or the completed depth seen from the ToF sensor or a second camera (RGB-D registration).
+ *   Inputs  pred [B,Hp,Wp] f32; H, W, interpolate, lo < hi as cfp_depth_unproject (a full-resolution state goes in with Hp == H,
+ *           interpolate = 0 and infinite bounds); K_src, K_dst [B][4] f32 ON THE DEVICE: (fx, fy, cx, cy) of the H x W source grid and of
+ *           the Hd x Wd target grid, under the caller contract of cfp_depth_unproject; T [B][12] f32 ON THE DEVICE: row-major [R|t],
+ *           P' = R P + t in the camera frame of cfp_depth_unproject (x right, y down, z forward); splat 1 or 2; z_near > 0.
+ *   Source  d = d(x, y) of cfp_depth_unproject (csrc/metrics_pred.h, bit for bit).  A source whose d is not finite, or d <= 0, is skipped.
+ *   Point   float32, in this order of operations (no fused multiply-add):
+ *             X = ((float)x - cx) / fx * d     Y = ((float)y - cy) / fy * d     Z = d
+ *             X' = (T[0] * X + T[1] * Y) + T[2] * Z + T[3]      Y' likewise with T[4..7], Z' with T[8..11]   (left to right)
+ *           A point is skipped unless Z' is finite and Z' >= z_near.  Then  u = fx' * (X' / Z') + cx',  v = fy' * (Y' / Z') + cy'.
+ *   Splat   splat = 1 hits the pixel (floorf(u + 0.5f), floorf(v + 0.5f)); splat = 2 hits the four pixels floorf(u) + {0, 1},
+ *           floorf(v) + {0, 1}, which closes the cracks of a mild magnification.  A hit outside 0 <= column < Wd, 0 <= row < Hd is dropped;
+ *           the test is made on the float values, before any conversion to int (a NaN or huge u, v hits nothing).
+ *   Z-buffer  one 64-bit unsigned atomic minimum per hit on ws[b][row][column], with the key (bits(Z') << 32) | (y * W + x): positive
+ *           floats order like their bits, so the nearest surface wins and a tie in depth goes to the lowest source index.  An integer
+ *           minimum does not depend on the order of arrival: two calls on the same tensors give identical bits.
+ *   Outputs depth_out [B,Hd,Wd] f32 = Z' of the winning key, index_out [B,Hd,Wd] i32 = its source y * W + x; a pixel nothing hit gets NaN
+ *           and -1.  plane_out [B,Hd,Wd] f32 (given exactly when plane is): a map that travels with the depth (a variance or std map) --
+ *           plane points to image 0's Hu x Wu f32, image b's lies plane_stride ELEMENTS further, brought to the H x W grid like the
+ *           uncertainty plane of cfp_points_compact -- read at the winning source pixel; NaN where nothing hit.
+ * Three launches (fill the workspace with all ones, splat, resolve) on `stream`, no host synchronisation, no allocation.  Workspace of
+ * cfp_depth_reproject_ws_bytes(B, Hd, Wd) = 8 bytes per target pixel, 8-byte aligned; 0 for a non-positive argument. */
+size_t cfp_depth_reproject_ws_bytes(int B, int Hd, int Wd);
+int cfp_depth_reproject(const float* pred, int Hp, int Wp, int H, int W, int B, int interpolate, float lo, float hi,
+                        const float* K_src /* device, [B][4] */, const float* T /* device, [B][12] */,
+                        const float* K_dst /* device, [B][4] */, int Hd, int Wd, int splat, float z_near,
+                        const float* plane /* or NULL */, int Hu, int Wu, long long plane_stride, float* depth_out /* [B][Hd][Wd] */,
+                        int* index_out /* [B][Hd][Wd] */, float* plane_out /* [B][Hd][Wd] or NULL */, void* ws, size_t ws_bytes,
+                        cfp_stream_t stream);
+
+/* Fusion of the current prediction with a prior on the same grid (the previous state warped by cfp_depth_reproject) by their variances,
+ * per pixel, with a gate that keeps a changed scene or an uncovered surface from being averaged away.
+ *   Inputs  cur [B,Hp,Wp] f32; H, W, interpolate, lo < hi as cfp_depth_unproject; cur_std: image 0's Hu x Wu f32 plane, image b's
+ *           std_stride ELEMENTS further, brought to H x W like the plane of cfp_depth_reproject; std_floor > 0; prior_depth, prior_var
+ *           [B,H,W] f32; process_var >= 0 (what the prior's variance grows by per step); gate_k >= 0, gate_abs >= 0.
+ *   Pixel   float32, in this order:  c = d(x, y);  s = the std plane at the pixel, sf = s > std_floor ? s : std_floor (a NaN s gives
+ *           the floor), vc = sf * sf;  p = prior_depth, vp0 = prior_var: the prior is PRESENT iff both are finite;  vp = vp0 + process_var.
+ *             c finite, prior absent                                    -> (c, vc)
+ *             c not finite, prior present                               -> (p, vp)                                      counted FILLED
+ *             c not finite, prior absent                                -> (NaN, +inf)
+ *             both, |p - c| > gate_k * sqrtf(vc + vp) + gate_abs        -> (c, vc)                                      counted REJECTED
+ *             both, inside the gate:  w = vc / (vc + vp)                -> (c + w * (p - c), (vc * vp) / (vc + vp))     counted FUSED
+ *   Outputs out_depth, out_var [B,H,W] f32 (they may be prior_depth, prior_var themselves: a pixel is read before it is written); counts [B][4] i32 = {prior present, fused, rejected, filled};
+ *           stats [B][2] f64 = {sum |p - c|, sum (p - c)^2} over the pixels where both are present, before the gate: float32 terms
+ *           ((p - c) * (p - c) rounded once), float64 sums -- the temporal consistency of two consecutive frames.
+ * Two launches: per-workgroup partial sums into the workspace, then one workgroup per image finishes them in a fixed order; no
+ * floating-point atomics: two calls on the same tensors give identical bits.  No host synchronisation, no allocation.  Workspace of
+ * cfp_depth_fuse_ws_bytes(B, H, W) bytes, 8-byte aligned; 0 for a non-positive argument. */
+enum { CFP_FUSE_PRIOR = 0, CFP_FUSE_FUSED, CFP_FUSE_REJECTED, CFP_FUSE_FILLED };
+size_t cfp_depth_fuse_ws_bytes(int B, int H, int W);
+int cfp_depth_fuse(const float* cur, int Hp, int Wp, int H, int W, int B, int interpolate, float lo, float hi, const float* cur_std,
+                   int Hu, int Wu, long long std_stride, float std_floor, const float* prior_depth /* [B][H][W] */,
+                   const float* prior_var /* [B][H][W] */, float process_var, float gate_k, float gate_abs,
+                   float* out_depth /* [B][H][W] */, float* out_var /* [B][H][W] */, int* counts /* [B][4] */,
+                   double* stats /* [B][2] */, void* ws, size_t ws_bytes, cfp_stream_t stream);
+
 /* Surface-normal error of the predicted geometry against the ground truth's, per image, without leaving the device: the standard set of
  * the normal-estimation literature (mean, median and RMSE of the angle, share of pixels below 11.25, 22.5 and 30 degrees).
  *   Inputs  pred [B,Hp,Wp] f32 and gt [B,H,W] f32 (device); interpolate, lo < hi exactly as cfp_eval_metrics in mode 0; K [B][4] f32 ON
