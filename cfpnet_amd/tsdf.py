@@ -1,0 +1,149 @@
+"""A world-anchored map on the device: what room-scale reconstruction does with streaming ToF depth completion.
+
+`temporal.TemporalFilter` keeps a per-pixel state that follows the camera; whatever leaves the image is forgotten and every warp
+re-samples it.  `TsdfVolume` keeps a truncated signed distance field in a fixed world frame instead: `integrate` fuses a prediction and
+its std map into the voxels the camera sees (`cfp_tsdf_integrate`: the per-voxel weight is the inverse-variance sum `fuse` keeps per
+pixel), `raycast` turns the volume back into depth, std and normals in any view (`cfp_tsdf_raycast`), so two views combine into
+something a third can look at.  The arithmetic is `csrc/tsdf.hip` (definition in include/cfpnet_hip.h); nothing here
+computes on the CPU.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional, Sequence
+
+import torch
+
+from . import hip
+from .pointcloud import _check_out, _intrinsics, _pred3, _size
+from .temporal import _pose, _std_plane
+
+COUNT_NAMES = ("seen", "updated", "behind")           # columns of `counts` (CFP_TSDF_*)
+_F32_MAX = 3.4028234663852886e38                      # the library wants a finite cap: "no cap" is the largest float32
+
+
+def _positive(v, what: str) -> float:
+    v = float(v)
+    if not (v > 0.0 and math.isfinite(v)):
+        raise ValueError(f"{what} must be positive and finite, got {v}")
+    return v
+
+
+class TsdfVolume:
+    """A TSDF of `dims` = (Dx, Dy, Dz) voxels of edge `voxel` metres per image; voxel (i, j, k) has its centre at `origin` + voxel *
+    (i, j, k) in the world frame.  `.volume` [B,Dz,Dy,Dx,2] f32 holds (F, Wt) per voxel: F the signed distance to the surface over
+    `trunc` (3 * voxel by default), clipped at 1 in front, and Wt the sum of 1 / std^2 of what was fused, capped at `w_max` (None: no
+    cap); empty is (1, 0).  `intrinsics`: (fx, fy, cx, cy) of the H x W grid the predictions are seen on, or a float32 [B,4] tensor;
+    `size` = (H, W), twice the prediction by default.  A pose is [R|t], camera-from-world (Pc = R Pw + t), in every form
+    `TemporalFilter.update` takes; None is the identity.  The volume, the counts and the raycast's outputs are allocated once and
+    reused; nothing synchronises with the host: with a float32 device pose, `integrate` followed by `raycast` can be captured in a
+    graph."""
+
+    def __init__(self, dims: Sequence[int], voxel: float, origin: Sequence[float], intrinsics, size: Optional[Sequence[int]] = None,
+                 trunc: Optional[float] = None, w_max: Optional[float] = None, lo: float = 1e-3, hi: float = 10.0,
+                 std_floor: float = 1e-3, z_near: float = 1e-3):
+        try:
+            Dx, Dy, Dz = (int(v) for v in dims)
+        except (TypeError, ValueError):
+            raise ValueError(f"dims must be (Dx, Dy, Dz), got {dims!r}") from None
+        if min(Dx, Dy, Dz) < 1 or Dx * Dy * Dz >= 2 ** 31 - 256:
+            raise ValueError(f"dims must be positive with fewer than 2^31 voxels, got {(Dx, Dy, Dz)}")
+        try:
+            ox, oy, oz = (float(v) for v in origin)
+        except (TypeError, ValueError):
+            raise ValueError(f"origin must be (ox, oy, oz), got {origin!r}") from None
+        if not all(math.isfinite(v) for v in (ox, oy, oz)):
+            raise ValueError(f"origin must be finite, got {(ox, oy, oz)}")
+        self.dims, self.origin = (Dx, Dy, Dz), (ox, oy, oz)
+        self.voxel = _positive(voxel, "voxel")
+        self.trunc = 3.0 * self.voxel if trunc is None else _positive(trunc, "trunc")
+        if w_max is None or float(w_max) == math.inf:
+            self.w_max = _F32_MAX
+        else:
+            self.w_max = _positive(w_max, "w_max")
+        if not float(lo) < float(hi):
+            raise ValueError(f"empty depth range [{lo}, {hi}]")
+        self.lo, self.hi = float(lo), float(hi)
+        self.std_floor, self.z_near = _positive(std_floor, "std_floor"), _positive(z_near, "z_near")
+        if not isinstance(intrinsics, torch.Tensor):
+            _intrinsics(intrinsics, 1, "cpu")                             # refuse bad numbers now, not at the first frame
+        self.intrinsics, self.size = intrinsics, size
+        self.volume = self.counts = None
+        self._shape = None
+        self._rays = {}
+
+    def reset(self):
+        """Empty the volume: F = 1, Wt = 0.  The buffers stay."""
+        if self.volume is not None:
+            self.volume[..., 0] = 1.0
+            self.volume[..., 1] = 0.0
+
+    def _allocate(self, B, h, w, dev):
+        Dx, Dy, Dz = self.dims
+        self._shape = (B, h, w)
+        self._hw = _size(self.size, h, w)
+        self._K = _intrinsics(self.intrinsics, B, dev)
+        self.volume = torch.empty(B, Dz, Dy, Dx, 2, dtype=torch.float32, device=dev)
+        self.counts = torch.zeros(B, 3, dtype=torch.int32, device=dev)
+        self._rays = {}
+        self.reset()
+
+    def integrate(self, pred: torch.Tensor, unc: Optional[torch.Tensor] = None, pose=None) -> torch.Tensor:
+        """pred [B,h,w] / [B,1,h,w] f32 on the device and its uncertainty (the model's [B,3,h,w] tensor or a [B,hu,wu] std map; None:
+        every observation weighs 1), seen from `pose` -> counts [B,3] i32 in `COUNT_NAMES` order, on the device: the voxels that saw a
+        valid depth, that were updated, that lie more than `trunc` behind the surface.  The first call allocates the volume (empty);
+        a call with another batch or prediction size starts a new one."""
+        pred = _pred3(pred)
+        B, h, w = pred.shape
+        std = None if unc is None else _std_plane(unc, B)
+        if self._shape != (B, h, w):
+            self._allocate(B, h, w, pred.device)
+        H, W = self._hw
+        Dx, Dy, Dz = self.dims
+        T = _pose(pose, B, pred.device)
+        hip.call("cfp_tsdf_integrate", pred.data_ptr(), h, w, H, W, B, int((h, w) != (H, W)), self.lo, self.hi, hip.ptr(std),
+                 0 if std is None else std.shape[1], 0 if std is None else std.shape[2], 0 if std is None else std.stride(0),
+                 self.std_floor, self._K.data_ptr(), T.data_ptr(), self.volume.data_ptr(), Dx, Dy, Dz, *self.origin, self.voxel,
+                 self.trunc, self.z_near, self.w_max, self.counts.data_ptr(), hip.current_stream())
+        return self.counts
+
+    def raycast(self, pose=None, intrinsics=None, size: Optional[Sequence[int]] = None, t_range: Optional[Sequence[float]] = None,
+                step: Optional[float] = None, normals: bool = True, out=None):
+        """The volume seen from `pose` by the camera `intrinsics` / `size` = (Hd, Wd) (the integrating camera's by default) -> (depth
+        [B,Hd,Wd] f32, std [B,Hd,Wd] f32) or, with `normals`, (depth, std, normals [B,Hd,Wd,3] f32 in the camera frame, facing the
+        camera like `unproject`'s).  Rays are marched from t_range[0] to t_range[1] ((z_near, hi) by default) in camera depth, every
+        `step` (trunc / 2 by default); NaN where a ray meets no surface or leaves what was observed.  The depth is metric depth on the
+        (Hd, Wd) grid: it goes straight into `pointcloud.point_cloud(depth, K, size=(Hd, Wd), lo=-inf, hi=inf)`.  The results of a
+        view of one size are the volume's own buffers, overwritten by the next raycast of that size; `out`: the tuple of an earlier
+        call to write into.  Bitwise reproducible; no host synchronisation."""
+        if self.volume is None:
+            raise ValueError("nothing was integrated yet: the volume is allocated by the first integrate")
+        B = self.volume.shape[0]
+        dev = self.volume.device
+        Hd, Wd = self._hw if size is None else _size(size, 1, 1)
+        K = self._K if intrinsics is None else _intrinsics(intrinsics, B, dev)
+        t0, t1 = (self.z_near, self.hi) if t_range is None else (float(v) for v in t_range)
+        if not (t0 < t1 and math.isfinite(t0) and math.isfinite(t1)):
+            raise ValueError(f"t_range must be finite with t_min < t_max, got {(t0, t1)}")
+        step = 0.5 * self.trunc if step is None else _positive(step, "step")
+        want = 3 if normals else 2
+        if out is not None:
+            if not isinstance(out, (tuple, list)) or len(out) != want:
+                raise ValueError("out must be (depth, std) or, with normals, (depth, std, normals)")
+            out = tuple(out)
+        else:
+            out = self._rays.get((Hd, Wd, bool(normals)))
+            if out is None:
+                out = (torch.empty(B, Hd, Wd, dtype=torch.float32, device=dev), torch.empty(B, Hd, Wd, dtype=torch.float32, device=dev))
+                if normals:
+                    out += (torch.empty(B, Hd, Wd, 3, dtype=torch.float32, device=dev),)
+                self._rays[(Hd, Wd, bool(normals))] = out
+        _check_out(out[0], (B, Hd, Wd), torch.float32, "out depth")
+        _check_out(out[1], (B, Hd, Wd), torch.float32, "out std")
+        if normals:
+            _check_out(out[2], (B, Hd, Wd, 3), torch.float32, "out normals")
+        T = _pose(pose, B, dev)
+        Dx, Dy, Dz = self.dims
+        hip.call("cfp_tsdf_raycast", self.volume.data_ptr(), Dx, Dy, Dz, B, *self.origin, self.voxel, K.data_ptr(), T.data_ptr(), Hd, Wd,
+                 t0, t1, step, out[0].data_ptr(), out[2].data_ptr() if normals else 0, out[1].data_ptr(), hip.current_stream())
+        return out

@@ -802,6 +802,70 @@ int cfp_depth_fuse(const float* cur, int Hp, int Wp, int H, int W, int B, int in
                    float* out_depth /* [B][H][W] */, float* out_var /* [B][H][W] */, int* counts /* [B][4] */,
                    double* stats /* [B][2] */, void* ws, size_t ws_bytes, cfp_stream_t stream);
 
+/* A world-anchored map: a truncated signed distance field (TSDF) whose per-voxel weight is the inverse-variance sum cfp_depth_fuse keeps
+ * per pixel.  cfp_tsdf_integrate fuses one frame into the volume, cfp_tsdf_raycast turns the volume back into depth, normals and std in
+ * any view.  Common to both:
+ *   Volume  float [B,Dz,Dy,Dx,2] ON THE DEVICE, 8-byte aligned: (F, Wt) per voxel, x fastest; voxel (i, j, k) has its centre at
+ *           origin + voxel * (i, j, k) in the world frame; ox, oy, oz (finite) and voxel > 0 are host floats.  Empty: F = 1, Wt = 0.
+ *   Camera  K [B][4] f32 ON THE DEVICE (fx, fy, cx, cy) under the caller contract of cfp_depth_unproject; T [B][12] f32 ON THE DEVICE:
+ *           row-major [R|t], camera-from-world, Pc = R Pw + t in the camera frame of cfp_depth_unproject (x right, y down, z forward).
+ * Float32 in the order written here, no fused multiply-add.
+ *
+ * cfp_tsdf_integrate
+ *   Inputs  pred [B,Hp,Wp] f32; H, W, interpolate, lo < hi as cfp_depth_unproject; std (NULL: every observation weighs 1): image 0's
+ *           Hu x Wu f32 plane, image b's std_stride ELEMENTS further, brought to H x W like the plane of cfp_depth_reproject;
+ *           std_floor, trunc, z_near, w_max positive and finite.
+ *   Voxel   Xw = ox + voxel * (float)i     Yw = oy + voxel * (float)j     Zw = oz + voxel * (float)k
+ *           Xc = (T[0] * Xw + T[1] * Yw) + T[2] * Zw + T[3]      Yc likewise with T[4..7], Zc with T[8..11]   (left to right)
+ *           Skipped unless Zc is finite and Zc >= z_near.  Then  u = fx * (Xc / Zc) + cx,  v = fy * (Yc / Zc) + cy  and the pixel is
+ *           (floorf(u + 0.5f), floorf(v + 0.5f)), tested against 0 <= column < W, 0 <= row < H on the float values, before any
+ *           conversion to int (a NaN or huge u, v reads nothing).  d = d(column, row) of cfp_depth_unproject (csrc/metrics_pred.h, bit
+ *           for bit); skipped unless d is finite and d > 0 -- otherwise the voxel has SEEN a valid depth.
+ *             sdf = d - Zc;  sdf < -trunc: the voxel lies BEHIND the surface, skipped;  f = fminf(1, sdf / trunc)
+ *             s = the std plane at the pixel, sf = s > std_floor ? s : std_floor (a NaN s gives the floor), w = 1 / (sf * sf);
+ *             without a plane w = 1.  An observation whose w is 0 or not finite (an infinite std) is skipped.
+ *             F' = (F * Wt + f * w) / (Wt + w)     Wt' = fminf(Wt + w, w_max)                                          UPDATED
+ *           A skipped voxel is neither read nor written.
+ *   Outputs the volume in place; counts [B][3] i32 = {valid depth seen, updated, behind the surface}, overwritten.
+ * One thread per voxel, x along the lanes.  The counts are summed as integers (per workgroup, then one integer atomic add per workgroup
+ * onto a word a first launch zeroes); no floating-point atomics: two calls on the same tensors give identical bits.  No host
+ * synchronisation, no allocation, no workspace.
+ *
+ * cfp_tsdf_raycast
+ *   Inputs  Hd x Wd: the target grid K describes; t_min < t_max, both finite; step > 0; floor((t_max - t_min) / step) < 2^24.
+ *   Ray     rx = ((float)x - cx) / fx,  ry = ((float)y - cy) / fy,  r = (rx, ry, 1): the ray parameter is the camera depth.  Samples at
+ *           t_k = t_min + (float)k * step  for  k = 0 .. floorf((t_max - t_min) / step)  (a product, not a running sum).
+ *   Point   q = (rx * t - T[3], ry * t - T[7], t - T[11]);  Pw = R^T q:  Xw = (T[0] * q.x + T[4] * q.y) + T[8] * q.z,  Yw with T[1], T[5],
+ *           T[9],  Zw with T[2], T[6], T[10];  g = ((Xw - ox) / voxel, (Yw - oy) / voxel, (Zw - oz) / voxel).
+ *   Sample  with i0 = floorf(g.x), a = g.x - i0 (j0, b and k0, c likewise): VALID iff 0 <= i0 <= Dx - 2, 0 <= j0 <= Dy - 2,
+ *           0 <= k0 <= Dz - 2 (on the float values; NaN fails) and all 8 corners have Wt > 0.  Its value is the trilinear blend, x first,
+ *           then y, then z:  c(j, k) = (1 - a) * F(i0, j, k) + a * F(i0 + 1, j, k);  e(k) = (1 - b) * c(j0, k) + b * c(j0 + 1, k);
+ *           F = (1 - c) * e(k0) + c * e(k0 + 1).  The trilinear Wt is the same blend of the weights.
+ *   Hit     the first pair of consecutive samples k - 1, k, both valid, with F_prev > 0 >= F_cur:
+ *             depth = t_prev + step * (F_prev / (F_prev - F_cur))
+ *           A consecutive valid pair with F_prev < 0 < F_cur met first is a back face: it ends the ray without a hit.  No hit: NaN.
+ *   Std     1 / sqrtf(trilinear Wt) sampled at the ray's point at t = depth; NaN without a hit or where that sample is not valid.
+ *   Normal  the central difference of the trilinear F at g +- 1 along each grid axis (+- one voxel along the world axes) at that
+ *           point, n_w = (F(g + e_x) - F(g - e_x), ...), normalised (divided by sqrtf((x * x + y * y) + z * z)) and rotated into the
+ *           camera frame, n = R n_w, rows left to right.  F falls from free space into the surface, so its gradient points out of the
+ *           surface towards the camera that saw it: the sign convention of cfp_depth_unproject's normals (n . P < 0, a fronto-parallel
+ *           wall gives (0, 0, -1)).  If one of the six samples is not valid, or the length is 0 or not finite, or there is no hit, the
+ *           normal is (NaN, NaN, NaN) -- not the (0, 0, 0) of cfp_depth_unproject: a map knows where it knows nothing.
+ *   Outputs depth [B,Hd,Wd] f32; normal [B,Hd,Wd,3] f32 or NULL; std [B,Hd,Wd] f32 or NULL.
+ * One workgroup per 16 x 16 pixel tile; (F, Wt) is read as one 8-byte value.  The march may skip steps at which the ray cannot touch the
+ * volume's box; the per-sample test still decides, so the result does not depend on it.  Reads only: bitwise reproducible.  No host
+ * synchronisation, no allocation, no workspace. */
+enum { CFP_TSDF_SEEN = 0, CFP_TSDF_UPDATED, CFP_TSDF_BEHIND };
+int cfp_tsdf_integrate(const float* pred, int Hp, int Wp, int H, int W, int B, int interpolate, float lo, float hi,
+                       const float* std /* or NULL */, int Hu, int Wu, long long std_stride, float std_floor,
+                       const float* K /* device, [B][4] */, const float* T /* device, [B][12] */,
+                       float* volume /* [B][Dz][Dy][Dx][2] */, int Dx, int Dy, int Dz, float ox, float oy, float oz, float voxel,
+                       float trunc, float z_near, float w_max, int* counts /* [B][3] */, cfp_stream_t stream);
+int cfp_tsdf_raycast(const float* volume /* [B][Dz][Dy][Dx][2] */, int Dx, int Dy, int Dz, int B, float ox, float oy, float oz,
+                     float voxel, const float* K /* device, [B][4] */, const float* T /* device, [B][12] */, int Hd, int Wd,
+                     float t_min, float t_max, float step, float* depth /* [B][Hd][Wd] */, float* normal /* [B][Hd][Wd][3] or NULL */,
+                     float* std /* [B][Hd][Wd] or NULL */, cfp_stream_t stream);
+
 /* Surface-normal error of the predicted geometry against the ground truth's, per image, without leaving the device: the standard set of
  * the normal-estimation literature (mean, median and RMSE of the angle, share of pixels below 11.25, 22.5 and 30 degrees).
  *   Inputs  pred [B,Hp,Wp] f32 and gt [B,H,W] f32 (device); interpolate, lo < hi exactly as cfp_eval_metrics in mode 0; K [B][4] f32 ON
