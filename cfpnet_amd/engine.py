@@ -144,6 +144,10 @@ class Engine:
         # Built, parity-tested and MEASURED SLOWER than the two kernels it replaces (40 vs 40 us alone at 30x40x816, 32 vs 23 us with
         # four copies side by side; whole step 2.96 vs 2.57 ms with its first version): OFF by default, CFP_MBCONV_FUSED=1 enables it.
         self.mbconv_fused = os.environ.get("CFP_MBCONV_FUSED", "0") == "1"
+        # the expand GEMM of the inverted-residual blocks (1x1, K <= 256) through cfp_pw_rows (csrc/pw_rows.hip): input rows in registers,
+        # weights streamed once per workgroup; the bits of the cfp_conv2d_nhwc launch it replaces (profiles/pw_rows_ab.txt).
+        # 16-bit modes; CFP_PW_ROWS=0 keeps the implicit GEMM (A/B).
+        self.pw_rows = os.environ.get("CFP_PW_ROWS", "1") != "0"
         # squeeze-excite through cfp_dwconv3x3_se_nhwc + cfp_se_gate_fold2 (16-bit modes; CFP_SE2=0: the round-2 pair)
         # The float32 depthwise kernel leaves the same partial dot products, so the default f16x3 mode can take this path too.  Measured:
         # one graph at a time it is faster at every batch (3.69 vs 3.87 ms at batch 1, 4.03 vs 4.26 at 2, 4.91 vs 5.05 at 4, 7.08 vs 7.17 at 8:
@@ -430,6 +434,15 @@ class Engine:
                    Ho, Wo, act, residual, self._ws(B * Ho * Wo, out.C, k * k * x.C))
         return Ho, Wo
 
+    def _expand(self, name, x: Act, out: Act, B, H, W, taps):
+        """The 1x1 expand convolution + BatchNorm + SiLU of an inverted-residual block: the short-K kernel where it takes the shape (16-bit
+        modes, plain weights), the implicit GEMM otherwise -- the same bits either way."""
+        if (self.pw_rows and self.half and not self.weights2 and taps is None
+                and ops.pw_rows_fits(B * H * W, x.C, out.C, x.ld, out.ld, ops.DT[self.dtype])):
+            ops.pw_rows(x, self.P[name + ".w"], self.P[name + ".s"], self.P[name + ".t"], out, B * H * W, hip.ACT_SILU)
+        else:
+            self._cv(name, x, out, B, H, W, 1, 1, None, hip.ACT_SILU)
+
     def _lin(self, wname, x: Act, out: Act, rows, act=hip.ACT_NONE, residual=None, st: Optional[str] = None, ln=None):
         ops.linear(x, self.P[wname], self.P[st + ".s"] if st else None, self.P[st + ".t"] if st else None, out, rows, act, residual,
                    None if ln is not None else self._ws(rows, out.C, x.C), ln)
@@ -507,7 +520,7 @@ class Engine:
                     # round 3: the depthwise kernel applies the reduce FC to its own channel sums (it is linear in them), the tail kernel
                     # adds the K partial vectors, finishes the gate and folds it into float32 project weights in one full-chip launch
                     mid = self._act(plan, f"enc{bi}.mid", B * h * w, b.mid)
-                    self._cv(q + ".pw", x, mid, B, h, w, 1, 1, None, hip.ACT_SILU)
+                    self._expand(q + ".pw", x, mid, B, h, w, taps)
                     K = ops.dwconv3x3_se_parts(B, ho, wo, b.mid, b.stride, ops.DT[self.dtype])
                     hpart = self._f32(plan, f"enc{bi}.hpart", B * K * b.se_rd)
                     ops.dwconv3x3_se(mid, self.P[q + ".dw.w"], self.P[q + ".dw.s"], self.P[q + ".dw.t"], mid2, self.P[q + ".se.wr"], hpart,
@@ -528,7 +541,7 @@ class Engine:
                     continue
                 else:
                     mid = self._act(plan, f"enc{bi}.mid", B * h * w, b.mid)
-                    self._cv(q + ".pw", x, mid, B, h, w, 1, 1, None, hip.ACT_SILU)
+                    self._expand(q + ".pw", x, mid, B, h, w, taps)
                     # depthwise + BN + SiLU, emitting the per-strip channel sums squeeze-excite needs
                     ns = ops.dwconv3x3_strips(B, ho, wo, b.mid, b.stride, ops.DT[self.dtype])
                     part = self._f32(plan, f"enc{bi}.sum", B * ns * b.mid)

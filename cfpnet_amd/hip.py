@@ -183,6 +183,9 @@ SIGNATURES = {
     "cfp_conv3x3_pw_fused_variant": (_i, [_i] * 5),
     "cfp_conv3x3_chunk_variant": (_i, [_i] * 4),
     "cfp_conv3x3_pw_fused": (_i, [_p, _i, _p, _p, _p, _i, _p, _p, _p, _i, _p, _i, _p, _i] + [_i] * 12 + [_p]),
+    "cfp_pw_rows_fits": (_i, [_ll, _i, _i, _i, _i, _i]),
+    "cfp_pw_rows_groups": (_i, [_ll, _i, _i, _p]),
+    "cfp_pw_rows": (_i, [_p, _i, _p, _p, _p, _i, _p, _i, _ll, _i, _i, _i, _i, _p]),
     "cfp_hist_encoder": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
     "cfp_depth_head_fused": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
     "cfp_bin_head_fused": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),

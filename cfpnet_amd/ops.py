@@ -160,6 +160,27 @@ def linear(x: Act, w: torch.Tensor, scale, shift, out: Act, rows: int, act=hip.A
     conv2d(x, w, scale, shift, out, 1, 1, rows, 1, 1, 1, 0, 0, 1, rows, act, residual, ws, ln)
 
 
+def pw_rows_fits(rows: int, K: int, N: int, in_ld: int, out_ld: int, dt: int) -> bool:
+    """Whether cfp_pw_rows takes the shape (ask before graph capture): 16-bit, K % 8 == 0 and <= 256, N % 8 == 0, aligned pitches."""
+    return bool(hip.load().cfp_pw_rows_fits(rows, K, N, in_ld, out_ld, dt))
+
+
+def pw_rows_groups(rows: int, K: int, N: int):
+    """(column groups an automatic cfp_pw_rows launch runs, the most a launch of this shape can run)."""
+    import ctypes
+    mx = ctypes.c_int(0)
+    return int(hip.load().cfp_pw_rows_groups(rows, K, N, ctypes.byref(mx))), mx.value
+
+
+def pw_rows(x: Act, w: torch.Tensor, scale, shift, out: Act, rows: int, act=hip.ACT_NONE, groups: int = 0):
+    """out[:rows] = act(scale * (x[:rows] @ w^T) + shift) through the short-K kernel (csrc/pw_rows.hip): the bits of conv2d() on the same
+    operands.  w [out.C, x.C]; `groups` = 0: the kernel chooses its column groups."""
+    assert x.rows >= rows and out.rows >= rows and x.dt == out.dt
+    assert w.dtype == x.buf.dtype and tuple(w.shape) == (out.C, x.C) and w.is_contiguous(), (w.shape, out.C, x.C)
+    hip.call("cfp_pw_rows", x.ptr, x.ld, w.data_ptr(), hip.ptr(scale), hip.ptr(shift), act, out.ptr, out.ld, rows, x.C, out.C, groups,
+             x.dt, _s())
+
+
 def dwconv3x3(x: Act, w, scale, shift, out: Act, B, H, W, stride, pad_t, pad_l, Ho, Wo, act):
     hip.call("cfp_dwconv3x3_nhwc", x.ptr, x.ld, w.data_ptr(), scale.data_ptr(), shift.data_ptr(), out.ptr, out.ld,
              B, H, W, x.C, stride, pad_t, pad_l, Ho, Wo, act, x.dt, _s())

@@ -246,6 +246,22 @@ int cfp_conv3x3_pw_fused(const void* in, int in_ld, const void* w1, const float*
                          void* out, int out_ld, int B, int H, int W, int Cin, int Cmid, int Cout, int stride, int pad_t, int pad_l,
                          int Ho, int Wo, int dtype, cfp_stream_t stream);
 
+/* Short-K pointwise GEMM (csrc/pw_rows.hip), bf16 / f16:
+ *   out[m, n] = act(scale[n] * sum_k in[m, k] * w[n, k] + shift[n]),  m < M, k < K <= 256, n < N.
+ * Replaces the conv_pw + bn1 + SiLU of timm's InvertedResidual blocks (encoder.py:57-69; oracle/cfpnet_oracle.py) as a cfp_conv2d_nhwc
+ * launch, bit for bit: a workgroup keeps its 64 input rows in registers as whole MFMA fragments and streams only the weights, one group
+ * of output columns per workgroup.
+ *   in [M][in_ld] (K channels; may be a channel slice of a wider buffer), w [N][K] as cfp_conv2d_nhwc lays out 1x1 weights, scale / shift
+ *   [N] f32 (may be NULL = 1 / 0), out [M][out_ld] (N channels; may be a channel slice).  act CFP_ACT_NONE or CFP_ACT_SILU (CFP_EINVAL
+ *   otherwise).  groups: column groups of the launch, 0 = chosen for about two workgroups per CU, else clamped to what the shape allows.
+ * cfp_pw_rows_fits -> 1 when the launch takes the shape: 16-bit storage, K % 8 == 0 and K <= 256, N % 8 == 0, row pitches multiples of
+ * 8 elements that cover K / N, 0 < M < 2^31; else 0, and the launch returns CFP_ESHAPE: the caller keeps cfp_conv2d_nhwc, nothing falls
+ * back silently.  cfp_pw_rows_groups -> the column groups an automatic launch runs, *max_groups (may be NULL) = the most it can run. */
+int cfp_pw_rows_fits(long long M, int K, int N, int in_ld, int out_ld, int dtype);
+int cfp_pw_rows_groups(long long M, int K, int N, int* max_groups);
+int cfp_pw_rows(const void* in, int in_ld, const void* w, const float* scale, const float* shift, int act, void* out, int out_ld,
+                long long M, int K, int N, int groups, int dtype, cfp_stream_t stream);
+
 /* cfp_se_hidden + cfp_se_fold in one launch (mean -> FC -> SiLU -> FC -> sigmoid -> per-image project weights),
  * structured for latency: this is what the engine calls between the depthwise conv and the project conv of every
  * inverted-residual block.  Same arguments as the two calls it replaces; C <= 2048, R <= 64. */
