@@ -1,0 +1,224 @@
+"""Camera tracking on the device: where the pose of `temporal.TemporalFilter` and `tsdf.TsdfVolume` comes from when no odometry delivers it.
+
+`icp` aligns a frame -- the prediction and its std map -- with a model map in another camera by dense point-to-plane ICP: every source
+pixel is back-projected like `pointcloud.unproject` does, moved by the current pose estimate, projected into the model camera and
+paired with the model point it lands on (projective data association); the pairs' point-to-plane residuals, weighted by the two
+predicted variances, give one 6 x 6 Gauss-Newton step per iteration (`cfp_icp_step`: accumulate and finalize, two launches, no atomics).
+The model map is a `TsdfVolume.raycast` (frame-to-model tracking, KinectFusion's other half) or the previous frame's
+`pointcloud.unproject(..., normals=True)` (frame-to-frame odometry).  `Tracker` is the loop around a volume: raycast -> track ->
+integrate, with nothing synchronising with the host, so an `update` can be captured in a graph.  The arithmetic is `csrc/icp.hip`
+(definition in include/cfpnet_hip.h); nothing here computes on the CPU.
+
+This is frame-to-model dense ICP and nothing more: no relocalisation, no loop closure, no image pyramid.  It follows a camera that moves
+a few degrees and centimetres per frame; a visual-inertial front end remains the answer for fast motion.
+"""
+from __future__ import annotations
+
+import math
+from typing import NamedTuple, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import hip
+from .pointcloud import _check_out, _intrinsics, _pred3, _size
+from .temporal import _pose, _std_plane, _ws
+from .tsdf import TsdfVolume
+
+STAT_NAMES = ("pairs", "weight", "rms", "rotation", "translation", "accepted")     # columns of `stats`
+
+
+class IcpResult(NamedTuple):
+    """What `icp` returns, all on the device.  `pose` [B,3,4] f32: [R|t] that takes a point of the current camera into the model camera.
+    `world` [B,3,4] f32: the camera-from-world pose of the current frame (None without `ref_pose`).  `stats` [iters,B,6] f32 in
+    `STAT_NAMES` order, one row per iteration: the number of pairs, sum w, the weighted rms of the point-to-plane residual BEFORE the
+    step (NaN without pairs), |omega| and |v| of the step (0 when refused), and whether the step was accepted (1 / 0).  `sums` [B,32] f64
+    of the last iteration: the 21 entries of the upper triangle of A = sum w J J^T by rows, the 6 of g = sum w J r, sum w r r, sum w,
+    the pair count, two zeros -- A is the information matrix of the pose at the solution (for a LEFT increment (omega, v) of `pose`), its
+    inverse the covariance a pose graph or a filter wants.  `index` [B,H,W] i32 (None unless asked for): the model pixel ym * Wm + xm
+    each source pixel was paired with in the last iteration, -1 where none.  `ws`: the workspace, reused when the tuple comes back as
+    `out`."""
+    pose: torch.Tensor
+    world: Optional[torch.Tensor]
+    stats: torch.Tensor
+    sums: torch.Tensor
+    index: Optional[torch.Tensor]
+    ws: torch.Tensor
+
+
+def _map(t, shape, what: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or not t.is_cuda:
+        raise ValueError(f"{what} must be a float32 device tensor")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{what} must be {tuple(shape)}, got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _icp_numbers(cos_min, iters, stride, dist_max, z_near, lo, hi, std_floor, min_pairs, min_pivot):
+    if not float(lo) < float(hi):
+        raise ValueError(f"empty depth range [{lo}, {hi}]")
+    for name, v in (("dist_max", dist_max), ("z_near", z_near), ("std_floor", std_floor)):
+        if not (float(v) > 0.0 and math.isfinite(float(v))):
+            raise ValueError(f"{name} must be positive and finite, got {v}")
+    if not -1.0 <= float(cos_min) <= 1.0:
+        raise ValueError(f"cos_min must lie in [-1, 1], got {cos_min}")
+    if int(iters) != iters or iters < 1:
+        raise ValueError(f"iters must be a positive integer, got {iters!r}")
+    if int(stride) != stride or stride < 1:
+        raise ValueError(f"stride must be a positive integer, got {stride!r}")
+    if int(min_pairs) != min_pairs or min_pairs < 6:
+        raise ValueError(f"min_pairs must be an integer of at least 6, got {min_pairs!r}")
+    if not 0.0 <= float(min_pivot) < 1.0:
+        raise ValueError(f"min_pivot must lie in [0, 1), got {min_pivot}")
+
+
+def icp(pred: torch.Tensor, intrinsics, model_depth: torch.Tensor, model_normals: torch.Tensor, pose0=None,
+        unc: Optional[torch.Tensor] = None, model_std: Optional[torch.Tensor] = None, model_intrinsics=None,
+        size: Optional[Sequence[int]] = None, src_normals: Optional[torch.Tensor] = None, cos_min: float = 0.5, iters: int = 10,
+        stride: int = 1, dist_max: float = 0.25, z_near: float = 1e-3, lo: float = 1e-3, hi: float = 10.0, std_floor: float = 1e-3,
+        min_pairs: int = 100, min_pivot: float = 1e-6, ref_pose=None, index: bool = False, out: Optional[IcpResult] = None) -> IcpResult:
+    """pred [B,h,w] / [B,1,h,w] f32 on the device, seen on the H x W grid of `size` like `pointcloud.unproject` sees it (twice the
+    prediction by default), aligned with the model map `model_depth` [B,Hm,Wm], `model_normals` [B,Hm,Wm,3] (`model_std` [B,Hm,Wm]
+    optional) of the camera `model_intrinsics` (= `intrinsics` by default) -> `IcpResult`.  `iters` Gauss-Newton iterations of
+    `cfp_icp_step` on one pose buffer, started from `pose0` ([R|t] current-to-model in every form `TemporalFilter.update` takes; None:
+    the identity, "the camera did not move"); the count is fixed, so the call can be captured in a graph.  `unc`: the model's [B,3,h,w]
+    uncertainty tensor or a [B,hu,wu] std map; with it or `model_std` a pair weighs 1 / (std^2 + model_std^2), else 1.  Only every
+    `stride`-th pixel in x and y is used.  A pair is dropped when its points lie more than `dist_max` apart or -- with `src_normals`
+    [B,H,W,3], `unproject`'s -- when the normals' cosine is below `cos_min`.  A step is refused (the pose stays as it is) with fewer than
+    `min_pairs` pairs or a pivot of the 6 x 6 system not above `min_pivot` times its largest diagonal entry: a scene that does not
+    constrain all six degrees of freedom.  `ref_pose`: camera-from-world of the model camera; given, `world` is the frame's own
+    camera-from-world pose.  `index=True` adds the association map.  `out`: the result of an earlier call to write into -- then nothing
+    is allocated here.  Bitwise reproducible; no host synchronisation."""
+    pred = _pred3(pred)
+    B, h, w = pred.shape
+    H, W = _size(size, h, w)
+    _icp_numbers(cos_min, iters, stride, dist_max, z_near, lo, hi, std_floor, min_pairs, min_pivot)
+    dev = pred.device
+    if not isinstance(model_depth, torch.Tensor) or model_depth.dim() != 3:
+        raise ValueError("model_depth must be a float32 device tensor [B,Hm,Wm]")
+    Hm, Wm = model_depth.shape[1:]
+    model_depth = _map(model_depth, (B, Hm, Wm), "model_depth")
+    model_normals = _map(model_normals, (B, Hm, Wm, 3), "model_normals")
+    if model_std is not None:
+        model_std = _map(model_std, (B, Hm, Wm), "model_std")
+    if src_normals is not None:
+        src_normals = _map(src_normals, (B, H, W, 3), "src_normals")
+    std = None if unc is None else _std_plane(unc, B)
+    K = _intrinsics(intrinsics, B, dev)
+    Km = K if model_intrinsics is None else _intrinsics(model_intrinsics, B, dev)
+    T0 = None if pose0 is None else _pose(pose0, B, dev)
+    Tr = None if ref_pose is None else _pose(ref_pose, B, dev)
+    iters, stride = int(iters), int(stride)
+    nbytes = hip.load().cfp_icp_ws_bytes(B, H, W, stride)
+    if out is not None:
+        if not isinstance(out, IcpResult):
+            raise ValueError("out must be the IcpResult of an earlier call")
+        _check_out(out.pose, (B, 3, 4), torch.float32, "out pose")
+        if (out.world is None) != (Tr is None):
+            raise ValueError("out world must be given exactly when ref_pose is")
+        if Tr is not None:
+            _check_out(out.world, (B, 3, 4), torch.float32, "out world")
+        _check_out(out.stats, (iters, B, 6), torch.float32, "out stats")
+        _check_out(out.sums, (B, 32), torch.float64, "out sums")
+        if (out.index is None) == bool(index):
+            raise ValueError("out index must be given exactly when index is asked for")
+        if index:
+            _check_out(out.index, (B, H, W), torch.int32, "out index")
+        _ws(nbytes, out.ws, dev)
+    else:
+        out = IcpResult(torch.empty(B, 3, 4, dtype=torch.float32, device=dev),
+                        None if Tr is None else torch.empty(B, 3, 4, dtype=torch.float32, device=dev),
+                        torch.empty(iters, B, 6, dtype=torch.float32, device=dev), torch.empty(B, 32, dtype=torch.float64, device=dev),
+                        torch.empty(B, H, W, dtype=torch.int32, device=dev) if index else None, _ws(nbytes, None, dev))
+    T = out.pose.view(B, 12)
+    if T0 is None:
+        T.zero_()
+        T[:, ::5] = 1.0                                                   # entries 0, 5, 10: the identity, written on the device
+    elif T0.data_ptr() != T.data_ptr():
+        T.copy_(T0)
+    interp = int((h, w) != (H, W))                    # the rule of pointcloud.unproject
+    stream = hip.current_stream()
+    for it in range(iters):
+        last = it == iters - 1
+        hip.call("cfp_icp_step", pred.data_ptr(), h, w, H, W, B, interp, float(lo), float(hi), hip.ptr(std),
+                 0 if std is None else std.shape[1], 0 if std is None else std.shape[2], 0 if std is None else std.stride(0),
+                 float(std_floor), hip.ptr(src_normals), float(cos_min), K.data_ptr(), model_depth.data_ptr(), model_normals.data_ptr(),
+                 hip.ptr(model_std), Hm, Wm, Km.data_ptr(), stride, float(z_near), float(dist_max), int(min_pairs), float(min_pivot),
+                 T.data_ptr(), hip.ptr(Tr) if last else 0, hip.ptr(out.world) if last else 0, hip.ptr(out.index) if last else 0,
+                 out.sums.data_ptr(), out.stats[it].data_ptr(), out.ws.data_ptr(), nbytes, stream)
+    return out
+
+
+_TRACKER_OPTIONS = ("cos_min", "iters", "stride", "dist_max", "min_pairs", "min_pivot")
+
+
+class Tracker:
+    """Frame-to-model tracking around a `TsdfVolume`: every `update` ray-casts the volume at the last pose, aligns the new frame with that
+    raycast (`icp`, started from "the camera did not move") and integrates the frame at the pose it found.  `pose0`: camera-from-world
+    of the first frame (None: the identity: the world frame is the first camera's).  `icp_options`: `cos_min`, `iters`, `stride`,
+    `dist_max`, `min_pairs`, `min_pivot` of `icp`; the depth range, the std floor, z_near, the camera and the grid are the volume's.
+    `.pose` [B,3,4] f32 is the last pose, on the device.  Nothing synchronises with the host: once the first frame is in, an `update`
+    can be captured in a graph and replayed on new inputs.
+
+    A lost frame is still integrated: `update` does not look at the result on the host.  `stats[-1, :, 5]` says whether the last step
+    was accepted; a caller who wants to keep a doubtful frame out of the map calls `update(..., integrate=False)` (or `track`), reads
+    the stats and integrates the frame afterwards."""
+
+    def __init__(self, volume: TsdfVolume, pose0=None, **icp_options):
+        if not isinstance(volume, TsdfVolume):
+            raise ValueError("volume must be a TsdfVolume")
+        unknown = sorted(set(icp_options) - set(_TRACKER_OPTIONS))
+        if unknown:
+            raise ValueError(f"unknown icp option(s) {unknown}: one of {_TRACKER_OPTIONS}")
+        defaults = dict(cos_min=0.5, iters=10, stride=1, dist_max=0.25, min_pairs=100, min_pivot=1e-6)
+        defaults.update(icp_options)
+        _icp_numbers(lo=volume.lo, hi=volume.hi, std_floor=volume.std_floor, z_near=volume.z_near, **defaults)
+        if pose0 is not None and not (isinstance(pose0, torch.Tensor) and pose0.is_cuda):
+            n = np.ndim(pose0.numpy() if isinstance(pose0, torch.Tensor) else pose0)
+            _pose(pose0, len(pose0) if n == 3 else 1, "cpu")              # refuse bad numbers now, not at the first frame
+        self.volume, self.pose0, self.options = volume, pose0, defaults
+        self.pose = self.stats = None
+        self._out = None
+        self._primed = False
+
+    def reset(self):
+        """Forget the trajectory: the next `update` integrates at `pose0` without tracking.  The volume is not touched."""
+        self._primed = False
+
+    def _track(self, pred, unc) -> IcpResult:
+        if not self._primed:
+            raise ValueError("nothing to track against yet: the first update integrates the first frame")
+        pred = _pred3(pred)
+        vol = self.volume
+        depth, std, normals = vol.raycast(self.pose, normals=True)
+        if self._out is not None and (self._out.pose.shape[0] != pred.shape[0] or self._out.index is not None):
+            self._out = None
+        self._out = icp(pred, vol.camera, depth, normals, None, unc, std, None, vol.grid_size, None, lo=vol.lo, hi=vol.hi,
+                        std_floor=vol.std_floor, z_near=vol.z_near, ref_pose=self.pose, out=self._out, **self.options)
+        self.stats = self._out.stats
+        return self._out
+
+    def track(self, pred: torch.Tensor, unc: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The camera-from-world pose [B,3,4] f32 (device; the tracker's own buffer, overwritten by the next call) of the frame `pred`,
+        `unc` against the volume as it is; `.stats` [iters,B,6] is `icp`'s.  Stores nothing: `.pose` and the volume stay."""
+        return self._track(pred, unc).world
+
+    def update(self, pred: torch.Tensor, unc: Optional[torch.Tensor] = None, integrate: bool = True):
+        """`track`, the pose stored in `.pose` (a device copy), the frame integrated at it -> (pose [B,3,4], stats [iters,B,6]).  The
+        first call (and the first after `reset`) integrates at `pose0` without tracking and returns stats None."""
+        if not self._primed:
+            pred = _pred3(pred)
+            B = pred.shape[0]
+            T0 = _pose(self.pose0, B, pred.device).view(B, 3, 4)
+            if self.pose is None or self.pose.shape[0] != B:
+                self.pose = torch.empty(B, 3, 4, dtype=torch.float32, device=pred.device)
+            self.pose.copy_(T0)
+            self.volume.integrate(pred, unc, self.pose)
+            self._primed = True
+            self.stats = None
+            return self.pose, None
+        res = self._track(pred, unc)
+        self.pose.copy_(res.world)
+        if integrate:
+            self.volume.integrate(pred, unc, self.pose)
+        return self.pose, res.stats

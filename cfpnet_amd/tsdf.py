@@ -72,6 +72,16 @@ class TsdfVolume:
         self._shape = None
         self._rays = {}
 
+    @property
+    def camera(self) -> Optional[torch.Tensor]:
+        """The intrinsics [B,4] f32 on the device the volume integrates with; None before the first integrate.  Read-only."""
+        return None if self._shape is None else self._K
+
+    @property
+    def grid_size(self) -> Optional[tuple]:
+        """(H, W) of the grid the predictions are seen on; None before the first integrate.  Read-only."""
+        return None if self._shape is None else self._hw
+
     def reset(self):
         """Empty the volume: F = 1, Wt = 0.  The buffers stay."""
         if self.volume is not None:

@@ -882,6 +882,66 @@ int cfp_tsdf_raycast(const float* volume /* [B][Dz][Dy][Dx][2] */, int Dx, int D
                      float t_min, float t_max, float step, float* depth /* [B][Hd][Wd] */, float* normal /* [B][Hd][Wd][3] or NULL */,
                      float* std /* [B][Hd][Wd] or NULL */, cfp_stream_t stream);
 
+/* Camera tracking: one Gauss-Newton iteration of dense point-to-plane ICP of a frame against a model map, per image, without leaving the
+ * device -- projective data association, the 6 x 6 normal equations weighted by the two variances, the solve and the pose update.  The
+ * frame is the prediction and its std; the model is a depth / normal / std map in the MODEL camera: a cfp_tsdf_raycast (frame-to-model
+ * tracking) or the previous frame's cfp_depth_unproject (frame-to-frame odometry).
+ *   Inputs  pred [B,Hp,Wp] f32; H, W, interpolate, lo < hi as cfp_depth_unproject; std (NULL: none): image 0's Hu x Wu f32 plane, image
+ *           b's std_stride ELEMENTS further, brought to H x W like the plane of cfp_depth_reproject; src_normals [B,H,W,3] f32 or NULL;
+ *           K_src, K_mdl [B][4] f32 ON THE DEVICE: (fx, fy, cx, cy) of the H x W source grid and (fxm, fym, cxm, cym) of the Hm x Wm model
+ *           grid, under the caller contract of cfp_depth_unproject; mdl_depth [B,Hm,Wm], mdl_normals [B,Hm,Wm,3], mdl_std [B,Hm,Wm] or NULL.
+ *   Pose    T [B][12] f32 ON THE DEVICE, in and out: row-major [R|t], it takes a point of the CURRENT camera into the MODEL camera,
+ *           Pm = R P + t, camera frames of cfp_depth_unproject.  The caller initialises it; the identity means the camera did not move.
+ *   Pair    float32, in this order of operations (no fused multiply-add), for the source pixels x % stride == 0 && y % stride == 0:
+ *             d = d(x, y) of cfp_depth_unproject (csrc/metrics_pred.h, bit for bit); skipped unless d is finite and d > 0
+ *             P = (rx * d, ry * d, d)  with  rx = ((float)x - cx) / fx,  ry = ((float)y - cy) / fy
+ *             X' = (T[0] * X + T[1] * Y) + T[2] * Z + T[3]      Y' likewise with T[4..7], Z' with T[8..11]   (left to right)
+ *             skipped unless Z' is finite and Z' >= z_near;  u = fxm * (X' / Z') + cxm,  v = fym * (Y' / Z') + cym
+ *             model pixel (xm, ym) = (floorf(u + 0.5f), floorf(v + 0.5f)), tested against 0 <= xm < Wm, 0 <= ym < Hm on the float
+ *             values, before any conversion to int;  dm = mdl_depth there: skipped unless dm is finite and dm > 0;  n = mdl_normals
+ *             there: skipped unless its three components are finite and (n.x * n.x + n.y * n.y) + n.z * n.z > 0.25f (a raycast writes
+ *             NaN for "no normal", cfp_depth_unproject 0: both kinds of map work)
+ *             Q = (((float)xm - cxm) / fxm * dm, ((float)ym - cym) / fym * dm, dm);  D = P' - Q
+ *             skipped unless (D.x * D.x + D.y * D.y) + D.z * D.z <= dist_max * dist_max
+ *             with src_normals: s = the source normal at the pixel, skipped unless s passes the test of n and
+ *             ((R s) . n) >= cos_min, R s by rows left to right like P' without the translation, the dot product (a + b) + c
+ *             r = (n.x * D.x + n.y * D.y) + n.z * D.z
+ *             J = (P' x n, n) = (Y' * n.z - Z' * n.y, Z' * n.x - X' * n.z, X' * n.y - Y' * n.x, n.x, n.y, n.z): the derivative of r
+ *             for a LEFT increment xi = (omega, v), P'' = exp(xi) P'
+ *             w = 1 / (sf * sf + sm * sm):  sf = s > std_floor ? s : std_floor for s = the std plane at the pixel (a NaN s gives the
+ *             floor; without a std plane sf = std_floor), sm = mdl_std at the model pixel, 0 when mdl_std is NULL or the value is not
+ *             finite.  A pair whose w is 0 or not finite (an infinite std) is skipped.  With no std plane at all (both NULL) w = 1.
+ *   Index   index [B,H,W] i32 or NULL: ym * Wm + xm of the pixel's pair, -1 where there is none; a pixel off the stride grid gets -1, so
+ *           the map is fully written.
+ *   Sums    30 per image, in this order: the 21 entries of the upper triangle of A = sum w J J^T by rows ((w * J[a]) * J[c], c >= a),
+ *           the 6 of g = sum w J r ((w * J[a]) * r), sum (w * r) * r, sum w, the number of pairs.  Every product is float32, every
+ *           accumulation double: per thread, __shfl_xor inside the wave, a fixed tree through LDS, ONE row of 30 doubles per workgroup
+ *           in the workspace; the number of workgroups per image depends on the shape alone (at most 128).
+ *   Step    one 64-lane workgroup per image, in double: the rows summed in a fixed order; sums [B][32] f64 or NULL receives the 30 values
+ *           and 2 zeros.  A xi = -g is solved by LDL^T.  The step is REFUSED if pairs < min_pairs or a pivot is not above
+ *           min_pivot * (largest diagonal entry of A); a refused step leaves T bit for bit as it was.  Otherwise exp(xi): with
+ *           theta^2 = |omega|^2 and K = [omega]x,  Re = I + a K + b K^2,  te = (I + b K + c K^2) v,  a = sin(theta) / theta,
+ *           b = (1 - cos(theta)) / theta^2,  c = (theta - sin(theta)) / theta^3, and (1, 1/2, 1/6) when theta^2 < 1e-12;
+ *           T' = exp(xi) o T:  R' = Re R,  t' = Re t + te;  the rows of R' re-orthonormalised by Gram-Schmidt (row 0, row 1, row 2 =
+ *           row 0 x row 1);  rounded to float32 and written over T.
+ *   World   with T_ref [B][12] (camera-from-world of the model camera) T_world [B][12] is written on every call, refused or not: the
+ *           camera-from-world pose of the current frame, R_cur = R^T R_ref, t_cur = R^T (t_ref - t) with [R|t] the T just written.
+ *           T_ref and T_world are given together or not at all.
+ *   Stats   stats [B][6] f32 = {pairs, sum w, sqrtf(sum w r r / sum w) (NaN without pairs), |omega|, |v| (0 when refused), accepted (1 / 0)}.
+ *   Checks  stride >= 1; std_floor, z_near, dist_max positive and finite; 0 <= min_pivot < 1; min_pairs >= 6; -1 <= cos_min <= 1.
+ * Two launches (accumulate, finalize) on `stream`, no atomics: two calls on the same inputs give identical bits.  No host
+ * synchronisation, no allocation.  Workspace of cfp_icp_ws_bytes(B, H, W, stride) bytes, 8-byte aligned; 0 for arguments that make no sense. */
+size_t cfp_icp_ws_bytes(int B, int H, int W, int stride);
+int cfp_icp_step(const float* pred, int Hp, int Wp, int H, int W, int B, int interpolate, float lo, float hi,
+                 const float* std /* or NULL */, int Hu, int Wu, long long std_stride, float std_floor,
+                 const float* src_normals /* [B][H][W][3] or NULL */, float cos_min, const float* K_src /* device, [B][4] */,
+                 const float* mdl_depth /* [B][Hm][Wm] */, const float* mdl_normals /* [B][Hm][Wm][3] */,
+                 const float* mdl_std /* [B][Hm][Wm] or NULL */, int Hm, int Wm, const float* K_mdl /* device, [B][4] */,
+                 int stride, float z_near, float dist_max, int min_pairs, float min_pivot,
+                 float* T /* device, [B][12], in and out */, const float* T_ref /* [B][12] or NULL */,
+                 float* T_world /* [B][12] or NULL, given exactly when T_ref is */, int* index /* [B][H][W] or NULL */,
+                 double* sums /* [B][32] or NULL */, float* stats /* [B][6] */, void* ws, size_t ws_bytes, cfp_stream_t stream);
+
 /* Surface-normal error of the predicted geometry against the ground truth's, per image, without leaving the device: the standard set of
  * the normal-estimation literature (mean, median and RMSE of the angle, share of pixels below 11.25, 22.5 and 30 degrees).
  *   Inputs  pred [B,Hp,Wp] f32 and gt [B,H,W] f32 (device); interpolate, lo < hi exactly as cfp_eval_metrics in mode 0; K [B][4] f32 ON
