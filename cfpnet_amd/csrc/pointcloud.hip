@@ -15,10 +15,11 @@
 // chunk of 256 consecutive candidates (4 per lane, step by step 64 contiguous ones).  Three launches and no atomics, so the order and
 // every bit of the result are a function of the inputs alone:
 //   1. count    per (image, chunk): popcount of the predicate's ballots -> workspace
-//   2. scan     one workgroup per image: exclusive scan of the chunk counts in place, the total -> counts[b]
+//   2. scan     one workgroup per image: exclusive scan of the chunk counts in place, the total -> counts[b] (chunk_scan.h)
 //   3. scatter  the predicate again; rank = chunk offset + kept lanes of the earlier steps + popcount(ballot & lanes below)
 // Rows at or beyond `cap` are dropped, counts[b] stays the true total.
 #include "common.h"
+#include "chunk_scan.h"
 #include "metrics_pred.h"
 
 #include <algorithm>
@@ -168,28 +169,6 @@ __global__ __launch_bounds__(256) void compact_count_kernel(CompP p) {
   if (lane == 0) p.ws[(long long)b * p.nchunks + chunk] = n;
 }
 
-// exclusive scan of one image's chunk counts in place; thread t owns a run of consecutive chunks
-__global__ __launch_bounds__(256) void compact_scan_kernel(int* __restrict__ ws, int* __restrict__ counts, int nchunks) {
-  __shared__ int s[2][256];
-  const int b = blockIdx.x, t = threadIdx.x;
-  int* w = ws + (long long)b * nchunks;
-  const int L = (nchunks + 255) / 256;
-  const int j0 = min((long long)t * L, (long long)nchunks), j1 = min((long long)(t + 1) * L, (long long)nchunks);
-  int sum = 0;
-  for (int j = j0; j < j1; ++j) sum += w[j];
-  s[0][t] = sum;
-  __syncthreads();
-  int cur = 0;
-  for (int o = 1; o < 256; o <<= 1) {                             // inclusive Hillis-Steele scan of the 256 run sums
-    s[cur ^ 1][t] = s[cur][t] + (t >= o ? s[cur][t - o] : 0);
-    cur ^= 1;
-    __syncthreads();
-  }
-  int run = s[cur][t] - sum;                                      // exclusive prefix of this thread's run
-  for (int j = j0; j < j1; ++j) { const int c = w[j]; w[j] = run; run += c; }
-  if (t == 255) counts[b] = s[cur][255];
-}
-
 template <bool NORMALS>
 __global__ __launch_bounds__(256) void compact_scatter_kernel(CompP p) {
   const int b = blockIdx.y, lane = threadIdx.x & 63;
@@ -289,7 +268,7 @@ extern "C" int cfp_points_compact(const float* points, const float* normals, int
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const dim3 grid(cdiv(p.nchunks, 4), B);
   hipLaunchKernelGGL(compact_count_kernel, grid, dim3(256), 0, s, p);
-  hipLaunchKernelGGL(compact_scan_kernel, dim3(B), dim3(256), 0, s, p.ws, counts, p.nchunks);
+  hipLaunchKernelGGL(chunk_scan_kernel, dim3(B), dim3(256), 0, s, p.ws, counts, p.nchunks);
   if (normals) hipLaunchKernelGGL(compact_scatter_kernel<true>, grid, dim3(256), 0, s, p);
   else hipLaunchKernelGGL(compact_scatter_kernel<false>, grid, dim3(256), 0, s, p);
   return cfp_check_launch("cfp_points_compact");

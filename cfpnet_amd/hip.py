@@ -103,6 +103,8 @@ SIGNATURES = {
     "cfp_depth_fuse": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _i, _i, _ll, _f, _p, _p, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p]),
     "cfp_tsdf_integrate": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _i, _i, _ll, _f, _p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _p, _p]),
     "cfp_tsdf_raycast": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, _p, _p, _i, _i, _f, _f, _f, _p, _p, _p, _p]),
+    "cfp_tsdf_surface_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "cfp_tsdf_surface": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "cfp_icp_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "cfp_icp_step": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _i, _i, _ll, _f, _p, _f, _p, _p, _p, _p, _i, _i, _p, _i, _f, _f, _i, _f, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "cfp_normal_metrics_ws_bytes": (_sz, [_i, _i, _i]),

@@ -4,18 +4,19 @@
 re-samples it.  `TsdfVolume` keeps a truncated signed distance field in a fixed world frame instead: `integrate` fuses a prediction and
 its std map into the voxels the camera sees (`cfp_tsdf_integrate`: the per-voxel weight is the inverse-variance sum `fuse` keeps per
 pixel), `raycast` turns the volume back into depth, std and normals in any view (`cfp_tsdf_raycast`), so two views combine into
-something a third can look at.  The arithmetic is `csrc/tsdf.hip` (definition in include/cfpnet_hip.h); nothing here
-computes on the CPU.
+something a third can look at, and `surface_points` takes the map out: the zero crossings of F along the voxel lattice's edges as oriented
+points in the world frame (`cfp_tsdf_surface`, `csrc/tsdf_surface.hip`), which `write_ply` stores.  The arithmetic is
+`csrc/tsdf.hip` (definition in include/cfpnet_hip.h); nothing here computes on the CPU except the PLY writer.
 """
 from __future__ import annotations
 
 import math
-from typing import Optional, Sequence
+from typing import List, Optional, Sequence
 
 import torch
 
 from . import hip
-from .pointcloud import _check_out, _intrinsics, _pred3, _size
+from .pointcloud import _check_out, _intrinsics, _pred3, _size, write_ply
 from .temporal import _pose, _std_plane
 
 COUNT_NAMES = ("seen", "updated", "behind")           # columns of `counts` (CFP_TSDF_*)
@@ -27,6 +28,28 @@ def _positive(v, what: str) -> float:
     if not (v > 0.0 and math.isfinite(v)):
         raise ValueError(f"{what} must be positive and finite, got {v}")
     return v
+
+
+class SurfacePoints:
+    """Result of `TsdfVolume.surface_points`, everything on the device: `points` [B,cap,3] f32 in the world frame, `normals` [B,cap,3]
+    f32 or None (towards the free space the observing camera was in; NaN where the volume does not know), `std` [B,cap] f32, `index`
+    [B,cap] i32 (the lattice edge 3 * voxel + axis a row came from), `counts` [B] i32 -- the number of crossings per image, also when it
+    exceeds `capacity`.  Rows at or beyond min(count, capacity) hold nothing of meaning."""
+
+    def __init__(self, points, normals, std, index, counts, capacity: int):
+        self.points, self.normals, self.std, self.index, self.counts = points, normals, std, index, counts
+        self.capacity = capacity
+
+    def split(self) -> List[dict]:
+        """The one host synchronisation: per image {"points": [n,3], "normals", "std", "index"} trimmed to its count (None where
+        absent).  Raises if an image has more crossings than `capacity`."""
+        counts = self.counts.cpu().tolist()
+        over = [(b, n) for b, n in enumerate(counts) if n > self.capacity]
+        if over:
+            raise RuntimeError(f"surface_points overflow: (image, kept) = {over} exceeds capacity {self.capacity}")
+        trim = lambda t, b, n: None if t is None else t[b, :n]
+        return [{"points": trim(self.points, b, n), "normals": trim(self.normals, b, n), "std": trim(self.std, b, n),
+                 "index": trim(self.index, b, n)} for b, n in enumerate(counts)]
 
 
 class TsdfVolume:
@@ -71,6 +94,7 @@ class TsdfVolume:
         self.volume = self.counts = None
         self._shape = None
         self._rays = {}
+        self._surface_ws = None
 
     @property
     def camera(self) -> Optional[torch.Tensor]:
@@ -96,6 +120,7 @@ class TsdfVolume:
         self.volume = torch.empty(B, Dz, Dy, Dx, 2, dtype=torch.float32, device=dev)
         self.counts = torch.zeros(B, 3, dtype=torch.int32, device=dev)
         self._rays = {}
+        self._surface_ws = None
         self.reset()
 
     def integrate(self, pred: torch.Tensor, unc: Optional[torch.Tensor] = None, pose=None) -> torch.Tensor:
@@ -157,3 +182,85 @@ class TsdfVolume:
         hip.call("cfp_tsdf_raycast", self.volume.data_ptr(), Dx, Dy, Dz, B, *self.origin, self.voxel, K.data_ptr(), T.data_ptr(), Hd, Wd,
                  t0, t1, step, out[0].data_ptr(), out[2].data_ptr() if normals else 0, out[1].data_ptr(), hip.current_stream())
         return out
+
+    def _surface_args(self, w_min, max_jump):
+        if self.volume is None:
+            raise ValueError("nothing was integrated yet: the volume is allocated by the first integrate")
+        w_min = float(w_min)
+        max_jump = math.inf if max_jump is None else float(max_jump)
+        if not w_min >= 0.0:
+            raise ValueError(f"w_min must not be negative, got {w_min}")
+        if not max_jump >= 0.0:
+            raise ValueError(f"max_jump must not be negative, got {max_jump}")
+        B = self.volume.shape[0]
+        nbytes = hip.load().cfp_tsdf_surface_ws_bytes(B, *self.dims)
+        if nbytes == 0:
+            raise ValueError(f"dims {self.dims} have too many lattice edges for an int32 index (3 * Dx * Dy * Dz < 2^31)")
+        if self._surface_ws is None:
+            self._surface_ws = torch.empty(nbytes // 8, dtype=torch.int64, device=self.volume.device)
+        return B, w_min, max_jump, nbytes
+
+    def _surface(self, w_min, max_jump, nbytes, res, counts):
+        Dx, Dy, Dz = self.dims
+        hip.call("cfp_tsdf_surface", self.volume.data_ptr(), Dx, Dy, Dz, self.volume.shape[0], *self.origin, self.voxel, w_min, max_jump,
+                 0 if res is None else res.capacity, *((0, 0, 0, 0) if res is None else
+                                                       (res.points.data_ptr(), hip.ptr(res.normals), res.std.data_ptr(), res.index.data_ptr())),
+                 counts.data_ptr(), self._surface_ws.data_ptr(), nbytes, hip.current_stream())
+
+    def surface_count(self, w_min: float = 0.0, max_jump: Optional[float] = None) -> torch.Tensor:
+        """The number of crossings `surface_points` with the same options would keep -> counts [B] i32 on the device.  It only counts
+        (the volume is read once); no host synchronisation."""
+        B, w_min, max_jump, nbytes = self._surface_args(w_min, max_jump)
+        counts = torch.empty(B, dtype=torch.int32, device=self.volume.device)
+        self._surface(w_min, max_jump, nbytes, None, counts)
+        return counts
+
+    def surface_points(self, capacity: Optional[int] = None, w_min: float = 0.0, max_jump: Optional[float] = None, normals: bool = True,
+                       out: Optional[SurfacePoints] = None) -> SurfacePoints:
+        """The map as oriented points in the WORLD frame (`cfp_tsdf_surface`): one point per edge of the voxel lattice along which F
+        changes sign between two observed voxels, in the order of the edge index 3 * voxel + axis, with the normal (the gradient of F,
+        towards the free space the camera saw the surface from: R times it is the raycast's normal) and the std 1 / sqrt(Wt) blended
+        along the edge.  `w_min`: both voxels have at least this weight; `max_jump` (None: no filter): |F(p) - F(q)| is at most this --
+        2 * voxel / trunc is what a clean surface gives, more is an edge between a surface and something fused behind it.  With an
+        explicit `capacity` (rows per image) nothing synchronises with the host -- `counts` still reports the true numbers and `split()`
+        raises on overflow -- and `out`, the result of an earlier call with the same capacity and normals, reuses every buffer, so the
+        call can be captured in a graph after `integrate`.  `capacity=None` counts first, reads the largest count in one host
+        synchronisation and allocates exactly that (at least 1).  After `Tracker.update` has run over a sequence the map is
+        `tracker.volume.surface_points()`.  Bitwise reproducible."""
+        B, w_min, max_jump, nbytes = self._surface_args(w_min, max_jump)
+        dev = self.volume.device
+        if out is not None:
+            if not isinstance(out, SurfacePoints) or (capacity is not None and out.capacity != int(capacity)) or \
+                    (out.normals is not None) != bool(normals):
+                raise ValueError("out must be the SurfacePoints of a call with the same capacity and normals")
+            cap = out.capacity
+            _check_out(out.points, (B, cap, 3), torch.float32, "out.points")
+            _check_out(out.std, (B, cap), torch.float32, "out.std")
+            _check_out(out.index, (B, cap), torch.int32, "out.index")
+            _check_out(out.counts, (B,), torch.int32, "out.counts")
+            if normals:
+                _check_out(out.normals, (B, cap, 3), torch.float32, "out.normals")
+            res = out
+        else:
+            if capacity is None:
+                cap = max(int(self.surface_count(w_min, max_jump).max()), 1)              # the one host synchronisation
+            else:
+                cap = int(capacity)
+                if cap < 1:
+                    raise ValueError(f"capacity must be at least 1, got {cap}")
+            res = SurfacePoints(torch.empty(B, cap, 3, dtype=torch.float32, device=dev),
+                                torch.empty(B, cap, 3, dtype=torch.float32, device=dev) if normals else None,
+                                torch.empty(B, cap, dtype=torch.float32, device=dev), torch.empty(B, cap, dtype=torch.int32, device=dev),
+                                torch.empty(B, dtype=torch.int32, device=dev), cap)
+        self._surface(w_min, max_jump, nbytes, res, res.counts)
+        return res
+
+    def write_ply(self, path_pattern: str, **options) -> List[int]:
+        """One binary PLY per image (xyz and, unless `normals=False`, the normals) through `pointcloud.write_ply`: image b goes to
+        `path_pattern.format(b)` -- a pattern without a field is used as it is for a single image.  `options` are those of
+        `surface_points`.  Host side after one synchronisation.  Returns the vertex counts."""
+        parts = self.surface_points(**options).split()
+        paths = [path_pattern.format(b) for b in range(len(parts))]
+        if len(set(paths)) != len(paths):
+            raise ValueError(f"path_pattern {path_pattern!r} names the same file for several images: put a {{}} field into it")
+        return [write_ply(path, part["points"], part["normals"]) for path, part in zip(paths, parts)]

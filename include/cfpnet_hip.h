@@ -882,6 +882,39 @@ int cfp_tsdf_raycast(const float* volume /* [B][Dz][Dy][Dx][2] */, int Dx, int D
                      float t_min, float t_max, float step, float* depth /* [B][Hd][Wd] */, float* normal /* [B][Hd][Wd][3] or NULL */,
                      float* std /* [B][Hd][Wd] or NULL */, cfp_stream_t stream);
 
+/* The map out of the volume: the zero crossings of F along the edges of the voxel lattice of a cfp_tsdf_integrate volume, as oriented
+ * points in the WORLD frame.  Voxel (i, j, k) has index n = (k * Dy + j) * Dx + i and its centre at (ox + voxel * (float)i,
+ * oy + voxel * (float)j, oz + voxel * (float)k), the expressions of cfp_tsdf_integrate.  Float32 in the order written here, no fused
+ * multiply-add: every discrete decision is a comparison of float32 values in memory or one correctly rounded float32 operation.
+ *   Candidates  edge e = 3 * n + a for axis a = 0 / 1 / 2 = +x / +y / +z runs from voxel p = n to q = p + e_a; candidates are numbered by
+ *           e ascending (voxel-major, then axis).  An edge whose q is outside the grid is never kept.
+ *   Kept    iff  Wt(p) > 0 && Wt(q) > 0 && Wt(p) >= w_min && Wt(q) >= w_min
+ *           and  (F(p) < 0 && F(q) >= 0) || (F(p) >= 0 && F(q) < 0)          (-0.0 counts as non-negative, a NaN F never crosses)
+ *           and  fabsf(F(p) - F(q)) <= max_jump                              (max_jump = +inf: no filter)
+ *   Point   t = F(p) / (F(p) - F(q));  the coordinate along a is  o_a + voxel * ((float)idx_a + t),  the other two are the centre's.
+ *   Std     1 / sqrtf((1 - t) * Wt(p) + t * Wt(q))
+ *   Normal  the central difference of F at a voxel along axis c is F(+1) - F(-1), valid only if both neighbours are in the grid with
+ *           Wt > 0;  g = (1 - t) * g(p) + t * g(q) per component;  len = sqrtf((gx * gx + gy * gy) + gz * gz);  n = g / len if all six
+ *           differences are valid, len > 0 and len is finite, otherwise (NaN, NaN, NaN).  It points towards increasing F -- towards the
+ *           free space the observing camera was in: the world-frame counterpart of the raycast's normal (R times it is what
+ *           cfp_tsdf_raycast writes).
+ *   Outputs per image, rows r < min(count, cap) in candidate order: points [B][cap][3] f32; normals [B][cap][3] f32 or NULL; std
+ *           [B][cap] f32 or NULL; index [B][cap] i32 holding e; counts [B] i32: the true number kept, also when it exceeds cap.  Rows
+ *           at or beyond min(count, cap) are not written.  points == NULL (then index, normals and std are NULL too): the call only
+ *           counts.
+ * Refused before anything is dereferenced: a null volume, counts or ws; points without index; normals or std without points;
+ * non-positive dimensions; 3 * Dx * Dy * Dz >= 2^31 (the edge index is an int32) or B > 65535; a non-finite origin; voxel not positive
+ * and finite; w_min or max_jump negative or NaN; cap < 1 with points; a volume or workspace that is not 8-byte aligned; a workspace
+ * smaller than cfp_tsdf_surface_ws_bytes(B, Dx, Dy, Dz) (0 for arguments that make no sense).
+ * Count per chunk of 256 voxels, exclusive scan per image in two levels, scatter -- four launches and no atomics: the order and every bit
+ * are a function of the volume alone.  Nothing is zeroed (every word of the workspace is written before it is read).  No host
+ * synchronisation, no allocation; capturable in a graph. */
+size_t cfp_tsdf_surface_ws_bytes(int B, int Dx, int Dy, int Dz);
+int cfp_tsdf_surface(const float* volume /* [B][Dz][Dy][Dx][2] */, int Dx, int Dy, int Dz, int B, float ox, float oy, float oz,
+                     float voxel, float w_min, float max_jump, int cap, float* points /* [B][cap][3] or NULL */,
+                     float* normals /* [B][cap][3] or NULL */, float* std /* [B][cap] or NULL */, int* index /* [B][cap] or NULL */,
+                     int* counts /* [B] */, void* ws, size_t ws_bytes, cfp_stream_t stream);
+
 /* Camera tracking: one Gauss-Newton iteration of dense point-to-plane ICP of a frame against a model map, per image, without leaving the
  * device -- projective data association, the 6 x 6 normal equations weighted by the two variances, the solve and the pose update.  The
  * frame is the prediction and its std; the model is a depth / normal / std map in the MODEL camera: a cfp_tsdf_raycast (frame-to-model
