@@ -9,6 +9,11 @@
 // through LDS in a fixed tree, and leave as one INTEGER atomic add per workgroup and count onto a word a first launch has zeroed -- an
 // integer sum does not depend on the order of arrival, so two launches give identical bits.
 //
+// Integrate with colour (cfp_tsdf_integrate_rgb) is the same kernel with COLOR = true: a voxel the geometry step has updated and that lies
+// within trunc of the surface reads the three planes of the image at the pixel its depth came from and folds them into its (R, G, B, Wc)
+// entry of the colour volume -- one 16-byte load and one 16-byte store, 1 KB contiguous per wave -- and a fourth count joins the three.
+// The COLOR = false instance is the kernel cfp_tsdf_integrate has always launched.
+//
 // Raycast.  A workgroup owns a 16 x 16 pixel tile (a wave four rows of 16), so that neighbouring rays walk through the same cells and
 // their 8-corner gathers hit the same lines.  Every sample reads its corners as float2 (F, Wt).  The march may skip the part of the ray
 // that cannot touch the volume's box; the skipped samples are ones the per-sample test would call invalid anyway.
@@ -36,6 +41,8 @@ struct IntegrateP {
   FastDiv div_x, div_xy;
   float ox, oy, oz, voxel, trunc, z_near, w_max, std_floor;
   int* counts;
+  const float* rgb; float4* color;                    // COLOR only: the image [B][3][H][W], the colour volume, c = x * cstd + mean
+  float mean[3], cstd[3];
 };
 
 // counts are zeroed by a launch of the library's own: a captured hipMemsetAsync of these B * 12 bytes (not a multiple of 8) came back from
@@ -44,8 +51,10 @@ __global__ __launch_bounds__(256) void tsdf_zero_counts_kernel(int* __restrict__
   for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) counts[i] = 0;
 }
 
+template <bool COLOR>
 __global__ __launch_bounds__(256) void tsdf_integrate_kernel(IntegrateP p) {
-  __shared__ int s[3][256];
+  constexpr int kCounts = COLOR ? 4 : 3;
+  __shared__ int s[kCounts][256];
   const MetP& m = p.m;
   const int b = blockIdx.y;
   const unsigned nvox = (unsigned)p.Dx * p.Dy * p.Dz;            // < 2^31
@@ -53,17 +62,44 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(IntegrateP p) {
   const float* sb = p.u.pred ? p.u.pred + (long long)b * p.std_stride : nullptr;
   const float* K = p.K + b * 4;
   const float* T = p.T + b * 12;
-  const float fx = K[0], fy = K[1], cx = K[2], cy = K[3];
+  float fx = K[0], fy = K[1], cx = K[2], cy = K[3];
   float2* vol = p.volume + (long long)b * nvox;
-  int seen = 0, updated = 0, behind = 0;
+  int seen = 0, updated = 0, behind = 0, coloured = 0;
+  // The plain kernel fills the scalar register file to the brim, and the colour step's extra branches and pointers made the compiler
+  // spill scalars.  The COLOR instance therefore holds its launch constants -- camera, pose, volume frame, image and colour volume -- in
+  // vector registers (the empty asm's "+v"), of which it has plenty: 72 of 512 / 7 waves.  The plain instance compiles as before.
+  float cm[3] = {0.f, 0.f, 0.f}, cs[3] = {1.f, 1.f, 1.f};
+  const float* rgb = nullptr; float4* cvol = nullptr;
+  int plane = 0;
+  float ox = p.ox, oy = p.oy, oz = p.oz, voxel = p.voxel, trunc = p.trunc, w_max = p.w_max;
+  float tv[12] = {};
+  auto Tat = [&](int e) { if constexpr (COLOR) return tv[e]; else return T[e]; };
+  if constexpr (COLOR) {
+    asm volatile("" : "+v"(fx), "+v"(fy), "+v"(cx), "+v"(cy));
+    asm volatile("" : "+v"(ox), "+v"(oy), "+v"(oz), "+v"(voxel), "+v"(trunc), "+v"(w_max));
+#pragma unroll
+    for (int e = 0; e < 12; ++e) {
+      tv[e] = T[e];
+      asm volatile("" : "+v"(tv[e]));
+    }
+    plane = m.H * m.W;                                // < 2^31 - 256
+    rgb = p.rgb + (long long)b * 3 * plane;
+    cvol = p.color + (long long)b * nvox;
+    asm volatile("" : "+v"(rgb), "+v"(cvol), "+v"(plane));
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      cm[c] = p.mean[c]; cs[c] = p.cstd[c];
+      asm volatile("" : "+v"(cm[c]), "+v"(cs[c]));
+    }
+  }
   for (long long n64 = (long long)blockIdx.x * 256 + threadIdx.x; n64 < nvox; n64 += (long long)gridDim.x * 256) {
     const unsigned n = (unsigned)n64;
     const unsigned k = fd_div(n, p.div_xy), r = n - k * p.div_xy.d;
     const unsigned j = fd_div(r, p.div_x), i = r - j * p.div_x.d;
-    const float Xw = p.ox + p.voxel * (float)i, Yw = p.oy + p.voxel * (float)j, Zw = p.oz + p.voxel * (float)k;
-    const float Xc = (T[0] * Xw + T[1] * Yw) + T[2] * Zw + T[3];
-    const float Yc = (T[4] * Xw + T[5] * Yw) + T[6] * Zw + T[7];
-    const float Zc = (T[8] * Xw + T[9] * Yw) + T[10] * Zw + T[11];
+    const float Xw = ox + voxel * (float)i, Yw = oy + voxel * (float)j, Zw = oz + voxel * (float)k;
+    const float Xc = (Tat(0) * Xw + Tat(1) * Yw) + Tat(2) * Zw + Tat(3);
+    const float Yc = (Tat(4) * Xw + Tat(5) * Yw) + Tat(6) * Zw + Tat(7);
+    const float Zc = (Tat(8) * Xw + Tat(9) * Yw) + Tat(10) * Zw + Tat(11);
     if (!(finitef(Zc) && Zc >= p.z_near)) continue;
     const float uu = fx * (Xc / Zc) + cx, vv = fy * (Yc / Zc) + cy;
     const float col = floorf(uu + 0.5f), row = floorf(vv + 0.5f);
@@ -73,8 +109,8 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(IntegrateP p) {
     if (!(finitef(d) && d > 0.f)) continue;
     seen += 1;
     const float sdf = d - Zc;
-    if (sdf < -p.trunc) { behind += 1; continue; }
-    const float f = fminf(1.f, sdf / p.trunc);
+    if (sdf < -trunc) { behind += 1; continue; }
+    const float f = fminf(1.f, sdf / trunc);
     float w = 1.f;
     if (sb) {
       const float sd = met_plane(p.u, sb, pix);
@@ -84,19 +120,31 @@ __global__ __launch_bounds__(256) void tsdf_integrate_kernel(IntegrateP p) {
     if (!(w > 0.f && w < INFINITY)) continue;                    // an infinite std observes nothing
     const float2 fw = vol[n];
     const float tot = fw.y + w;
-    vol[n] = make_float2((fw.x * fw.y + f * w) / tot, fminf(tot, p.w_max));
+    vol[n] = make_float2((fw.x * fw.y + f * w) / tot, fminf(tot, w_max));
     updated += 1;
+    if constexpr (COLOR) {
+      if (sdf > trunc) continue;                                 // free space in front of the surface takes no colour
+      const float* cb = rgb + pix;
+      const float c0 = cb[0] * cs[0] + cm[0], c1 = cb[plane] * cs[1] + cm[1], c2 = cb[2ll * plane] * cs[2] + cm[2];
+      if (!(finitef(c0) && finitef(c1) && finitef(c2))) continue;
+      const float4 cw = cvol[n];
+      const float ctot = cw.w + w;
+      cvol[n] = make_float4((cw.x * cw.w + c0 * w) / ctot, (cw.y * cw.w + c1 * w) / ctot, (cw.z * cw.w + c2 * w) / ctot, fminf(ctot, w_max));
+      coloured += 1;
+    }
   }
   s[0][threadIdx.x] = seen; s[1][threadIdx.x] = updated; s[2][threadIdx.x] = behind;
+  if constexpr (COLOR) s[3][threadIdx.x] = coloured;
   __syncthreads();
 #pragma unroll
   for (int o = 128; o > 0; o >>= 1) {
     if ((int)threadIdx.x < o) {
       s[0][threadIdx.x] += s[0][threadIdx.x + o]; s[1][threadIdx.x] += s[1][threadIdx.x + o]; s[2][threadIdx.x] += s[2][threadIdx.x + o];
+      if constexpr (COLOR) s[3][threadIdx.x] += s[3][threadIdx.x + o];
     }
     __syncthreads();
   }
-  if (threadIdx.x < 3 && s[threadIdx.x][0] != 0) atomicAdd(p.counts + b * 3 + threadIdx.x, s[threadIdx.x][0]);
+  if (threadIdx.x < kCounts && s[threadIdx.x][0] != 0) atomicAdd(p.counts + b * kCounts + threadIdx.x, s[threadIdx.x][0]);
 }
 
 struct RaycastP {
@@ -231,33 +279,33 @@ __global__ __launch_bounds__(kTile * kTile) void tsdf_raycast_kernel(RaycastP p)
 
 bool pos_finite(float v) { return v > 0.f && v < INFINITY; }      // false for NaN
 
-}  // namespace
-
-extern "C" int cfp_tsdf_integrate(const float* pred, int Hp, int Wp, int H, int W, int B, int interpolate, float lo, float hi,
-                                  const float* std, int Hu, int Wu, long long std_stride, float std_floor, const float* K, const float* T,
-                                  float* volume, int Dx, int Dy, int Dz, float ox, float oy, float oz, float voxel, float trunc,
-                                  float z_near, float w_max, int* counts, cfp_stream_t stream) {
-  CFP_REQUIRE(pred && K && T && volume && counts, CFP_EINVAL, "cfp_tsdf_integrate: null pointer");
-  CFP_REQUIRE(B > 0 && Hp > 0 && Wp > 0 && H > 0 && W > 0 && Dx > 0 && Dy > 0 && Dz > 0, CFP_ESHAPE,
-              "cfp_tsdf_integrate: non-positive dimension");
+// cfp_tsdf_integrate and cfp_tsdf_integrate_rgb: one set of checks (`who` names the caller in the message) and one launch; rgb != null
+// selects the COLOR instance, whose mean, cstd and color the caller has checked
+int integrate_launch(const char* who_, const float* pred, int Hp, int Wp, int H, int W, int B, int interpolate, float lo, float hi,
+                     const float* std, int Hu, int Wu, long long std_stride, float std_floor, const float* K, const float* T, float* volume,
+                     int Dx, int Dy, int Dz, float ox, float oy, float oz, float voxel, float trunc, float z_near, float w_max,
+                     const float* rgb, const float* mean, const float* cstd, float* color, int* counts, cfp_stream_t stream) {
+  const std::string who(who_);
+  CFP_REQUIRE(pred && K && T && volume && counts, CFP_EINVAL, who + ": null pointer");
+  CFP_REQUIRE(B > 0 && Hp > 0 && Wp > 0 && H > 0 && W > 0 && Dx > 0 && Dy > 0 && Dz > 0, CFP_ESHAPE, who + ": non-positive dimension");
   CFP_REQUIRE((long long)H * W < (1ll << 31) - 256 && (long long)Hp * Wp < (1ll << 31) && H <= kMaxDim && W <= kMaxDim && B <= 65535,
-              CFP_ESHAPE, "cfp_tsdf_integrate: image or batch too large");
+              CFP_ESHAPE, who + ": image or batch too large");
   CFP_REQUIRE(Dx <= kMaxDim && Dy <= kMaxDim && Dz <= kMaxDim && (long long)Dx * Dy < (1ll << 31) &&
-                  (long long)Dx * Dy * Dz < (1ll << 31) - 256, CFP_ESHAPE, "cfp_tsdf_integrate: volume too large");
-  CFP_REQUIRE(interpolate || (Hp == H && Wp == W), CFP_ESHAPE, "cfp_tsdf_integrate: sizes differ and interpolate is off");
-  CFP_REQUIRE(lo < hi, CFP_EINVAL, "cfp_tsdf_integrate: empty depth range");
+                  (long long)Dx * Dy * Dz < (1ll << 31) - 256, CFP_ESHAPE, who + ": volume too large");
+  CFP_REQUIRE(interpolate || (Hp == H && Wp == W), CFP_ESHAPE, who + ": sizes differ and interpolate is off");
+  CFP_REQUIRE(lo < hi, CFP_EINVAL, who + ": empty depth range");
   if (std) {
-    CFP_REQUIRE(Hu > 0 && Wu > 0, CFP_ESHAPE, "cfp_tsdf_integrate: non-positive dimension (std)");
-    CFP_REQUIRE((long long)Hu * Wu < (1ll << 31), CFP_ESHAPE, "cfp_tsdf_integrate: std plane too large");
-    CFP_REQUIRE(std_stride >= 0, CFP_EINVAL, "cfp_tsdf_integrate: negative std image stride");
+    CFP_REQUIRE(Hu > 0 && Wu > 0, CFP_ESHAPE, who + ": non-positive dimension (std)");
+    CFP_REQUIRE((long long)Hu * Wu < (1ll << 31), CFP_ESHAPE, who + ": std plane too large");
+    CFP_REQUIRE(std_stride >= 0, CFP_EINVAL, who + ": negative std image stride");
   }
-  CFP_REQUIRE(pos_finite(std_floor), CFP_EINVAL, "cfp_tsdf_integrate: std_floor must be positive and finite");
-  CFP_REQUIRE(pos_finite(voxel), CFP_EINVAL, "cfp_tsdf_integrate: voxel must be positive and finite");
-  CFP_REQUIRE(pos_finite(trunc), CFP_EINVAL, "cfp_tsdf_integrate: trunc must be positive and finite");
-  CFP_REQUIRE(pos_finite(z_near), CFP_EINVAL, "cfp_tsdf_integrate: z_near must be positive and finite");
-  CFP_REQUIRE(pos_finite(w_max), CFP_EINVAL, "cfp_tsdf_integrate: w_max must be positive and finite");
-  CFP_REQUIRE(std::isfinite(ox) && std::isfinite(oy) && std::isfinite(oz), CFP_EINVAL, "cfp_tsdf_integrate: origin must be finite");
-  CFP_REQUIRE((reinterpret_cast<uintptr_t>(volume) & 7) == 0, CFP_EINVAL, "cfp_tsdf_integrate: volume must be 8-byte aligned");
+  CFP_REQUIRE(pos_finite(std_floor), CFP_EINVAL, who + ": std_floor must be positive and finite");
+  CFP_REQUIRE(pos_finite(voxel), CFP_EINVAL, who + ": voxel must be positive and finite");
+  CFP_REQUIRE(pos_finite(trunc), CFP_EINVAL, who + ": trunc must be positive and finite");
+  CFP_REQUIRE(pos_finite(z_near), CFP_EINVAL, who + ": z_near must be positive and finite");
+  CFP_REQUIRE(pos_finite(w_max), CFP_EINVAL, who + ": w_max must be positive and finite");
+  CFP_REQUIRE(std::isfinite(ox) && std::isfinite(oy) && std::isfinite(oz), CFP_EINVAL, who + ": origin must be finite");
+  CFP_REQUIRE((reinterpret_cast<uintptr_t>(volume) & 7) == 0, CFP_EINVAL, who + ": volume must be 8-byte aligned");
   IntegrateP p;
   p.m = met_params(pred, nullptr, Hp, Wp, H, W, B, interpolate, 0, lo, hi);
   p.u = met_params(std, nullptr, std ? Hu : H, std ? Wu : W, H, W, B, std && (Hu != H || Wu != W) ? 1 : 0, 0, 0.f, 0.f);
@@ -268,11 +316,39 @@ extern "C" int cfp_tsdf_integrate(const float* pred, int Hp, int Wp, int H, int 
   p.div_x = make_fastdiv((unsigned)Dx); p.div_xy = make_fastdiv((unsigned)Dx * (unsigned)Dy);
   p.ox = ox; p.oy = oy; p.oz = oz; p.voxel = voxel; p.trunc = trunc; p.z_near = z_near; p.w_max = w_max; p.std_floor = std_floor;
   p.counts = counts;
+  p.rgb = rgb; p.color = reinterpret_cast<float4*>(color);
+  for (int c = 0; c < 3; ++c) { p.mean[c] = rgb ? mean[c] : 0.f; p.cstd[c] = rgb ? cstd[c] : 1.f; }      // the host pointers of the call
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const long long nvox = (long long)Dx * Dy * Dz;
-  hipLaunchKernelGGL(tsdf_zero_counts_kernel, dim3(cdiv(B * 3, 256)), dim3(256), 0, s, counts, B * 3);
-  hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)std::min<long long>((nvox + 255) / 256, kMaxBlocks), B), dim3(256), 0, s, p);
-  return cfp_check_launch("cfp_tsdf_integrate");
+  const int ncounts = B * (rgb ? 4 : 3);
+  const dim3 grid((unsigned)std::min<long long>((nvox + 255) / 256, kMaxBlocks), B);
+  hipLaunchKernelGGL(tsdf_zero_counts_kernel, dim3(cdiv(ncounts, 256)), dim3(256), 0, s, counts, ncounts);
+  if (rgb) hipLaunchKernelGGL(tsdf_integrate_kernel<true>, grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(tsdf_integrate_kernel<false>, grid, dim3(256), 0, s, p);
+  return cfp_check_launch(who_);
+}
+
+}  // namespace
+
+extern "C" int cfp_tsdf_integrate(const float* pred, int Hp, int Wp, int H, int W, int B, int interpolate, float lo, float hi,
+                                  const float* std, int Hu, int Wu, long long std_stride, float std_floor, const float* K, const float* T,
+                                  float* volume, int Dx, int Dy, int Dz, float ox, float oy, float oz, float voxel, float trunc,
+                                  float z_near, float w_max, int* counts, cfp_stream_t stream) {
+  return integrate_launch("cfp_tsdf_integrate", pred, Hp, Wp, H, W, B, interpolate, lo, hi, std, Hu, Wu, std_stride, std_floor, K, T, volume,
+                          Dx, Dy, Dz, ox, oy, oz, voxel, trunc, z_near, w_max, nullptr, nullptr, nullptr, nullptr, counts, stream);
+}
+
+extern "C" int cfp_tsdf_integrate_rgb(const float* pred, int Hp, int Wp, int H, int W, int B, int interpolate, float lo, float hi,
+                                      const float* std, int Hu, int Wu, long long std_stride, float std_floor, const float* K,
+                                      const float* T, float* volume, int Dx, int Dy, int Dz, float ox, float oy, float oz, float voxel,
+                                      float trunc, float z_near, float w_max, const float* rgb, const float* mean, const float* cstd,
+                                      float* color, int* counts, cfp_stream_t stream) {
+  CFP_REQUIRE(rgb && mean && cstd && color, CFP_EINVAL, "cfp_tsdf_integrate_rgb: null pointer");
+  for (int c = 0; c < 3; ++c)
+    CFP_REQUIRE(std::isfinite(mean[c]) && std::isfinite(cstd[c]), CFP_EINVAL, "cfp_tsdf_integrate_rgb: mean and cstd must be finite");
+  CFP_REQUIRE(aligned16(color), CFP_EINVAL, "cfp_tsdf_integrate_rgb: color must be 16-byte aligned");
+  return integrate_launch("cfp_tsdf_integrate_rgb", pred, Hp, Wp, H, W, B, interpolate, lo, hi, std, Hu, Wu, std_stride, std_floor, K, T,
+                          volume, Dx, Dy, Dz, ox, oy, oz, voxel, trunc, z_near, w_max, rgb, mean, cstd, color, counts, stream);
 }
 
 extern "C" int cfp_tsdf_raycast(const float* volume, int Dx, int Dy, int Dz, int B, float ox, float oy, float oz, float voxel,

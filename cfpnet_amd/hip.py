@@ -103,6 +103,10 @@ SIGNATURES = {
     "cfp_depth_fuse": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _i, _i, _ll, _f, _p, _p, _f, _f, _f, _p, _p, _p, _p, _p, _sz, _p]),
     "cfp_tsdf_integrate": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _i, _i, _ll, _f, _p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _p, _p]),
     "cfp_tsdf_raycast": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, _p, _p, _i, _i, _f, _f, _f, _p, _p, _p, _p]),
+    "cfp_tsdf_integrate_rgb": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _i, _i, _ll, _f, _p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _f, _f, _f, _p,
+                                    C.POINTER(C.c_float), C.POINTER(C.c_float), _p, _p, _p]),
+    "cfp_tsdf_shade": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, _p, _p, _i, _i, _p, _p, _p]),
+    "cfp_tsdf_surface_rgb": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _i, _p, _p]),
     "cfp_tsdf_surface_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "cfp_tsdf_surface": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "cfp_icp_ws_bytes": (_sz, [_i, _i, _i, _i]),

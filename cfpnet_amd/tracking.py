@@ -20,7 +20,7 @@ from typing import NamedTuple, Optional, Sequence
 import numpy as np
 import torch
 
-from . import hip
+from . import hip, render
 from .pointcloud import _check_out, _intrinsics, _pred3, _size
 from .temporal import _pose, _std_plane, _ws
 from .tsdf import TsdfVolume
@@ -203,9 +203,8 @@ class Tracker:
         `unc` against the volume as it is; `.stats` [iters,B,6] is `icp`'s.  Stores nothing: `.pose` and the volume stay."""
         return self._track(pred, unc).world
 
-    def update(self, pred: torch.Tensor, unc: Optional[torch.Tensor] = None, integrate: bool = True):
-        """`track`, the pose stored in `.pose` (a device copy), the frame integrated at it -> (pose [B,3,4], stats [iters,B,6]).  The
-        first call (and the first after `reset`) integrates at `pose0` without tracking and returns stats None."""
+    def _update(self, pred, unc, integrate, fuse):
+        """`update` and `update_rgb`: `fuse(pose)` integrates the frame."""
         if not self._primed:
             pred = _pred3(pred)
             B = pred.shape[0]
@@ -213,12 +212,25 @@ class Tracker:
             if self.pose is None or self.pose.shape[0] != B:
                 self.pose = torch.empty(B, 3, 4, dtype=torch.float32, device=pred.device)
             self.pose.copy_(T0)
-            self.volume.integrate(pred, unc, self.pose)
+            fuse(self.pose)
             self._primed = True
             self.stats = None
             return self.pose, None
         res = self._track(pred, unc)
         self.pose.copy_(res.world)
         if integrate:
-            self.volume.integrate(pred, unc, self.pose)
+            fuse(self.pose)
         return self.pose, res.stats
+
+    def update(self, pred: torch.Tensor, unc: Optional[torch.Tensor] = None, integrate: bool = True):
+        """`track`, the pose stored in `.pose` (a device copy), the frame integrated at it -> (pose [B,3,4], stats [iters,B,6]).  The
+        first call (and the first after `reset`) integrates at `pose0` without tracking and returns stats None."""
+        return self._update(pred, unc, integrate, lambda pose: self.volume.integrate(pred, unc, pose))
+
+    def update_rgb(self, pred: torch.Tensor, rgb: torch.Tensor, unc: Optional[torch.Tensor] = None, integrate: bool = True,
+                   mean=render.IMAGENET_MEAN, std=render.IMAGENET_STD):
+        """`update` with the frame's image: the frame is integrated by `TsdfVolume.integrate_rgb(pred, rgb, unc, pose, mean, std)`, so the
+        map takes the colour along -- `volume.write_ply(pattern, colors=True)` afterwards is the coloured room.  Tracking itself does
+        not look at the image: the poses are those of `update`."""
+        rgb = render._rgb4(rgb)                                           # refuse a bad image before the frame is tracked
+        return self._update(pred, unc, integrate, lambda pose: self.volume.integrate_rgb(pred, rgb, unc, pose, mean, std))

@@ -7,6 +7,11 @@ pixel), `raycast` turns the volume back into depth, std and normals in any view 
 something a third can look at, and `surface_points` takes the map out: the zero crossings of F along the voxel lattice's edges as oriented
 points in the world frame (`cfp_tsdf_surface`, `csrc/tsdf_surface.hip`), which `write_ply` stores.  The arithmetic is
 `csrc/tsdf.hip` (definition in include/cfpnet_hip.h); nothing here computes on the CPU except the PLY writer.
+
+Colour: `integrate_rgb` fuses the frame's RGB image -- the model's own input, already on the device at the grid's size --
+into a second volume `.color` of (R, G, B, Wc) per voxel by the same inverse-variance weights (`cfp_tsdf_integrate_rgb`, the same kernel
+as `integrate`), `shade` gives the colour image that belongs to a raycast (`cfp_tsdf_shade`), `surface_colors` the colours of the
+extracted points (`cfp_tsdf_surface_rgb`, both `csrc/tsdf_color.hip`), and `write_ply(..., colors=True)` stores them.
 """
 from __future__ import annotations
 
@@ -15,11 +20,12 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from . import hip
+from . import hip, render
 from .pointcloud import _check_out, _intrinsics, _pred3, _size, write_ply
 from .temporal import _pose, _std_plane
 
 COUNT_NAMES = ("seen", "updated", "behind")           # columns of `counts` (CFP_TSDF_*)
+COLOR_COUNT_NAMES = COUNT_NAMES + ("coloured",)       # columns of `color_counts`
 _F32_MAX = 3.4028234663852886e38                      # the library wants a finite cap: "no cap" is the largest float32
 
 
@@ -34,22 +40,24 @@ class SurfacePoints:
     """Result of `TsdfVolume.surface_points`, everything on the device: `points` [B,cap,3] f32 in the world frame, `normals` [B,cap,3]
     f32 or None (towards the free space the observing camera was in; NaN where the volume does not know), `std` [B,cap] f32, `index`
     [B,cap] i32 (the lattice edge 3 * voxel + axis a row came from), `counts` [B] i32 -- the number of crossings per image, also when it
-    exceeds `capacity`.  Rows at or beyond min(count, capacity) hold nothing of meaning."""
+    exceeds `capacity`.  Rows at or beyond min(count, capacity) hold nothing of meaning.  `colors` [B,cap,3] f32 or None: what
+    `TsdfVolume.surface_colors` wrote (NaN where the map has no colour)."""
 
-    def __init__(self, points, normals, std, index, counts, capacity: int):
+    def __init__(self, points, normals, std, index, counts, capacity: int, colors=None):
         self.points, self.normals, self.std, self.index, self.counts = points, normals, std, index, counts
         self.capacity = capacity
+        self.colors = colors
 
     def split(self) -> List[dict]:
-        """The one host synchronisation: per image {"points": [n,3], "normals", "std", "index"} trimmed to its count (None where
-        absent).  Raises if an image has more crossings than `capacity`."""
+        """The one host synchronisation: per image {"points": [n,3], "normals", "std", "index", "colors"} trimmed to its count (None
+        where absent).  Raises if an image has more crossings than `capacity`."""
         counts = self.counts.cpu().tolist()
         over = [(b, n) for b, n in enumerate(counts) if n > self.capacity]
         if over:
             raise RuntimeError(f"surface_points overflow: (image, kept) = {over} exceeds capacity {self.capacity}")
         trim = lambda t, b, n: None if t is None else t[b, :n]
         return [{"points": trim(self.points, b, n), "normals": trim(self.normals, b, n), "std": trim(self.std, b, n),
-                 "index": trim(self.index, b, n)} for b, n in enumerate(counts)]
+                 "index": trim(self.index, b, n), "colors": trim(self.colors, b, n)} for b, n in enumerate(counts)]
 
 
 class TsdfVolume:
@@ -92,8 +100,11 @@ class TsdfVolume:
             _intrinsics(intrinsics, 1, "cpu")                             # refuse bad numbers now, not at the first frame
         self.intrinsics, self.size = intrinsics, size
         self.volume = self.counts = None
+        self.color_counts = None
+        self._color = None
         self._shape = None
         self._rays = {}
+        self._shades = {}
         self._surface_ws = None
 
     @property
@@ -106,11 +117,19 @@ class TsdfVolume:
         """(H, W) of the grid the predictions are seen on; None before the first integrate.  Read-only."""
         return None if self._shape is None else self._hw
 
+    @property
+    def color(self) -> Optional[torch.Tensor]:
+        """The colour volume [B,Dz,Dy,Dx,4] f32, (R, G, B, Wc) per voxel, on the device; None before the first `integrate_rgb`.
+        Read-only."""
+        return self._color
+
     def reset(self):
-        """Empty the volume: F = 1, Wt = 0.  The buffers stay."""
+        """Empty the volume: F = 1, Wt = 0, and the colour volume, if there is one: (0, 0, 0, 0).  The buffers stay."""
         if self.volume is not None:
             self.volume[..., 0] = 1.0
             self.volume[..., 1] = 0.0
+        if self._color is not None:
+            self._color.zero_()
 
     def _allocate(self, B, h, w, dev):
         Dx, Dy, Dz = self.dims
@@ -119,7 +138,10 @@ class TsdfVolume:
         self._K = _intrinsics(self.intrinsics, B, dev)
         self.volume = torch.empty(B, Dz, Dy, Dx, 2, dtype=torch.float32, device=dev)
         self.counts = torch.zeros(B, 3, dtype=torch.int32, device=dev)
+        self.color_counts = None
+        self._color = None
         self._rays = {}
+        self._shades = {}
         self._surface_ws = None
         self.reset()
 
@@ -141,6 +163,38 @@ class TsdfVolume:
                  self.std_floor, self._K.data_ptr(), T.data_ptr(), self.volume.data_ptr(), Dx, Dy, Dz, *self.origin, self.voxel,
                  self.trunc, self.z_near, self.w_max, self.counts.data_ptr(), hip.current_stream())
         return self.counts
+
+    def integrate_rgb(self, pred: torch.Tensor, rgb: torch.Tensor, unc: Optional[torch.Tensor] = None, pose=None,
+                      mean=render.IMAGENET_MEAN, std=render.IMAGENET_STD) -> torch.Tensor:
+        """`integrate`, and the frame's colour with it in the same pass (`cfp_tsdf_integrate_rgb`): `rgb` [B,3,H,W] f32 on the device is
+        the normalised image on the volume's (H, W) grid -- the model's input -- and c = rgb * std + mean is fused into `.color` by the
+        weights of the geometry, at the voxels within `trunc` of the surface -> counts [B,4] i32 in `COLOR_COUNT_NAMES` order, on the
+        device: `.color_counts`, a buffer of its own (`.counts` is not written).  (F, Wt) and the first three counts are bit for bit
+        what `integrate` gives.  The first call allocates the colour volume (zeros); frames with and without an image mix freely, the
+        colour keeps its own weight Wc.  No host synchronisation; capturable like `integrate`."""
+        rgb = render._rgb4(rgb)
+        pred = _pred3(pred)
+        B, h, w = pred.shape
+        H, W = _size(self.size, h, w)
+        if tuple(rgb.shape) != (B, 3, H, W):
+            raise ValueError(f"rgb must be [B,3,H,W] = {(B, 3, H, W)}, the volume's grid, got {tuple(rgb.shape)}")
+        if rgb.device != pred.device:
+            raise ValueError("rgb and pred must be on the same device")
+        m, s = render._three(mean, "mean"), render._three(std, "std")
+        sd = None if unc is None else _std_plane(unc, B)
+        if self._shape != (B, h, w):
+            self._allocate(B, h, w, pred.device)
+        Dx, Dy, Dz = self.dims
+        if self._color is None:
+            self._color = torch.zeros(B, Dz, Dy, Dx, 4, dtype=torch.float32, device=pred.device)
+            self.color_counts = torch.zeros(B, 4, dtype=torch.int32, device=pred.device)
+        T = _pose(pose, B, pred.device)
+        hip.call("cfp_tsdf_integrate_rgb", pred.data_ptr(), h, w, H, W, B, int((h, w) != (H, W)), self.lo, self.hi, hip.ptr(sd),
+                 0 if sd is None else sd.shape[1], 0 if sd is None else sd.shape[2], 0 if sd is None else sd.stride(0),
+                 self.std_floor, self._K.data_ptr(), T.data_ptr(), self.volume.data_ptr(), Dx, Dy, Dz, *self.origin, self.voxel,
+                 self.trunc, self.z_near, self.w_max, rgb.data_ptr(), m, s, self._color.data_ptr(), self.color_counts.data_ptr(),
+                 hip.current_stream())
+        return self.color_counts
 
     def raycast(self, pose=None, intrinsics=None, size: Optional[Sequence[int]] = None, t_range: Optional[Sequence[float]] = None,
                 step: Optional[float] = None, normals: bool = True, out=None):
@@ -181,6 +235,55 @@ class TsdfVolume:
         Dx, Dy, Dz = self.dims
         hip.call("cfp_tsdf_raycast", self.volume.data_ptr(), Dx, Dy, Dz, B, *self.origin, self.voxel, K.data_ptr(), T.data_ptr(), Hd, Wd,
                  t0, t1, step, out[0].data_ptr(), out[2].data_ptr() if normals else 0, out[1].data_ptr(), hip.current_stream())
+        return out
+
+    def shade(self, depth: torch.Tensor, pose=None, intrinsics=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The colour of the map at the points the depth map names (`cfp_tsdf_shade`): `depth` [B,Hd,Wd] f32 on the device is a
+        `raycast` result seen from `pose` by `intrinsics` (the integrating camera's by default), or any metric depth on that grid ->
+        [B,Hd,Wd,3] f32, c in 0..1 as it was integrated; NaN where the depth is NaN or the map has no colour.  The grid is the depth's.
+        The result of one size is the volume's own buffer, overwritten by the next shade of that size; `out`: a tensor to write into.
+        Bitwise reproducible; no host synchronisation."""
+        if self._color is None:
+            raise ValueError("nothing was coloured yet: the colour volume is allocated by the first integrate_rgb")
+        B = self._color.shape[0]
+        dev = self._color.device
+        if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32 or not depth.is_cuda:
+            raise ValueError("depth must be a float32 device tensor")
+        if depth.dim() != 3 or depth.shape[0] != B or min(depth.shape) < 1:
+            raise ValueError(f"depth must be [B,Hd,Wd] with B = {B}, got {tuple(depth.shape)}")
+        depth = depth.contiguous()
+        Hd, Wd = depth.shape[1:]
+        K = self._K if intrinsics is None else _intrinsics(intrinsics, B, dev)
+        if out is None:
+            out = self._shades.get((Hd, Wd))
+            if out is None:
+                out = self._shades[(Hd, Wd)] = torch.empty(B, Hd, Wd, 3, dtype=torch.float32, device=dev)
+        _check_out(out, (B, Hd, Wd, 3), torch.float32, "out")
+        T = _pose(pose, B, dev)
+        Dx, Dy, Dz = self.dims
+        hip.call("cfp_tsdf_shade", self._color.data_ptr(), Dx, Dy, Dz, B, *self.origin, self.voxel, K.data_ptr(), T.data_ptr(), Hd, Wd,
+                 depth.data_ptr(), out.data_ptr(), hip.current_stream())
+        return out
+
+    def surface_colors(self, sp: SurfacePoints, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The colours of the points `surface_points` extracted (`cfp_tsdf_surface_rgb`) -> [B,cap,3] f32 on the device, also stored
+        as `sp.colors`: the colours of the edge's two voxels blended like the point itself, the colour of the one end that has one, or
+        NaN where neither has.  Rows at or beyond min(count, capacity) are not written.  `out`: a tensor to write into (`sp.colors`,
+        if there is one, by default).  No host synchronisation; capturable after `surface_points(capacity, out=...)`."""
+        if self._color is None:
+            raise ValueError("nothing was coloured yet: the colour volume is allocated by the first integrate_rgb")
+        if not isinstance(sp, SurfacePoints):
+            raise ValueError("sp must be the SurfacePoints of surface_points")
+        B, cap = self._color.shape[0], sp.capacity
+        _check_out(sp.index, (B, cap), torch.int32, "sp.index")
+        _check_out(sp.counts, (B,), torch.int32, "sp.counts")
+        if out is None:
+            out = sp.colors if sp.colors is not None else torch.empty(B, cap, 3, dtype=torch.float32, device=self._color.device)
+        _check_out(out, (B, cap, 3), torch.float32, "out")
+        Dx, Dy, Dz = self.dims
+        hip.call("cfp_tsdf_surface_rgb", self.volume.data_ptr(), self._color.data_ptr(), Dx, Dy, Dz, B, sp.index.data_ptr(),
+                 sp.counts.data_ptr(), cap, out.data_ptr(), hip.current_stream())
+        sp.colors = out
         return out
 
     def _surface_args(self, w_min, max_jump):
@@ -258,9 +361,19 @@ class TsdfVolume:
     def write_ply(self, path_pattern: str, **options) -> List[int]:
         """One binary PLY per image (xyz and, unless `normals=False`, the normals) through `pointcloud.write_ply`: image b goes to
         `path_pattern.format(b)` -- a pattern without a field is used as it is for a single image.  `options` are those of
-        `surface_points`.  Host side after one synchronisation.  Returns the vertex counts."""
-        parts = self.surface_points(**options).split()
+        `surface_points`, and `colors=True`: the points' `surface_colors` as `uchar red green blue` (a point the map has no colour
+        for is black); it raises without a colour volume.  Host side after one synchronisation.  Returns the vertex counts."""
+        colors = bool(options.pop("colors", False))
+        if colors and self._color is None:
+            raise ValueError("colors=True, but nothing was coloured yet: the colour volume is allocated by the first integrate_rgb")
+        sp = self.surface_points(**options)
+        if colors:
+            self.surface_colors(sp)
+        parts = sp.split()
         paths = [path_pattern.format(b) for b in range(len(parts))]
         if len(set(paths)) != len(paths):
             raise ValueError(f"path_pattern {path_pattern!r} names the same file for several images: put a {{}} field into it")
+        if colors:
+            return [write_ply(path, part["points"], part["normals"], torch.nan_to_num(part["colors"], nan=0.0))
+                    for path, part in zip(paths, parts)]
         return [write_ply(path, part["points"], part["normals"]) for path, part in zip(paths, parts)]

@@ -915,6 +915,64 @@ int cfp_tsdf_surface(const float* volume /* [B][Dz][Dy][Dx][2] */, int Dx, int D
                      float* normals /* [B][cap][3] or NULL */, float* std /* [B][cap] or NULL */, int* index /* [B][cap] or NULL */,
                      int* counts /* [B] */, void* ws, size_t ws_bytes, cfp_stream_t stream);
 
+/* Colour in the map: a second volume next to the TSDF, fused by the same inverse-variance weights, and its two readers.  The conventions
+ * are those of the TSDF block above: float32 in the order written here, no fused multiply-add, K [B][4] and T [B][12] ON THE DEVICE.
+ *   Colour volume  float [B,Dz,Dy,Dx,4] ON THE DEVICE, 16-byte aligned: (R, G, B, Wc) per voxel, x fastest, next to the unchanged (F, Wt)
+ *           volume.  Empty is (0, 0, 0, 0).  Wc is the colour's own inverse-variance sum, not Wt: frames integrated without an image
+ *           (cfp_tsdf_integrate) and with one can be mixed freely, and the geometry never depends on whether colour is kept.
+ *
+ * cfp_tsdf_integrate_rgb
+ *   Inputs  every argument of cfp_tsdf_integrate; rgb [B][3][H][W] f32 ON THE DEVICE, on the H x W grid, planar (the model's input);
+ *           mean[3], cstd[3]: HOST arrays of finite floats, copied into the kernel arguments like cfp_render_rgb's; color: the colour
+ *           volume; counts [B][4] i32 = {valid depth seen, updated, behind the surface, coloured}, overwritten.
+ *   Voxel   everything cfp_tsdf_integrate does up to and including UPDATED, unchanged: (F, Wt) and the first three counts are bit for
+ *           bit what cfp_tsdf_integrate writes for the same inputs.  Then, for an UPDATED voxel only, with the pix, w and sdf of the
+ *           geometry step:  sdf > trunc: nothing (free space in front of the surface takes no colour);  otherwise
+ *             c_k = rgb[b][k][pix] * cstd[k] + mean[k]  for k = 0, 1, 2;  skipped unless all three are finite;
+ *             C_k' = (C_k * Wc + c_k * w) / (Wc + w)     Wc' = fminf(Wc + w, w_max)                                    COLOURED
+ *           A voxel that is not coloured has its colour entry neither read nor written.
+ *   Refused, with a message, before anything launches: everything cfp_tsdf_integrate refuses; a null rgb, mean, cstd or color; a
+ *           non-finite mean or cstd; a colour volume that is not 16-byte aligned.
+ * The same kernel as cfp_tsdf_integrate (its COLOR instance): integer counts onto words a first launch zeroes, no floating-point
+ * atomics, two calls on the same tensors give identical bits; no host synchronisation, no allocation, no workspace; capturable.
+ *
+ * cfp_tsdf_shade: the colour of the map at the points a depth map names.
+ *   Inputs  the colour volume; depth [B,Hd,Wd] f32 on the grid K describes -- a cfp_tsdf_raycast result, or any metric depth there.
+ *   Pixel   the Ray rx, ry of cfp_tsdf_raycast, its Point at t = depth, and g, i0 / a, j0 / b, k0 / c of its Sample.  The result is
+ *           (NaN, NaN, NaN) if the depth is not finite, if the cell test 0 <= i0 <= Dx - 2, 0 <= j0 <= Dy - 2, 0 <= k0 <= Dz - 2 fails (on
+ *           the float values), or if no corner of the cell has Wc > 0.  Otherwise, over the corners in the order x fastest, then y, then
+ *           z, with tw = (wx * wy) * wz (wx one of 1 - a and a, wy of 1 - b and b, wz of 1 - c and c):
+ *             den = sum of tw, num_k = sum of tw * C_k, over the corners with Wc > 0, both accumulated in corner order from 0
+ *             out_k = num_k / den
+ *           The blend is renormalised over the corners that have a colour instead of demanding all eight: the colour band is trunc thick
+ *           along the viewing ray, and corners of a hit cell may lie outside it at grazing angles.
+ *   Outputs rgb_out [B,Hd,Wd,3] f32.
+ * One thread per pixel in 16 x 16 tiles, a corner is one 16-byte load.  Reads only: bitwise reproducible.
+ *
+ * cfp_tsdf_surface_rgb: the colours of the rows cfp_tsdf_surface wrote.
+ *   Inputs  both volumes; index [B][cap] i32, the edge indices e; counts [B] i32; cap >= 1.
+ *   Row     for each r < min(counts[b], cap):  n = e / 3, a = e - 3 * n, p = n, q = p + e_a;  t = F(p) / (F(p) - F(q)), the expression of
+ *           cfp_tsdf_surface, read from the geometry volume.  Both ends with Wc > 0: (1 - t) * C(p) + t * C(q) per channel; exactly one:
+ *           that end's colour; neither: (NaN, NaN, NaN).  A row whose e is negative, is >= 3 * Dx * Dy * Dz, or whose q leaves the grid
+ *           gets NaN and reads nothing: the index is device data and cannot take a load outside the volumes.
+ *   Outputs colors [B][cap][3] f32; rows at or beyond min(count, cap) are not written.
+ * Refused: null pointers; non-positive dimensions; 3 * Dx * Dy * Dz >= 2^31 or B > 65535; cap < 1; a geometry volume that is not 8-byte
+ * or a colour volume that is not 16-byte aligned.  One thread per row; no workspace, no atomics, no host synchronisation. */
+enum { CFP_TSDF_COLOURED = 3 };
+int cfp_tsdf_integrate_rgb(const float* pred, int Hp, int Wp, int H, int W, int B, int interpolate, float lo, float hi,
+                           const float* std /* or NULL */, int Hu, int Wu, long long std_stride, float std_floor,
+                           const float* K /* device, [B][4] */, const float* T /* device, [B][12] */,
+                           float* volume /* [B][Dz][Dy][Dx][2] */, int Dx, int Dy, int Dz, float ox, float oy, float oz, float voxel,
+                           float trunc, float z_near, float w_max, const float* rgb /* device, [B][3][H][W] */,
+                           const float* mean /* host, [3] */, const float* cstd /* host, [3] */,
+                           float* color /* [B][Dz][Dy][Dx][4] */, int* counts /* [B][4] */, cfp_stream_t stream);
+int cfp_tsdf_shade(const float* color /* [B][Dz][Dy][Dx][4] */, int Dx, int Dy, int Dz, int B, float ox, float oy, float oz, float voxel,
+                   const float* K /* device, [B][4] */, const float* T /* device, [B][12] */, int Hd, int Wd,
+                   const float* depth /* [B][Hd][Wd] */, float* rgb_out /* [B][Hd][Wd][3] */, cfp_stream_t stream);
+int cfp_tsdf_surface_rgb(const float* volume /* [B][Dz][Dy][Dx][2] */, const float* color /* [B][Dz][Dy][Dx][4] */, int Dx, int Dy, int Dz,
+                         int B, const int* index /* [B][cap] */, const int* counts /* [B] */, int cap, float* colors /* [B][cap][3] */,
+                         cfp_stream_t stream);
+
 /* Camera tracking: one Gauss-Newton iteration of dense point-to-plane ICP of a frame against a model map, per image, without leaving the
  * device -- projective data association, the 6 x 6 normal equations weighted by the two variances, the solve and the pose update.  The
  * frame is the prediction and its std; the model is a depth / normal / std map in the MODEL camera: a cfp_tsdf_raycast (frame-to-model
