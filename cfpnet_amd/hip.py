@@ -111,6 +111,10 @@ SIGNATURES = {
     "cfp_tsdf_surface": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "cfp_icp_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "cfp_icp_step": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _i, _i, _ll, _f, _p, _f, _p, _p, _p, _p, _i, _i, _p, _i, _f, _f, _i, _f, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "cfp_luma": (_i, [_p, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _i, _i, _p, _p]),
+    "cfp_icp_rgb_ws_bytes": (_sz, [_i, _i, _i, _i]),
+    "cfp_icp_rgb_step": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _i, _i, _ll, _f, _p, _f, _p, _p, _p, _p, _i, _i, _p, _i, _f, _f, _i, _f, _p, _p, _p, _p, _p, _p, _p, _sz,
+                              _p, _p, _f, _f, _p, _p]),
     "cfp_normal_metrics_ws_bytes": (_sz, [_i, _i, _i]),
     "cfp_normal_metrics": (_i, [_p, _i, _i, _p, _i, _i, _i, _i, _f, _f, _p, _p, _sz, _p, _p, _p, _p]),
     "cfp_tof_zone_consistency": (_i, [_p, _i, _i, _i, _i, _i, _i, _f, _f, _p, _p, _p, _i, _f, _i, C.c_double, _i, _p, _p, _p, _p]),

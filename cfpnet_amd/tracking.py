@@ -9,6 +9,13 @@ The model map is a `TsdfVolume.raycast` (frame-to-model tracking, KinectFusion's
 integrate, with nothing synchronising with the host, so an `update` can be captured in a graph.  The arithmetic is `csrc/icp.hip`
 (definition in include/cfpnet_hip.h); nothing here computes on the CPU.
 
+`icp_rgb` is `icp` with the image: beside the point-to-plane term every pair compares the frame's luminance with the model's picture
+(`TsdfVolume.shade` of the raycast) at the pixel it projects to (`cfp_icp_rgb_step`, `csrc/icp_rgb.hip`).  In front of a
+wall, on a floor, along a corridor geometry observes three of the six degrees of freedom and `icp` refuses every step; the texture
+observes the other three.  `Tracker(..., photo_std=...)` turns it on for `update_rgb`.  There is ONE image level: the photometric term
+pulls over about half the finest texture period -- a pixel or two on natural images --, while geometry keeps its wide basin for the
+degrees of freedom it sees.  An image pyramid is a later step.
+
 This is frame-to-model dense ICP and nothing more: no relocalisation, no loop closure, no image pyramid.  It follows a camera that moves
 a few degrees and centimetres per frame; a visual-inertial front end remains the answer for fast motion.
 """
@@ -26,6 +33,7 @@ from .temporal import _pose, _std_plane, _ws
 from .tsdf import TsdfVolume
 
 STAT_NAMES = ("pairs", "weight", "rms", "rotation", "translation", "accepted")     # columns of `stats`
+STAT_NAMES_RGB = STAT_NAMES + ("photo_pairs", "photo_rms")                         # columns of `stats` of `icp_rgb`
 
 
 class IcpResult(NamedTuple):
@@ -37,13 +45,22 @@ class IcpResult(NamedTuple):
     the pair count, two zeros -- A is the information matrix of the pose at the solution (for a LEFT increment (omega, v) of `pose`), its
     inverse the covariance a pose graph or a filter wants.  `index` [B,H,W] i32 (None unless asked for): the model pixel ym * Wm + xm
     each source pixel was paired with in the last iteration, -1 where none.  `ws`: the workspace, reused when the tuple comes back as
-    `out`."""
+    `out`.
+
+    From `icp_rgb` with an image: `stats` [iters,B,8] in `STAT_NAMES_RGB` order -- the six above (pairs, weight and rms are the
+    geometric ones), the number of photometric pairs and their rms intensity residual (NaN without any); `sums` [B,64]: the 30 above,
+    the same 30 over the photometric pairs (A and g of the step are the sums of the two halves), four zeros; `residual` [B,H,W] f32 (None
+    unless asked for): the intensity residual model - frame of the last iteration where a photometric pair was formed, NaN elsewhere;
+    `src_luma` [B,H,W], `mdl_luma` [B,Hm,Wm]: the luminance planes the call computed (None where the caller passed a plane)."""
     pose: torch.Tensor
     world: Optional[torch.Tensor]
     stats: torch.Tensor
     sums: torch.Tensor
     index: Optional[torch.Tensor]
     ws: torch.Tensor
+    residual: Optional[torch.Tensor] = None
+    src_luma: Optional[torch.Tensor] = None
+    mdl_luma: Optional[torch.Tensor] = None
 
 
 def _map(t, shape, what: str) -> torch.Tensor:
@@ -89,6 +106,74 @@ def icp(pred: torch.Tensor, intrinsics, model_depth: torch.Tensor, model_normals
     constrain all six degrees of freedom.  `ref_pose`: camera-from-world of the model camera; given, `world` is the frame's own
     camera-from-world pose.  `index=True` adds the association map.  `out`: the result of an earlier call to write into -- then nothing
     is allocated here.  Bitwise reproducible; no host synchronisation."""
+    return _icp(pred, intrinsics, model_depth, model_normals, pose0, unc, model_std, model_intrinsics, size, src_normals, cos_min, iters,
+                stride, dist_max, z_near, lo, hi, std_floor, min_pairs, min_pivot, ref_pose, index, out, None)
+
+
+def _luma(img, shape, mean, std, buf, what: str):
+    """A luminance plane [B,H,W] of `shape` out of `img`: a ready plane is used as it is (-> (plane, None)); a planar normalised image
+    [B,3,H,W] or an interleaved one [B,H,W,3] in 0..1 goes through `cfp_luma` into `buf` (allocated when None) -> (buf, buf)."""
+    B, H, W = shape
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.float32 or not img.is_cuda:
+        raise ValueError(f"{what} must be a float32 device tensor")
+    if tuple(img.shape) == (B, H, W):
+        if buf is not None:
+            raise ValueError(f"out holds a luminance buffer for {what}, but {what} is a ready plane")
+        return img.contiguous(), None
+    planar = what == "rgb"
+    want = (B, 3, H, W) if planar else (B, H, W, 3)
+    if tuple(img.shape) != want:
+        raise ValueError(f"{what} must be {want} or a luminance plane {(B, H, W)}, got {tuple(img.shape)}")
+    img = img.contiguous()
+    if buf is None:
+        buf = torch.empty(B, H, W, dtype=torch.float32, device=img.device)
+    else:
+        _check_out(buf, (B, H, W), torch.float32, f"out luminance of {what}")
+    hip.call("cfp_luma", img.data_ptr(), 0 if planar else 1, render._three(mean, "mean") if planar else None,
+             render._three(std, "std") if planar else None, H, W, B, buf.data_ptr(), hip.current_stream())
+    return buf, buf
+
+
+def icp_rgb(pred: torch.Tensor, intrinsics, model_depth: torch.Tensor, model_normals: torch.Tensor, pose0=None,
+            unc: Optional[torch.Tensor] = None, model_std: Optional[torch.Tensor] = None, model_intrinsics=None,
+            size: Optional[Sequence[int]] = None, src_normals: Optional[torch.Tensor] = None, cos_min: float = 0.5, iters: int = 10,
+            stride: int = 1, dist_max: float = 0.25, z_near: float = 1e-3, lo: float = 1e-3, hi: float = 10.0, std_floor: float = 1e-3,
+            min_pairs: int = 100, min_pivot: float = 1e-6, ref_pose=None, index: bool = False, out: Optional[IcpResult] = None,
+            rgb: Optional[torch.Tensor] = None, model_rgb: Optional[torch.Tensor] = None, photo_std: float = 0.04,
+            photo_max: float = 0.25, mean=render.IMAGENET_MEAN, std=render.IMAGENET_STD, residual: bool = False) -> IcpResult:
+    """`icp` with every argument of `icp`, and the image: `rgb` is the frame's, [B,3,H,W] f32 normalised like the model's input
+    (c = rgb * std + mean, as `TsdfVolume.integrate_rgb` reads it) or a ready luminance plane [B,H,W]; `model_rgb` the model's picture on
+    the model grid, [B,Hm,Wm,3] in 0..1 -- `TsdfVolume.shade` of the raycast -- or a luminance plane [B,Hm,Wm].  Giving only one of the
+    two is an error; giving neither is `icp` itself, with its result shapes.  With both, every pair of `icp` that lands inside the model
+    picture also compares luminances (bilinear in the model's, NaN taps and residuals above `photo_max` dropped) and the step solves the
+    sum of the two systems (`cfp_icp_rgb_step`); `min_pairs` counts the geometric pairs.
+
+    `photo_std`: the intensity noise in 0..1 units; a photometric pair weighs 1 / photo_std^2, on the maximum-likelihood footing of
+    1 / (std^2 + model_std^2) of the depth.  The default 0.04 -- roughly 10 / 255 -- is a stated prior and is NOT measured on any sensor;
+    with unit geometric weights (no `unc`, no `model_std`) it has to be chosen against 1 / metre^2 instead.  `residual=True` adds the
+    residual map.  `stats` is [iters,B,8] (`STAT_NAMES_RGB`), `sums` [B,64].  The luminance planes are computed once per call (`cfp_luma`)
+    into buffers that `out` reuses: with `out` nothing is allocated.  One image level: see the module's docstring.  Bitwise reproducible;
+    no host synchronisation."""
+    if (rgb is None) != (model_rgb is None):
+        raise ValueError("rgb and model_rgb are given together or not at all")
+    photo = None
+    if rgb is not None:
+        for name, v, top in (("photo_std", photo_std, False), ("photo_max", photo_max, True)):
+            if not (float(v) > 0.0 and (top or math.isfinite(float(v)))):
+                raise ValueError(f"{name} must be positive{'' if top else ' and finite'}, got {v}")
+        weight = 1.0 / (float(photo_std) * float(photo_std))
+        if not 1e-38 < weight < 3e38:                                     # as a float32: positive and finite
+            raise ValueError(f"photo_std gives no finite float32 weight: {photo_std}")
+        photo = (rgb, model_rgb, weight, float(photo_max), mean, std, bool(residual))
+    elif residual:
+        raise ValueError("residual needs rgb and model_rgb")
+    return _icp(pred, intrinsics, model_depth, model_normals, pose0, unc, model_std, model_intrinsics, size, src_normals, cos_min, iters,
+                stride, dist_max, z_near, lo, hi, std_floor, min_pairs, min_pivot, ref_pose, index, out, photo)
+
+
+def _icp(pred, intrinsics, model_depth, model_normals, pose0, unc, model_std, model_intrinsics, size, src_normals, cos_min, iters, stride,
+         dist_max, z_near, lo, hi, std_floor, min_pairs, min_pivot, ref_pose, index, out, photo) -> IcpResult:
+    """`icp` (photo None) and `icp_rgb` (photo = (rgb, model_rgb, weight, photo_max, mean, std, residual))."""
     pred = _pred3(pred)
     B, h, w = pred.shape
     H, W = _size(size, h, w)
@@ -109,7 +194,9 @@ def icp(pred: torch.Tensor, intrinsics, model_depth: torch.Tensor, model_normals
     T0 = None if pose0 is None else _pose(pose0, B, dev)
     Tr = None if ref_pose is None else _pose(ref_pose, B, dev)
     iters, stride = int(iters), int(stride)
-    nbytes = hip.load().cfp_icp_ws_bytes(B, H, W, stride)
+    nbytes = (hip.load().cfp_icp_ws_bytes if photo is None else hip.load().cfp_icp_rgb_ws_bytes)(B, H, W, stride)
+    ncol, nsum = (6, 32) if photo is None else (8, 64)
+    want_res = photo is not None and photo[6]
     if out is not None:
         if not isinstance(out, IcpResult):
             raise ValueError("out must be the IcpResult of an earlier call")
@@ -118,18 +205,30 @@ def icp(pred: torch.Tensor, intrinsics, model_depth: torch.Tensor, model_normals
             raise ValueError("out world must be given exactly when ref_pose is")
         if Tr is not None:
             _check_out(out.world, (B, 3, 4), torch.float32, "out world")
-        _check_out(out.stats, (iters, B, 6), torch.float32, "out stats")
-        _check_out(out.sums, (B, 32), torch.float64, "out sums")
+        _check_out(out.stats, (iters, B, ncol), torch.float32, "out stats")
+        _check_out(out.sums, (B, nsum), torch.float64, "out sums")
         if (out.index is None) == bool(index):
             raise ValueError("out index must be given exactly when index is asked for")
         if index:
             _check_out(out.index, (B, H, W), torch.int32, "out index")
+        if (out.residual is None) == want_res:
+            raise ValueError("out residual must be given exactly when residual is asked for")
+        if want_res:
+            _check_out(out.residual, (B, H, W), torch.float32, "out residual")
+        if photo is None and (out.src_luma is not None or out.mdl_luma is not None):
+            raise ValueError("out holds luminance buffers, but no image is given")
         _ws(nbytes, out.ws, dev)
     else:
         out = IcpResult(torch.empty(B, 3, 4, dtype=torch.float32, device=dev),
                         None if Tr is None else torch.empty(B, 3, 4, dtype=torch.float32, device=dev),
-                        torch.empty(iters, B, 6, dtype=torch.float32, device=dev), torch.empty(B, 32, dtype=torch.float64, device=dev),
-                        torch.empty(B, H, W, dtype=torch.int32, device=dev) if index else None, _ws(nbytes, None, dev))
+                        torch.empty(iters, B, ncol, dtype=torch.float32, device=dev), torch.empty(B, nsum, dtype=torch.float64, device=dev),
+                        torch.empty(B, H, W, dtype=torch.int32, device=dev) if index else None, _ws(nbytes, None, dev),
+                        torch.empty(B, H, W, dtype=torch.float32, device=dev) if want_res else None)
+    if photo is not None:
+        sl, sbuf = _luma(photo[0], (B, H, W), photo[4], photo[5], out.src_luma, "rgb")
+        ml, mbuf = _luma(photo[1], (B, Hm, Wm), photo[4], photo[5], out.mdl_luma, "model_rgb")
+        if sbuf is not out.src_luma or mbuf is not out.mdl_luma:
+            out = out._replace(src_luma=sbuf, mdl_luma=mbuf)
     T = out.pose.view(B, 12)
     if T0 is None:
         T.zero_()
@@ -140,6 +239,15 @@ def icp(pred: torch.Tensor, intrinsics, model_depth: torch.Tensor, model_normals
     stream = hip.current_stream()
     for it in range(iters):
         last = it == iters - 1
+        if photo is not None:
+            hip.call("cfp_icp_rgb_step", pred.data_ptr(), h, w, H, W, B, interp, float(lo), float(hi), hip.ptr(std),
+                     0 if std is None else std.shape[1], 0 if std is None else std.shape[2], 0 if std is None else std.stride(0),
+                     float(std_floor), hip.ptr(src_normals), float(cos_min), K.data_ptr(), model_depth.data_ptr(),
+                     model_normals.data_ptr(), hip.ptr(model_std), Hm, Wm, Km.data_ptr(), stride, float(z_near), float(dist_max),
+                     int(min_pairs), float(min_pivot), T.data_ptr(), hip.ptr(Tr) if last else 0, hip.ptr(out.world) if last else 0,
+                     hip.ptr(out.index) if last else 0, out.sums.data_ptr(), out.stats[it].data_ptr(), out.ws.data_ptr(), nbytes,
+                     sl.data_ptr(), ml.data_ptr(), photo[2], photo[3], hip.ptr(out.residual) if last else 0, stream)
+            continue
         hip.call("cfp_icp_step", pred.data_ptr(), h, w, H, W, B, interp, float(lo), float(hi), hip.ptr(std),
                  0 if std is None else std.shape[1], 0 if std is None else std.shape[2], 0 if std is None else std.stride(0),
                  float(std_floor), hip.ptr(src_normals), float(cos_min), K.data_ptr(), model_depth.data_ptr(), model_normals.data_ptr(),
@@ -150,6 +258,7 @@ def icp(pred: torch.Tensor, intrinsics, model_depth: torch.Tensor, model_normals
 
 
 _TRACKER_OPTIONS = ("cos_min", "iters", "stride", "dist_max", "min_pairs", "min_pivot")
+_TRACKER_PHOTO_OPTIONS = ("photo_std", "photo_max")
 
 
 class Tracker:
@@ -160,6 +269,10 @@ class Tracker:
     `.pose` [B,3,4] f32 is the last pose, on the device.  Nothing synchronises with the host: once the first frame is in, an `update`
     can be captured in a graph and replayed on new inputs.
 
+    `photo_std` (None: off) and `photo_max` (0.25) of `icp_rgb`, given among the options, make `update_rgb` track with the image as
+    well: raycast -> `shade` -> `icp_rgb` against the shaded picture -> `integrate_rgb`.  `update` has no image and tracks by geometry;
+    so does a frame that comes before the map has any colour.
+
     A lost frame is still integrated: `update` does not look at the result on the host.  `stats[-1, :, 5]` says whether the last step
     was accepted; a caller who wants to keep a doubtful frame out of the map calls `update(..., integrate=False)` (or `track`), reads
     the stats and integrates the frame afterwards."""
@@ -167,9 +280,14 @@ class Tracker:
     def __init__(self, volume: TsdfVolume, pose0=None, **icp_options):
         if not isinstance(volume, TsdfVolume):
             raise ValueError("volume must be a TsdfVolume")
-        unknown = sorted(set(icp_options) - set(_TRACKER_OPTIONS))
+        unknown = sorted(set(icp_options) - set(_TRACKER_OPTIONS) - set(_TRACKER_PHOTO_OPTIONS))
         if unknown:
-            raise ValueError(f"unknown icp option(s) {unknown}: one of {_TRACKER_OPTIONS}")
+            raise ValueError(f"unknown icp option(s) {unknown}: one of {_TRACKER_OPTIONS + _TRACKER_PHOTO_OPTIONS}")
+        self.photo_std, self.photo_max = icp_options.pop("photo_std", None), icp_options.pop("photo_max", 0.25)
+        if self.photo_std is not None and not (float(self.photo_std) > 0.0 and math.isfinite(float(self.photo_std))):
+            raise ValueError(f"photo_std must be positive and finite (or None: off), got {self.photo_std}")
+        if not float(self.photo_max) > 0.0:
+            raise ValueError(f"photo_max must be positive, got {self.photo_max}")
         defaults = dict(cos_min=0.5, iters=10, stride=1, dist_max=0.25, min_pairs=100, min_pivot=1e-6)
         defaults.update(icp_options)
         _icp_numbers(lo=volume.lo, hi=volume.hi, std_floor=volume.std_floor, z_near=volume.z_near, **defaults)
@@ -185,16 +303,25 @@ class Tracker:
         """Forget the trajectory: the next `update` integrates at `pose0` without tracking.  The volume is not touched."""
         self._primed = False
 
-    def _track(self, pred, unc) -> IcpResult:
+    def _track(self, pred, unc, image=None) -> IcpResult:
+        """`image`: (rgb, mean, std) of the frame when the image takes part in the tracking."""
         if not self._primed:
             raise ValueError("nothing to track against yet: the first update integrates the first frame")
         pred = _pred3(pred)
         vol = self.volume
         depth, std, normals = vol.raycast(self.pose, normals=True)
-        if self._out is not None and (self._out.pose.shape[0] != pred.shape[0] or self._out.index is not None):
+        photo = image is not None and vol.color is not None
+        if self._out is not None and (self._out.pose.shape[0] != pred.shape[0] or self._out.index is not None or
+                                      (self._out.mdl_luma is not None) != photo):
             self._out = None
-        self._out = icp(pred, vol.camera, depth, normals, None, unc, std, None, vol.grid_size, None, lo=vol.lo, hi=vol.hi,
-                        std_floor=vol.std_floor, z_near=vol.z_near, ref_pose=self.pose, out=self._out, **self.options)
+        if photo:
+            self._out = icp_rgb(pred, vol.camera, depth, normals, None, unc, std, None, vol.grid_size, None, lo=vol.lo, hi=vol.hi,
+                                std_floor=vol.std_floor, z_near=vol.z_near, ref_pose=self.pose, out=self._out, rgb=image[0],
+                                model_rgb=vol.shade(depth, self.pose), photo_std=self.photo_std, photo_max=self.photo_max,
+                                mean=image[1], std=image[2], **self.options)
+        else:
+            self._out = icp(pred, vol.camera, depth, normals, None, unc, std, None, vol.grid_size, None, lo=vol.lo, hi=vol.hi,
+                            std_floor=vol.std_floor, z_near=vol.z_near, ref_pose=self.pose, out=self._out, **self.options)
         self.stats = self._out.stats
         return self._out
 
@@ -203,7 +330,7 @@ class Tracker:
         `unc` against the volume as it is; `.stats` [iters,B,6] is `icp`'s.  Stores nothing: `.pose` and the volume stay."""
         return self._track(pred, unc).world
 
-    def _update(self, pred, unc, integrate, fuse):
+    def _update(self, pred, unc, integrate, fuse, image=None):
         """`update` and `update_rgb`: `fuse(pose)` integrates the frame."""
         if not self._primed:
             pred = _pred3(pred)
@@ -216,7 +343,7 @@ class Tracker:
             self._primed = True
             self.stats = None
             return self.pose, None
-        res = self._track(pred, unc)
+        res = self._track(pred, unc, image)
         self.pose.copy_(res.world)
         if integrate:
             fuse(self.pose)
@@ -230,7 +357,9 @@ class Tracker:
     def update_rgb(self, pred: torch.Tensor, rgb: torch.Tensor, unc: Optional[torch.Tensor] = None, integrate: bool = True,
                    mean=render.IMAGENET_MEAN, std=render.IMAGENET_STD):
         """`update` with the frame's image: the frame is integrated by `TsdfVolume.integrate_rgb(pred, rgb, unc, pose, mean, std)`, so the
-        map takes the colour along -- `volume.write_ply(pattern, colors=True)` afterwards is the coloured room.  Tracking itself does
-        not look at the image: the poses are those of `update`."""
+        map takes the colour along -- `volume.write_ply(pattern, colors=True)` afterwards is the coloured room.  Without the option
+        `photo_std` tracking itself does not look at the image: the poses are those of `update`.  With it the frame is tracked by
+        `icp_rgb` against the shaded raycast (stats [iters,B,8]), once the map has colour: the first frame is integrated as ever."""
         rgb = render._rgb4(rgb)                                           # refuse a bad image before the frame is tracked
-        return self._update(pred, unc, integrate, lambda pose: self.volume.integrate_rgb(pred, rgb, unc, pose, mean, std))
+        image = None if self.photo_std is None else (rgb, mean, std)
+        return self._update(pred, unc, integrate, lambda pose: self.volume.integrate_rgb(pred, rgb, unc, pose, mean, std), image)

@@ -1033,6 +1033,64 @@ int cfp_icp_step(const float* pred, int Hp, int Wp, int H, int W, int B, int int
                  float* T_world /* [B][12] or NULL, given exactly when T_ref is */, int* index /* [B][H][W] or NULL */,
                  double* sums /* [B][32] or NULL */, float* stats /* [B][6] */, void* ws, size_t ws_bytes, cfp_stream_t stream);
 
+/* Colour in camera tracking: the step of cfp_icp_step with a photometric term beside the point-to-plane one.  In front of a wall, a floor
+ * or along a corridor geometry observes three of the six degrees of freedom and cfp_icp_step refuses; the texture on the surface observes
+ * the other three.  The images are luminance planes: the frame's on the source grid, the model's on the model grid (the picture of the
+ * map from the model camera: cfp_tsdf_shade of the raycast, or the previous frame's image).
+ *
+ * cfp_luma: one luminance plane out of an image.
+ *   Inputs  layout 0: rgb [B,3,H,W] f32, the model's normalised planar input, with mean[3], cstd[3] ON THE HOST: c = rgb * cstd + mean per
+ *           channel (the colour cfp_tsdf_integrate_rgb fuses).  Layout 1: rgb [B,H,W,3] f32 interleaved, already in 0..1 -- what
+ *           cfp_tsdf_shade writes --, c = rgb; mean and cstd are not read.
+ *   Pixel   Y = (0.299f * R + 0.587f * G) + 0.114f * B in float32 in that order (Rec. 601), no fused multiply-add; NaN if one of the three
+ *           c is not finite (so the NaN of a shaded pixel without colour stays a NaN).
+ *   Outputs luma [B,H,W] f32.
+ * Refused: null pointers; another layout; layout 0 without mean and cstd, or with non-finite ones; non-positive dimensions; H * W >= 2^31
+ * or B > 65535.  One pixel per lane; reads only its own pixel: bitwise reproducible; no workspace, no host synchronisation.
+ *
+ * cfp_icp_rgb_step: the arguments of cfp_icp_step, then src_luma [B,H,W] f32 (the H x W source grid), mdl_luma [B,Hm,Wm] f32,
+ * photo_weight > 0 and finite, photo_max > 0 (+inf: no gate), residual [B,H,W] f32 or NULL.
+ *   Geometric pair   the Pair of cfp_icp_step: the projection, the gates, w, r, J and the index map are its, bit for bit.
+ *   Photometric pair a source pixel that has a geometric pair forms one as well when, with the u, v, X', Y', Z' of that pair (unrounded):
+ *             x0 = floorf(u), y0 = floorf(v), ax = u - x0, ay = v - y0;  0 <= x0, x0 + 1 <= Wm - 1, 0 <= y0, y0 + 1 <= Hm - 1, tested on
+ *             the float values so that NaN fails;  the four taps I00 = mdl_luma(x0, y0), I10 (x0 + 1, y0), I01 (x0, y0 + 1), I11 and
+ *             Is = src_luma at the source pixel are finite;  in float32, in this order:
+ *               top = I00 + ax * (I10 - I00)          bot = I01 + ax * (I11 - I01)          Im = top + ay * (bot - top)
+ *               gx = (I10 - I00) + ay * ((I11 - I01) - (I10 - I00))          gy = bot - top
+ *             -- the bilinear interpolant and its exact derivative in u and v --  rI = Im - Is,  and |rI| <= photo_max.
+ *             gfx = gx * fxm, gfy = gy * fym;  a = (gfx / Z', gfy / Z', -((gfx * (X' / Z') + gfy * (Y' / Z')) / Z')): the gradient of Im in P'.
+ *             JI = (P' x a, a) = (Y' * a.z - Z' * a.y, Z' * a.x - X' * a.z, X' * a.y - Y' * a.x, a.x, a.y, a.z): the derivative of rI
+ *             for the LEFT increment of cfp_icp_step, J with n replaced by a.  The weight is wI = photo_weight for every pair
+ *             (1 / sigma_I^2 for an intensity noise sigma_I, on the footing of w = 1 / variance of the depth).
+ *   Residual  residual, when given, is fully written: rI where a photometric pair was formed, NaN elsewhere; a pixel off the stride grid
+ *           gets NaN by the rule of `index`.
+ *   Sums    60 per image: 0..29 the sums of cfp_icp_step over the geometric pairs; 30..59 in the same layout over the photometric
+ *           pairs (21 of sum wI JI JI^T, 6 of sum wI JI rI, sum (wI * rI) * rI, sum wI, the count).  Float32 products, double
+ *           accumulation, the fixed order of cfp_icp_step; ONE row of 60 doubles per workgroup in the workspace.
+ *   Step    A = A_geo + A_photo, g = g_geo + g_photo, added in double; min_pairs is tested against the GEOMETRIC count, the pivot test
+ *           runs on the combined A; the solve, exp, the composition, Gram-Schmidt and T_world are those of cfp_icp_step.  With no
+ *           photometric pair at all (mdl_luma all NaN) T, T_world and the first six stats are bit for bit those of cfp_icp_step.
+ *   Outputs sums [B][64] f64 or NULL: the 60 and 4 zeros.  stats [B][8] f32: the six of cfp_icp_step (pairs, sum w and the rms are the
+ *           geometric ones), photo_pairs, photo_rms = sqrtf(sum wI rI rI / sum wI) (NaN without photometric pairs).
+ *   Checks  those of cfp_icp_step; src_luma and mdl_luma are given together or not at all, and without them the call is refused
+ *           (CFP_EINVAL): cfp_icp_step is the entry that tracks without an image.
+ * One image level: the photometric term pulls over about half the finest texture period.  Two launches, no atomics: identical bits from
+ * call to call; no host synchronisation, no allocation.  Workspace of cfp_icp_rgb_ws_bytes(B, H, W, stride) bytes, 8-byte aligned. */
+int cfp_luma(const float* rgb, int layout, const float* mean /* host, [3], layout 0 */, const float* cstd /* host, [3], layout 0 */,
+             int H, int W, int B, float* luma /* [B][H][W] */, cfp_stream_t stream);
+size_t cfp_icp_rgb_ws_bytes(int B, int H, int W, int stride);
+int cfp_icp_rgb_step(const float* pred, int Hp, int Wp, int H, int W, int B, int interpolate, float lo, float hi,
+                     const float* std /* or NULL */, int Hu, int Wu, long long std_stride, float std_floor,
+                     const float* src_normals /* [B][H][W][3] or NULL */, float cos_min, const float* K_src /* device, [B][4] */,
+                     const float* mdl_depth /* [B][Hm][Wm] */, const float* mdl_normals /* [B][Hm][Wm][3] */,
+                     const float* mdl_std /* [B][Hm][Wm] or NULL */, int Hm, int Wm, const float* K_mdl /* device, [B][4] */,
+                     int stride, float z_near, float dist_max, int min_pairs, float min_pivot,
+                     float* T /* device, [B][12], in and out */, const float* T_ref /* [B][12] or NULL */,
+                     float* T_world /* [B][12] or NULL, given exactly when T_ref is */, int* index /* [B][H][W] or NULL */,
+                     double* sums /* [B][64] or NULL */, float* stats /* [B][8] */, void* ws, size_t ws_bytes,
+                     const float* src_luma /* [B][H][W] */, const float* mdl_luma /* [B][Hm][Wm] */, float photo_weight,
+                     float photo_max, float* residual /* [B][H][W] or NULL */, cfp_stream_t stream);
+
 /* Surface-normal error of the predicted geometry against the ground truth's, per image, without leaving the device: the standard set of
  * the normal-estimation literature (mean, median and RMSE of the angle, share of pixels below 11.25, 22.5 and 30 degrees).
  *   Inputs  pred [B,Hp,Wp] f32 and gt [B,H,W] f32 (device); interpolate, lo < hi exactly as cfp_eval_metrics in mode 0; K [B][4] f32 ON
