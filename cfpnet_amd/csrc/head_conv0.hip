@@ -16,11 +16,11 @@
 //            64-deep K-steps through the weight stages.
 //   phase 1  GEMM1 = depth_head.conv3x3, transposed as in head_fused.hip (acc1[i][j][r] = ram(ch 16 i + 4 fq + r, px 16 j + fr)); a wave
 //            owns two pixel rows of the tile; the B fragment of tap (dy, dx) is a 16-byte read of pixel (y + dy, fr + dx) of the tile.
-//            w3 streams in 18 K-steps of 64: LDS-DMA, XOR-swizzled 128-byte rows, two 16 KB stages, the stage hand-over of
-//            head_fused.hip (vmcnt AND lgkmcnt(0) before the barrier: the zero words of out-of-range DMA lanes).
+//            w3 streams in 18 K-steps of 64: LDS-DMA, XOR-swizzled 128-byte rows, two 16 KB stages, head_core.h's stage hand-over
+//            (vmcnt AND lgkmcnt(0) before the barrier: the zero words of out-of-range DMA lanes).
 //   phase 2  GEMM2 (conv_out from the packed accumulators: ops.permute_wout's K order), softmax, expectation, prob transposed through
-//            LDS -- head_fused.hip's code on 256 pixels.  Wout half 0 lands in the dead t halo during GEMM1, half 1 in the two stages
-//            after it; the prob staging tile overlays stages, t halo and the unet tile.
+//            LDS: head_core.h, the code head_fused.hip runs, on 256 pixels.  Wout half 0 lands in the dead t halo during GEMM1, half 1
+//            in the two stages after it; the prob staging tile overlays stages, t halo and the unet tile.
 //
 // LDS map (162 944 bytes: one workgroup = two waves per SIMD per CU):
 //   [      0,  32768)  two weight stages (conv0's K-steps, w3's K-steps, later Wout half 1)
@@ -29,14 +29,12 @@
 //   [ 158848, 162944)  f32: conv_out bias [256] | scale3, shift3 [128 each] | bin centres of the image [256] | conv0 scale, shift [128 each]
 //   [      0, 135168)  prob staging [256 bins][264] once GEMM2 is done
 // Every LDS-DMA destination lies below 64 KB.
-#include "common.h"
+#include "head_core.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-constexpr int HC_C = 128;                 // unet / ram channels
-constexpr int HC_NB = 256;                // bins
+constexpr int HC_C = HEAD_C;              // unet / ram channels
+constexpr int HC_NB = HEAD_NB;            // bins
 constexpr int HC_CIN = 32;                // channels of t
 constexpr int HC_K0 = 9 * HC_CIN;         // 288
 constexpr int HC_K3 = 9 * HC_C;           // 1152
@@ -48,7 +46,7 @@ constexpr int HC_UGROUPS = (HC_UPIX + 15) / 16;                      // 21 group
 constexpr int HC_OFF_T = 2 * HC_WSTAGE;
 constexpr int HC_OFF_U = 65536;
 constexpr int HC_OFF_K = HC_OFF_U + HC_UPIX * HC_UP;
-constexpr int HC_LDS = HC_OFF_K + 4 * 256 * 4;
+constexpr int HC_LDS = HC_OFF_K + HEAD_K_BYTES;
 constexpr int HC_BM = 256;                // pixels of a tile
 constexpr int HC_PPITCH = HC_BM + 8;      // prob staging pitch (elements)
 constexpr unsigned HC_OOB = 0x80000000u;
@@ -65,19 +63,12 @@ struct HeadC0P {
   int probe;        // timing probes (tools/head_bench.py): 1 = descriptors with zero records (no fetch), 2 = stop after GEMM1, 4 = stop after GEMM2, 8 = stop after phase 0
 };
 
-// stage hand-over as in head_fused.hip: this wave's LDS-DMA loads have landed AND its LDS-side operations have drained, then the barrier
-__device__ __forceinline__ void hc_handover() {
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  __syncthreads();
-  asm volatile("" ::: "memory");
-}
-
 template <typename H>
 __global__ __launch_bounds__(512, 1) void depth_head_conv0_kernel(HeadC0P p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* sT = smem + HC_OFF_T;
   unsigned char* sU = smem + HC_OFF_U;
-  float* sK = reinterpret_cast<float*>(smem + HC_OFF_K);   // [0,256) bias_out | [256,384) scale3 | [384,512) shift3 | [512,768) centres | [768,896) scale0 | [896,1024) shift0
+  float* sK = reinterpret_cast<float*>(smem + HC_OFF_K);   // head_core.h's constants block; its last quarter: conv0's scale and shift
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -112,15 +103,8 @@ __global__ __launch_bounds__(512, 1) void depth_head_conv0_kernel(HeadC0P p) {
       __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w3, (lds_ptr_t)(smem + buf * HC_WSTAGE + g * 1024), 16, (int)v, ks * 128, 0, 0);
     }
   };
-  // one half (64 permuted channels) of Wout -> 32 KB at `off`: 256 rows of 128 bytes, four DMA instructions per wave
-  auto issue_wout = [&](int half, int off) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int g = q * 8 + wave;
-      const unsigned v = (unsigned)(g * 8 + rsub) * (unsigned)(HC_C * 2) + (unsigned)lc * 16u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_o, (lds_ptr_t)(smem + off + g * 1024), 16, (int)v, half * 128, 0, 0);
-    }
-  };
+  // one half (64 permuted channels) of Wout -> 32 KB at `off`
+  auto issue_wout = [&](int half, int off) { head_issue_wout<8>(rs_o, smem + off, half * 128, wave, rsub, lc); };
 
   issue_w0(0, 0);
 
@@ -142,16 +126,16 @@ __global__ __launch_bounds__(512, 1) void depth_head_conv0_kernel(HeadC0P p) {
     // the per-channel / per-bin vectors of the epilogues wait in LDS from the start (head_fused.hip: loading them at their use costs an
     // exposed global round trip each)
     if (tid < 256) {
-      sK[tid] = p.bias_out[tid];
-      sK[512 + tid] = p.centers[(long long)b * HC_NB + tid];
+      sK[HEAD_K_BIAS + tid] = p.bias_out[tid];
+      sK[HEAD_K_CEN + tid] = p.centers[(long long)b * HC_NB + tid];
     } else if (tid < 384) {
       const int u = tid - 256;
-      sK[256 + u] = p.scale3 ? p.scale3[u] : 1.f;
-      sK[768 + u] = p.scale0 ? p.scale0[u] : 1.f;
+      sK[HEAD_K_SCALE3 + u] = p.scale3 ? p.scale3[u] : 1.f;
+      sK[HEAD_K_SCALE0 + u] = p.scale0 ? p.scale0[u] : 1.f;
     } else {
       const int u = tid - 384;
-      sK[384 + u] = p.shift3 ? p.shift3[u] : 0.f;
-      sK[896 + u] = p.shift0 ? p.shift0[u] : 0.f;
+      sK[HEAD_K_SHIFT3 + u] = p.shift3 ? p.shift3[u] : 0.f;
+      sK[HEAD_K_SHIFT0 + u] = p.shift0 ? p.shift0[u] : 0.f;
     }
 #pragma unroll
     for (int n = 0; n < 4; ++n)
@@ -175,7 +159,7 @@ __global__ __launch_bounds__(512, 1) void depth_head_conv0_kernel(HeadC0P p) {
       for (int i = 0; i < 8; ++i) acc0[g][i] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ks = 0; ks < 5; ++ks) {
-      hc_handover();                                       // stage ks & 1 (and, first time round, the t halo) landed; the other stage is consumed
+      head_handover();                                     // stage ks & 1 (and, first time round, the t halo) landed; the other stage is consumed
       if (ks < 4) issue_w0(ks + 1, (ks + 1) & 1);
       else issue_w3(0, 1);                                 // GEMM1's K-step k reads stage (k + 1) & 1
       const unsigned char* cW = smem + (ks & 1) * HC_WSTAGE;
@@ -211,8 +195,8 @@ __global__ __launch_bounds__(512, 1) void depth_head_conv0_kernel(HeadC0P p) {
       for (int i = 0; i < 8; ++i) {
         const int ch = i * 16 + fq * 4;
         float sc[4], sh[4], yv[4];
-        Vec<float>::load(sK + 768 + ch, sc);
-        Vec<float>::load(sK + 896 + ch, sh);
+        Vec<float>::load(sK + HEAD_K_SCALE0 + ch, sc);
+        Vec<float>::load(sK + HEAD_K_SHIFT0 + ch, sh);
 #pragma unroll
         for (int r = 0; r < 4; ++r) yv[r] = acc0[g][i][r] * sc[r] + sh[r];
         uint2 pk;
@@ -235,7 +219,7 @@ __global__ __launch_bounds__(512, 1) void depth_head_conv0_kernel(HeadC0P p) {
     for (int j = 0; j < 2; ++j) acc1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   const unsigned char* urow = sU + ((2 * wave) * HC_UW + fr) * HC_UP + fq * 16;      // tap (0, 0) of pixel (2 wave, fr)
   for (int ks = 0; ks < HC_STEPS; ++ks) {
-    hc_handover();                                         // stage (ks + 1) & 1 landed; the other consumed; ks == 0: the unet tile is written, t is dead
+    head_handover();                                       // stage (ks + 1) & 1 landed; the other consumed; ks == 0: the unet tile is written, t is dead
     if (ks == 0) issue_wout(0, HC_OFF_T);
     if (ks + 1 < HC_STEPS) issue_w3(ks + 1, ks & 1);
     const int tap = ks >> 1;                               // 128 channels = two K-steps per tap
@@ -256,7 +240,7 @@ __global__ __launch_bounds__(512, 1) void depth_head_conv0_kernel(HeadC0P p) {
         for (int j = 0; j < 2; ++j) acc1[i][j] = mfma16<H>(wf[i], pf[j], acc1[i][j]);
     }
   }
-  hc_handover();                                           // both stages consumed by every wave (Wout half 0 landed long ago)
+  head_handover();                                         // both stages consumed by every wave (Wout half 0 landed long ago)
   issue_wout(1, 0);                                        // lands while GEMM2 runs on half 0
   if (p.probe & 2) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -264,61 +248,18 @@ __global__ __launch_bounds__(512, 1) void depth_head_conv0_kernel(HeadC0P p) {
     return;
   }
 
-  // ---- ram = scale * acc + shift (depth_head.conv3x3 has a bias and no activation) -> B fragments of GEMM2 -------------------------------
-  s16x8 bh[4][2];
-#pragma unroll
-  for (int kb = 0; kb < 4; ++kb) {
-    float sc[2][4], sh[2][4];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int ch = (2 * kb + u) * 16 + fq * 4;
-      Vec<float>::load(sK + 256 + ch, sc[u]);
-      Vec<float>::load(sK + 384 + ch, sh[u]);
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[u * 4 + r] = acc1[2 * kb + u][j][r] * sc[u][r] + sh[u][r];
-      uint32_t hi[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const H h0 = from_f32<H>(v[2 * e]), h1 = from_f32<H>(v[2 * e + 1]);
-        hi[e] = (uint32_t)to_bits<H>(h0) | ((uint32_t)to_bits<H>(h1) << 16);
-      }
-      bh[kb][j] = __builtin_bit_cast(s16x8, u32x4{hi[0], hi[1], hi[2], hi[3]});
-    }
-  }
+  // ---- ram -> B fragments of GEMM2 ------------------------------------------------------------------------------------------------------
+  HeadFrags<false> bf;
+  head_ram_fragments<H, false>(acc1, sK, fq, bf, [](int, int, const uint32_t (&)[4]) {});
 
   __builtin_amdgcn_sched_barrier(0);      // acc1 is dead from here: keep the 128 registers of acc2 from being set up above this line
 
-  // ---- GEMM2: logit^T[bin][px], accumulators start at the conv_out bias ------------------------------------------------------------------
+  // ---- GEMM2 -----------------------------------------------------------------------------------------------------------------------------
   f32x4 acc2[16][2];
-#pragma unroll
-  for (int ti = 0; ti < 16; ++ti) {
-    float b4[4];
-    Vec<float>::load(sK + ti * 16 + fq * 4, b4);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc2[ti][j] = f32x4{b4[0], b4[1], b4[2], b4[3]};
-  }
-  auto gemm2_half = [&](int half, const unsigned char* base) {
-#pragma unroll
-    for (int kl = 0; kl < 2; ++kl) {
-      const int kb = half * 2 + kl;
-      const int pc = ((kl * 4 + fq) ^ (fr & 7)) * 16;
-#pragma unroll
-      for (int ti = 0; ti < 16; ++ti) {
-        const s16x8 af = *reinterpret_cast<const s16x8*>(base + (ti * 16 + fr) * 128 + pc);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc2[ti][j] = mfma16<H>(af, bh[kb][j], acc2[ti][j]);
-      }
-    }
-  };
-  gemm2_half(0, smem + HC_OFF_T);
-  hc_handover();                                           // Wout half 1 landed
-  gemm2_half(1, smem);
+  head_acc2_init(acc2, sK, fq);
+  head_gemm2_half<H, false>(acc2, bf, 0, smem + HC_OFF_T, false, fr, fq);
+  head_handover();                                         // Wout half 1 landed
+  head_gemm2_half<H, false>(acc2, bf, 1, smem, false, fr, fq);
   if (p.probe & 4) {
     if (tid == 0 && acc2[0][0][0] == 123.456f) p.pred[0] = acc2[15][1][3];
     return;
@@ -331,41 +272,10 @@ __global__ __launch_bounds__(512, 1) void depth_head_conv0_kernel(HeadC0P p) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int pl = wave * 32 + j * 16 + fr;                // pixel within the tile: row 2 wave + j, column fr
-    float mx = -3.0e38f;
-#pragma unroll
-    for (int ti = 0; ti < 16; ++ti)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) mx = fmaxf(mx, acc2[ti][j][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float s = 0.f;
-#pragma unroll
-    for (int ti = 0; ti < 16; ++ti)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float d = acc2[ti][j][r] - mx;
-        const float e = __expf(d);
-        acc2[ti][j][r] = e;
-        s += e;
-      }
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    const float inv = 1.f / s;
-    float dot = 0.f;
-#pragma unroll
-    for (int ti = 0; ti < 16; ++ti) {
-      float cen[4];
-      Vec<float>::load(sK + 512 + ti * 16 + fq * 4, cen);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float pr = acc2[ti][j][r] * inv;
-        dot = fmaf(pr, cen[r], dot);
-        if (prob) sP[(ti * 16 + fq * 4 + r) * HC_PPITCH + pl] = from_f32<H>(pr);
-      }
-    }
-    dot += __shfl_xor(dot, 16, 64);
-    dot += __shfl_xor(dot, 32, 64);
-    if (fq == 0) p.pred[(long long)b * p.HW + (y0 + 2 * wave + j) * p.W + x0 + fr] = dot;
+    // no STATS here: the moments it returns are zeros and go unused
+    head_softmax_column<H, false, HC_PPITCH>(acc2, j, sK + HEAD_K_CEN, prob != nullptr, sP + pl, fq, [&](float dot) {
+      if (fq == 0) p.pred[(long long)b * p.HW + (y0 + 2 * wave + j) * p.W + x0 + fr] = dot;
+    });
   }
   if (!prob) return;
   __syncthreads();

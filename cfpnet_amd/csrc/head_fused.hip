@@ -30,22 +30,22 @@
 //   * optional uncertainty planes (STATS, head_stats.h): t = sum e d in the exponential loop, the centred variance as a second walk over
 //     the exponentials in the accumulators and the centres in LDS (scaled by 1 / s at the end), stored by the lane quarters fq = 1, 2, 3
 //     beside fq = 0's pred.  A compile-time switch: the STATS = false kernels are the code they were.
-#include "common.h"
-#include "head_stats.h"
+//
+// Everything from the accumulators of GEMM1 on (ram -> B fragments, GEMM2, softmax, expectation, the STATS walk), the stage hand-over and the
+// Wout loader are head_core.h's, shared with head_conv0.hip; the main loop, the LDS map and every global address are this file's.
+#include "head_core.h"
 
 namespace {
 
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 constexpr int HF_BM = 128;              // pixels per workgroup
-constexpr int HF_C = 128;               // channels in / out of the 3x3 conv
-constexpr int HF_NB = 256;              // bins
+constexpr int HF_C = HEAD_C;            // channels in / out of the 3x3 conv
+constexpr int HF_NB = HEAD_NB;          // bins
 constexpr int HF_K = 9 * HF_C;
 constexpr int HF_STEPS = HF_K / 64;     // 18 K-steps
 constexpr int HF_STAGE = (HF_BM + HF_C) * 128;          // 32 KB: pixel rows + weight rows of one K-step
 constexpr int HF_PPITCH = HF_BM + 8;                    // prob staging pitch (elements)
 constexpr int HF_PBYTES = HF_NB * HF_PPITCH * 2;        // 69 632 B >= 2 stages: operand stages, later the prob staging tile
-constexpr int HF_CONST = 4 * 256 * 4;                   // 4 KB behind it: conv_out bias | conv3x3 scale, shift | bin centres of the tile's (two) images
+constexpr int HF_CONST = HEAD_K_BYTES;                  // 4 KB behind it: conv_out bias | conv3x3 scale, shift | bin centres of the tile's (two) images
 constexpr int HF_LDS = HF_PBYTES + HF_CONST;            // 72 KB: two workgroups per CU
 constexpr unsigned HF_OOB = 0x80000000u;
 static_assert(HF_PBYTES >= 2 * HF_STAGE, "prob staging must cover both operand stages");
@@ -60,22 +60,6 @@ struct HeadP {
   int probe;        // timing probes (tools/head_bench.py --probe): 1 = descriptors with zero records (no fetch), 2 = stop after GEMM1, 4 = stop after GEMM2
   float* stats;     // [B][3][HW] uncertainty planes (STATS kernels only; last, so that every other field keeps its kernel-argument offset)
 };
-
-#ifdef HF_GLDS
-__device__ __attribute__((aligned(16))) unsigned int g_hf_zero[4] = {0u, 0u, 0u, 0u};
-#endif
-// Stage hand-over: this wave's LDS-DMA loads have landed (vmcnt) AND its LDS-side operations have drained (lgkmcnt), then the
-// workgroup barrier.  With `s_waitcnt vmcnt(0)` + a raw s_barrier alone the kernel produced a wrong 32-pixel group (one wave's
-// pixels) about once per 640 forwards when three captured forwards ran concurrently -- never alone, never with same-input repeats
-// (tools/probes/inflight_race*.py, race_ab.sh: 5 / 3200 wrong results vs 0 / 3200 with this form): the zero words the hardware
-// writes for out-of-range lanes of a `buffer_load ... lds` are apparently not covered by vmcnt.  HF_RAW_BARRIER restores the old form.
-#ifdef HF_RAW_BARRIER
-#define HF_BARRIER() __builtin_amdgcn_s_barrier()
-template <int N> __device__ __forceinline__ void hf_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-#else
-#define HF_BARRIER() __syncthreads()
-template <int N> __device__ __forceinline__ void hf_wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory"); }
-#endif
 
 template <typename H, bool RAMLO, bool STATS>
 __global__ __launch_bounds__(256, 2) void depth_head_fused_kernel(HeadP p) {
@@ -124,23 +108,6 @@ __global__ __launch_bounds__(256, 2) void depth_head_fused_kernel(HeadP p) {
     unsigned char* sB = sA + HF_BM * 128;                  // weight rows
     const int tap = ks >> 1;                               // Cin = 128 = two K-steps per tap: all scalar
     const int kh = tap / 3, kw = tap - kh * 3;
-#ifdef HF_GLDS
-    {   // A/B variant: global_load_lds with a 64-bit pointer select against a zero word (the gen-2 GEMM's loader)
-      using gptr_t = const __attribute__((address_space(1))) void*;
-      const unsigned char* xt = reinterpret_cast<const unsigned char*>(p.x) + (long long)(((kh - 1) * p.W + (kw - 1)) * p.x_ld * 2 + (ks & 1) * 128);
-      const unsigned char* wk = reinterpret_cast<const unsigned char*>(p.w3) + ks * 128;
-      const unsigned bit2 = 1u << tap;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const unsigned char* src = (a_mask[i] & bit2) ? xt + a_off[i] : reinterpret_cast<const unsigned char*>(g_hf_zero);
-        __builtin_amdgcn_global_load_lds((gptr_t)src, (lds_ptr_t)(sA + (i * 4 + wave) * 1024), 16, 0, 0);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        __builtin_amdgcn_global_load_lds((gptr_t)(wk + b_off[j]), (lds_ptr_t)(sB + (j * 4 + wave) * 1024), 16, 0, 0);
-      return;
-    }
-#endif
     const unsigned soff = (unsigned)((kh * p.W + kw) * p.x_ld * 2 + (ks & 1) * 128);   // + guard - (W + 1) * ld * 2 = tap (kh-1, kw-1)
     const unsigned bit = 1u << tap;
 #pragma unroll
@@ -154,13 +121,7 @@ __global__ __launch_bounds__(256, 2) void depth_head_fused_kernel(HeadP p) {
   };
   // one half (64 permuted channels) of Wout -> a 32 KB stage: 256 rows of 128 bytes, 8 DMA instructions per wave
   auto issue_wout = [&](int half, int buf, int plane) {
-    unsigned char* dst = smem + buf * HF_STAGE;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      const int g = q * 4 + wave;                          // 8-row group
-      const unsigned v = (unsigned)(g * 8 + rsub) * (unsigned)(HF_C * 2) + (unsigned)lc * 16u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_o, (lds_ptr_t)(dst + g * 1024), 16, (int)v, half * 128 + plane * (HF_NB * HF_C * 2), 0, 0);
-    }
+    head_issue_wout<4>(rs_o, smem + buf * HF_STAGE, half * 128 + plane * (HF_NB * HF_C * 2), wave, rsub, lc);
   };
 
   f32x4 acc1[8][2];
@@ -172,21 +133,19 @@ __global__ __launch_bounds__(256, 2) void depth_head_fused_kernel(HeadP p) {
   issue(0, 0);
   // the per-channel / per-bin vectors the later phases need go to LDS now (their global latency hides behind K-step 0; read back
   // with ds_read_b128 when needed -- loading them where they are used cost three exposed global round trips per workgroup)
-  float* sK = reinterpret_cast<float*>(smem + HF_PBYTES);    // [0,256) bias_out | [256,384) scale3 | [384,512) shift3 | [512,768) centres(b0) | [768,1024) centres(b1)
+  float* sK = reinterpret_cast<float*>(smem + HF_PBYTES);    // head_core.h's constants block; its last quarter: the centres of the image the tile ends in
   const int img0 = m0 / p.HW;
   {
     const int img1 = min(p.B - 1, (min(m0 + HF_BM, p.M) - 1) / p.HW);
-    sK[tid] = p.bias_out[tid];
-    if (tid < 128) sK[256 + tid] = p.scale3 ? p.scale3[tid] : 1.f;
-    else sK[256 + tid] = p.shift3 ? p.shift3[tid - 128] : 0.f;
-    sK[512 + tid] = p.centers[(long long)img0 * HF_NB + tid];
-    sK[768 + tid] = p.centers[(long long)img1 * HF_NB + tid];
+    sK[HEAD_K_BIAS + tid] = p.bias_out[tid];
+    if (tid < 128) sK[HEAD_K_SCALE3 + tid] = p.scale3 ? p.scale3[tid] : 1.f;
+    else sK[HEAD_K_SHIFT3 + tid - 128] = p.shift3 ? p.shift3[tid - 128] : 0.f;
+    sK[HEAD_K_CEN + tid] = p.centers[(long long)img0 * HF_NB + tid];
+    sK[HEAD_K_CEN1 + tid] = p.centers[(long long)img1 * HF_NB + tid];
   }
   for (int ks = 0; ks < HF_STEPS; ++ks) {
     const int buf = ks & 1;
-    hf_wait_vmcnt<0>();
-    HF_BARRIER();                                          // stage `buf` landed for every wave; stage buf^1 fully consumed
-    asm volatile("" ::: "memory");
+    head_handover();                                       // stage `buf` landed for every wave; stage buf^1 fully consumed
     if (ks + 1 < HF_STEPS) issue(ks + 1, buf ^ 1);
     else issue_wout(0, buf ^ 1, 0);                        // the free stage receives Wout[:, first 64 channels]
     const unsigned char* cP = smem + buf * HF_STAGE + (wave * 32) * 128;    // this wave's 32 pixel rows
@@ -206,102 +165,48 @@ __global__ __launch_bounds__(256, 2) void depth_head_fused_kernel(HeadP p) {
     }
   }
   // HF_STEPS is even: the last K-step used stage 1, Wout half 0 is (being) written to stage 0
-  hf_wait_vmcnt<0>();
-  HF_BARRIER();                                            // stage 1 consumed by every wave; Wout half 0 landed
-  asm volatile("" ::: "memory");
+  head_handover();                                         // stage 1 consumed by every wave; Wout half 0 landed
   issue_wout(1, 1, 0);                                     // lands while GEMM2 runs on half 0
   if (p.probe & 2) {
-    hf_wait_vmcnt<0>();
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     if (tid == 0 && acc1[0][0][0] == 123.456f) p.pred[0] = acc1[7][1][3];
     return;
   }
 
-  // ---- ram = scale * acc + shift (depth_head.conv3x3 has a bias and no activation) -> B fragments of GEMM2 -------------------
-  s16x8 bh[4][2], bl[RAMLO ? 4 : 1][2];
+  // ---- ram -> B fragments of GEMM2 ----------------------------------------------------------------------------------------------
+  HeadFrags<RAMLO> bf;
   {
     H* ram_out = reinterpret_cast<H*>(p.ram_out);
+    head_ram_fragments<H, RAMLO>(acc1, sK, fq, bf, [&](int kb, int j, const uint32_t (&hi)[4]) {
+      if (ram_out) {                                       // test / tap hook: ram as the unfused path stores it
+        const int m = m0 + wave * 32 + j * 16 + fr;
+        if (m < p.M) {
 #pragma unroll
-    for (int kb = 0; kb < 4; ++kb) {
-      float sc[2][4], sh[2][4];
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int ch = (2 * kb + u) * 16 + fq * 4;
-        Vec<float>::load(sK + 256 + ch, sc[u]);
-        Vec<float>::load(sK + 384 + ch, sh[u]);
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) v[u * 4 + r] = acc1[2 * kb + u][j][r] * sc[u][r] + sh[u][r];
-        uint32_t hi[4], lo[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const H h0 = from_f32<H>(v[2 * e]), h1 = from_f32<H>(v[2 * e + 1]);
-          hi[e] = (uint32_t)to_bits<H>(h0) | ((uint32_t)to_bits<H>(h1) << 16);
-          lo[e] = pack2<H>(v[2 * e] - to_f32<H>(h0), v[2 * e + 1] - to_f32<H>(h1));
-        }
-        bh[kb][j] = __builtin_bit_cast(s16x8, u32x4{hi[0], hi[1], hi[2], hi[3]});
-        if constexpr (RAMLO) bl[kb][j] = __builtin_bit_cast(s16x8, u32x4{lo[0], lo[1], lo[2], lo[3]});
-        if (ram_out) {                                     // test / tap hook: ram as the unfused path stores it
-          const int m = m0 + wave * 32 + j * 16 + fr;
-          if (m < p.M) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-              uint2 w2 = {hi[2 * u], hi[2 * u + 1]};
-              *reinterpret_cast<uint2*>(ram_out + (long long)m * HF_C + (2 * kb + u) * 16 + fq * 4) = w2;
-            }
+          for (int u = 0; u < 2; ++u) {
+            uint2 w2 = {hi[2 * u], hi[2 * u + 1]};
+            *reinterpret_cast<uint2*>(ram_out + (long long)m * HF_C + (2 * kb + u) * 16 + fq * 4) = w2;
           }
         }
       }
-    }
+    });
   }
 
   __builtin_amdgcn_sched_barrier(0);      // acc1 is dead from here: keep the 128 registers of acc2 from being set up above this line
 
-  // ---- GEMM2: logit^T[bin][px], accumulators start at the conv_out bias ----------------------------------------------------------
+  // ---- GEMM2 ---------------------------------------------------------------------------------------------------------------------
   f32x4 acc2[16][2];
-#pragma unroll
-  for (int ti = 0; ti < 16; ++ti) {
-    float b4[4];
-    Vec<float>::load(sK + ti * 16 + fq * 4, b4);
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc2[ti][j] = f32x4{b4[0], b4[1], b4[2], b4[3]};
-  }
-  auto gemm2_half = [&](int half, const unsigned char* base, bool use_lo_b) {
-#pragma unroll
-    for (int kl = 0; kl < 2; ++kl) {
-      const int kb = half * 2 + kl;
-      const int pc = ((kl * 4 + fq) ^ (fr & 7)) * 16;
-#pragma unroll
-      for (int ti = 0; ti < 16; ++ti) {
-        const s16x8 af = *reinterpret_cast<const s16x8*>(base + (ti * 16 + fr) * 128 + pc);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc2[ti][j] = mfma16<H>(af, bh[kb][j], acc2[ti][j]);
-          if constexpr (RAMLO) { if (use_lo_b) acc2[ti][j] = mfma16<H>(af, bl[kb][j], acc2[ti][j]); }
-        }
-      }
-    }
-  };
+  head_acc2_init(acc2, sK, fq);
+  auto gemm2_half = [&](int half, const unsigned char* base, bool use_lo_b) { head_gemm2_half<H, RAMLO>(acc2, bf, half, base, use_lo_b, fr, fq); };
   constexpr bool ram_lo = RAMLO;
   gemm2_half(0, smem, ram_lo);
-  hf_wait_vmcnt<0>();
-  HF_BARRIER();                                            // Wout half 1 landed; every wave is done with half 0 (stage 0)
-  asm volatile("" ::: "memory");
+  head_handover();                                         // Wout half 1 landed; every wave is done with half 0 (stage 0)
   if (p.wout_lo) issue_wout(0, 0, 1);                      // lo plane of half 0 -> stage 0, during GEMM2 on half 1
   gemm2_half(1, smem + HF_STAGE, ram_lo);
   if (p.wout_lo) {                                         // Wout_lo * ram_hi: the lo plane only meets the hi fragments (lo * lo ~ 2^-22)
-    hf_wait_vmcnt<0>();
-    HF_BARRIER();
-    asm volatile("" ::: "memory");
+    head_handover();
     issue_wout(1, 1, 1);
     gemm2_half(0, smem, false);
-    hf_wait_vmcnt<0>();
-    HF_BARRIER();
-    asm volatile("" ::: "memory");
+    head_handover();
     gemm2_half(1, smem + HF_STAGE, false);
   }
   if (p.probe & 4) {
@@ -318,66 +223,15 @@ __global__ __launch_bounds__(256, 2) void depth_head_fused_kernel(HeadP p) {
     const int pl = wave * 32 + j * 16 + fr;                // pixel within the tile
     const int m = m0 + pl;
     const int bimg = min(m, p.M - 1) / p.HW;
-    float mx = -3.0e38f;
-#pragma unroll
-    for (int ti = 0; ti < 16; ++ti)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) mx = fmaxf(mx, acc2[ti][j][r]);
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float s = 0.f, t = 0.f;
-#pragma unroll
-    for (int ti = 0; ti < 16; ++ti)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float d = acc2[ti][j][r] - mx;
-        const float e = __expf(d);
-        acc2[ti][j][r] = e;
-        s += e;
-        if constexpr (STATS) t = fmaf(e, d, t);
-      }
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
+    const float* cen = sK + (bimg == img0 ? HEAD_K_CEN : HEAD_K_CEN1);
+    // the staging test stays on the per-lane pointer here: on the wave-uniform `prob` the allocator gave <bf16, RAMLO, !STATS> 156 bytes of
+    // scratch where the parent commit's kernel had 132, and this kernel's launches without prob are as fast as the parent's in this form
+    H* stage = prob ? sP + pl : nullptr;
+    const HeadMoments mo = head_softmax_column<H, STATS, HF_PPITCH>(acc2, j, cen, stage != nullptr, stage, fq, [&](float dot) {
+      if (fq == 0 && m < p.M) p.pred[m] = dot;
+    });
     if constexpr (STATS) {
-      t += __shfl_xor(t, 16, 64);
-      t += __shfl_xor(t, 32, 64);
-    }
-    const float inv = 1.f / s;
-    float ent = 0.f;
-    if constexpr (STATS) ent = unc_entropy(s, t, inv);
-    float dot = 0.f;
-#pragma unroll
-    for (int ti = 0; ti < 16; ++ti) {
-      float cen[4];
-      Vec<float>::load(sK + (bimg == img0 ? 512 : 768) + ti * 16 + fq * 4, cen);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float pr = acc2[ti][j][r] * inv;
-        dot = fmaf(pr, cen[r], dot);
-        if constexpr (!STATS) { if (prob) sP[(ti * 16 + fq * 4 + r) * HF_PPITCH + pl] = from_f32<H>(pr); }
-      }
-    }
-    dot += __shfl_xor(dot, 16, 64);
-    dot += __shfl_xor(dot, 32, 64);
-    if (fq == 0 && m < p.M) p.pred[m] = dot;
-    if constexpr (STATS) {
-      float var = 0.f;      // sum e (c - mu)^2: the accumulators hold the exponentials, 1 / s is applied once at the end
-#pragma unroll
-      for (int ti = 0; ti < 16; ++ti) {
-        float cen[4];
-        Vec<float>::load(sK + (bimg == img0 ? 512 : 768) + ti * 16 + fq * 4, cen);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float dc = cen[r] - dot;
-          var = fmaf(acc2[ti][j][r] * dc, dc, var);
-          // the staging store waits for this walk, where the accumulators die one by one as they do in the plain kernel's expectation
-          // loop: with it up there all 128 stay live across both loops and the allocator spills
-          if (prob) sP[(ti * 16 + fq * 4 + r) * HF_PPITCH + pl] = from_f32<H>(acc2[ti][j][r] * inv);
-        }
-      }
-      var += __shfl_xor(var, 16, 64);
-      var += __shfl_xor(var, 32, 64);
-      if (fq != 0 && m < p.M) p.stats[((long long)bimg * 3 + (fq - 1)) * p.HW + (m - bimg * p.HW)] = unc_plane(fq - 1, var * inv, ent, inv);
+      if (fq != 0 && m < p.M) p.stats[((long long)bimg * 3 + (fq - 1)) * p.HW + (m - bimg * p.HW)] = unc_plane(fq - 1, mo.var, mo.ent, mo.inv);
     }
   }
   if (!prob) return;
